@@ -12,11 +12,16 @@ the frame, plus ONE RCCL gather of the finished RGB band to rank 0 (strong scali
 Synthetic data: camera c2w=[I|(0,0,4)], fov 0.6911, near 2, far 6; random-init weights of the reference's
 architecture (default nn.Linear init / siren init / N(0,1) hash tables, seed 2).
 
-Prints ONE JSON line (rank 0).  `value` is Msamples/s over all ranks with everything already in HBM.  The line carries
-the precision modes on the same frame and `--steps` (the primary one -- f16x, the fastest mode within north_star's 1e-4 --
-in the top-level fields, BASELINE's named bf16 under `other_precision`, the f16-operand mode under `f16_precision`, the
-3-product bf16 split under `bf16x3_precision`), each with its own roofline object and its L-inf against the CPU oracle on
-the CPU-baseline tile.
+Prints ONE JSON line (rank 0).  `value` is Msamples/s over all ranks with everything already in HBM; `ms_per_step` is the
+wall time of one timed step.  A plain run sets up, warms up, times the `--steps` steps of the primary mode (f16x, the fastest
+mode within north_star's 1e-4) and prints the line.  `--dump-outputs DIR` writes the frame of the last timed step to
+DIR/rgb.npy (float32, 800 x 800 x 3).
+
+`--full` adds everything else, each on the same frame and `--steps`: BASELINE's named bf16 under `other_precision`, the
+f16-operand mode under `f16_precision`, the 3-product bf16 split under `bf16x3_precision`, each with its own roofline object
+and its L-inf against the CPU oracle on the CPU-baseline tile; the live HBM traffic of the primary mode, the clock under
+load, the other BASELINE configs, the training step, coarse -> fine, the CPU baseline; with N > 1 one GPU's whole-frame
+time and the scaling efficiency.  `--no-cpu-baseline`, `--no-other-configs` and `--no-traffic` trim a `--full` run.
 """
 import argparse
 import json
@@ -451,11 +456,16 @@ def main():
     # mode) under `bf16x3_precision`.
     ap.add_argument("--precision", default=None, choices=["bf16", "bf16x3", "f16", "f16x"])
     ap.add_argument("--engine", default=None, choices=["ls", "reg"], help="fused renderer engine (default: config.engine)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the slab timings of BASELINE configs 1, 3, 4, 5")
-    ap.add_argument("--no-traffic", action="store_true", help="do not measure roofline.traffic live (two rocprofv3 --pmc child runs, ~1 min)")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the other precision modes, configs, training step and CPU baseline, and measure traffic, clock and scaling")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's frame to DIR/rgb.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity against it")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the slab timings of BASELINE configs 1, 3, 4, 5")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: do not measure roofline.traffic live (rocprofv3 --pmc child runs, ~1 min)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)  # the child of measure_traffic: primary mode only, no JSON
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.engine == "reg" and args.precision in ("f16", "f16x"):
         ap.error(f"--precision {args.precision} exists on the layer-synchronous engine only (--engine ls)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -561,7 +571,7 @@ def main():
                 # doubled per MI355X_MICROARCH.md "HBM"); None when the shard differs from the profiled full frame
                 "traffic": HBM_TRAFFIC_FULL_FRAME.get((engine, prec)) if world == 1 else None,
                 "traffic_unit": "bytes/launch",
-                # (an earlier profile's figure; the primary mode's is replaced by a live measurement: measure_traffic)
+                # (an earlier profile's figure; with --full the primary mode's is replaced by a live measurement: measure_traffic)
                 "traffic_source": TRAFFIC_SOURCE.get((engine, prec)) if world == 1 else None}
 
     prec = args.precision
@@ -571,21 +581,26 @@ def main():
     dt, kern_ms, gath_ms, per_rank, frame = timed(prec, args.steps, args.warmup)
     # (now: with N > 1 `frame` is the gather's persistent receive buffer, which the next timed() call overwrites)
     checksum = round(float(frame.double().sum()), 3) if frame is not None else None
+    if args.dump_outputs and frame is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "rgb.npy"), frame.float().cpu().numpy())
     other = "bf16x3" if prec == "bf16" else "bf16"
-    dt2, kern2_ms, _, _, _ = timed(other, args.steps, 1)
     # third line: the f16-operand mode of the layer-synchronous engine (the fast mode's speed class, 11-bit operands)
-    third = "f16" if (engine == "ls" and "f16" not in (prec, other)) else None
+    third = "f16" if (args.full and engine == "ls" and "f16" not in (prec, other)) else None
+    # fourth: the other parity mode (3-product bf16 split) when the primary one is f16x
+    fourth = "bf16x3" if (args.full and "bf16x3" not in (prec, other)) else None
+    if args.full:
+        dt2, kern2_ms, _, _, _ = timed(other, args.steps, 1)
     if third is not None:
         dt3, kern3_ms, _, _, _ = timed(third, args.steps, 1)
-    # fourth: the other parity mode (3-product bf16 split) when the primary one is f16x
-    fourth = "bf16x3" if "bf16x3" not in (prec, other) else None
     if fourth is not None:
         dt4, kern4_ms, _, _, _ = timed(fourth, args.steps, 1)
 
     # N > 1: what one GPU needs for the WHOLE frame, measured in this very run on rank 0 after the timed regions (the other
     # ranks wait at the final barrier), so that the line explains itself: scaling_efficiency = that / (N x slowest rank's kernel)
     full_frame_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         if rank == 0:
             ws_full = torch.empty(max(int(lib.na_render_workspace_bytes(STEPS_PER_RAY, SIZE * SIZE)),
                                       int(lib.na_render_ls_workspace_bytes(STEPS_PER_RAY, SIZE * SIZE))), device=dev, dtype=torch.uint8)
@@ -610,7 +625,7 @@ def main():
         samples = SIZE * SIZE * STEPS_PER_RAY
         value = samples * args.steps / dt / 1e6
         primary_roofline = roofline(prec, kern_ms)
-        if world == 1 and not args.no_traffic:
+        if args.full and world == 1 and not args.no_traffic:
             t_live, t_src, mfma_busy = measure_traffic(prec, engine, primary_roofline["kernel"])
             # ONE method: the live PMC child passes of this very command, or null with the reason -- an earlier
             # profile's constant is never substituted for the primary mode
@@ -638,7 +653,7 @@ def main():
             res["scaling_efficiency"] = round(full_frame_ms / (world * kern_ms), 4)   # kernel time only; `value` also pays the gather
         if checksum is not None:
             res["config"]["frame_checksum"] = checksum
-        if world == 1:
+        if args.full and world == 1:
             rays_full = ops.raygen(c2w, focal, SIZE, (r0, 0, nrows, SIZE))
             rfn = renderer(prec)
             clk = clock_under_load(lambda: rfn(rays_full))
@@ -647,9 +662,10 @@ def main():
                 # MAC/clk x 2): an extra key -- `roofline.frac` stays priced against the nominal peak
                 clk["frac_of_mfma_peak_at_this_clock"] = round(res["roofline"]["frac"] * 2400.0 / clk["sclk_mhz"], 4)
                 res["clock_under_load"] = clk
-        res["other_precision"] = {"precision": other, "dtype": DTYPE_NAME[other], "value": round(samples * args.steps / dt2 / 1e6, 2),
-                                  "unit": "Msamples/s", "steps": args.steps, "ms_per_step": round(dt2 / args.steps * 1e3, 3),
-                                  "roofline": roofline(other, kern2_ms)}
+        if args.full:
+            res["other_precision"] = {"precision": other, "dtype": DTYPE_NAME[other], "value": round(samples * args.steps / dt2 / 1e6, 2),
+                                      "unit": "Msamples/s", "steps": args.steps, "ms_per_step": round(dt2 / args.steps * 1e3, 3),
+                                      "roofline": roofline(other, kern2_ms)}
         if third is not None:
             res["f16_precision"] = {"precision": third, "dtype": DTYPE_NAME[third], "value": round(samples * args.steps / dt3 / 1e6, 2),
                                     "unit": "Msamples/s", "steps": args.steps, "ms_per_step": round(dt3 / args.steps * 1e3, 3),
@@ -658,12 +674,12 @@ def main():
             res["bf16x3_precision"] = {"precision": fourth, "dtype": DTYPE_NAME[fourth], "value": round(samples * args.steps / dt4 / 1e6, 2),
                                        "unit": "Msamples/s", "steps": args.steps, "ms_per_step": round(dt4 / args.steps * 1e3, 3),
                                        "roofline": roofline(fourth, kern4_ms)}
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             res["other_configs"], res["other_configs_s"], res["outside_tolerance"] = other_configs(dev)
             res["train_step"] = train_step(dev)
             res["train_step_1m"] = train_step(dev, crop=128, iters=5)
             res["coarse_fine"] = coarse_fine(dev, ops.raygen(c2w, focal, SIZE, (0, 0, SIZE, SIZE)))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, ref, rays_cpu = cpu_baseline(model)
             res["cpu_baseline"] = cb
             # same tile through the HIP path: the benchmarked kernels are the parity-checked ones

@@ -5,17 +5,18 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(gpus, extra_env=None):
+def _bench(gpus, extra_env=None, args=("--full", "--no-cpu-baseline", "--no-other-configs", "--no-traffic")):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(extra_env or {})
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-other-configs", "--no-traffic"], env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", *args],
+                       env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]  # ONE JSON line, from rank 0
@@ -40,3 +41,15 @@ def test_bench_spawns_its_own_ranks():
     # ONE GPU time-share it, so the number itself only has to be sane here: ~0.5 when the launches serialise, up to 1.)
     assert "scaling_efficiency" not in one
     assert two["single_gpu_full_frame_kernel_ms"] > 0 and 0.2 < two["scaling_efficiency"] <= 1.1
+
+
+def test_plain_bench_line_and_dumped_frame(tmp_path):
+    """A plain run times the primary mode only and, with --dump-outputs, writes the frame of its last timed step."""
+    line = _bench(1, args=("--dump-outputs", str(tmp_path)))
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"].startswith("f16x")
+    for key in ("other_precision", "f16_precision", "bf16x3_precision", "clock_under_load", "other_configs", "cpu_baseline"):
+        assert key not in line
+    rgb = np.load(tmp_path / "rgb.npy")
+    assert rgb.dtype == np.float32 and rgb.shape == (800, 800, 3) and np.isfinite(rgb).all()
+    assert abs(float(rgb.astype(np.float64).sum()) - line["config"]["frame_checksum"]) <= 1e-3
