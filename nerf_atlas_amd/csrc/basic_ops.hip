@@ -196,19 +196,14 @@ __global__ void compute_pts_kernel(const float* __restrict__ rays, const float* 
 // src/neural_blocks.py:139-193.  One thread per (sample, level): 8 float4 gathers from a 1 MiB table.
 // Streaming stores for outputs that are written once, are far larger than any cache and are read by ANOTHER kernel (encoder
 // rows: 140-256 bytes per sample, gigabytes per frame tile): non-temporal stores leave the L2 / memory-side cache alone and
-// took hash_encode from 1.74 ms to 1.05-1.19 ms per 20 M samples (1.8 -> 2.6-3.0 TB/s).  NA_STREAM_NT=0 switches them off.
-#ifndef NA_STREAM_NT
-#define NA_STREAM_NT 1
-#endif
+// took hash_encode from 1.74 ms to 1.05-1.19 ms per 20 M samples (1.8 -> 2.6-3.0 TB/s).
 typedef float stream_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void stream_store4(float* dst, float a, float b, float c, float d) {
   const stream_f32x4 v = {a, b, c, d};
-  if (NA_STREAM_NT) __builtin_nontemporal_store(v, (stream_f32x4*)dst);
-  else *(stream_f32x4*)dst = v;
+  __builtin_nontemporal_store(v, (stream_f32x4*)dst);
 }
 __device__ __forceinline__ void stream_store1(float* dst, float a) {
-  if (NA_STREAM_NT) __builtin_nontemporal_store(a, dst);
-  else *dst = a;
+  __builtin_nontemporal_store(a, dst);
 }
 // lead = 1: the row starts with one more copy of x -- [x | x | features], the init row cat([p, enc(p)]) of a hash-encoded
 // SkipConnMLP (src/neural_blocks.py:283-287) written by the encoder itself (training: no cat launch, round 6)

@@ -204,22 +204,6 @@ __device__ __forceinline__ float mip_feature(float m0, float m1, float m2, float
   return damp * sin_cw(6.283185307179586f * rev + delta);
 }
 
-// cos on the same reduction: even Taylor polynomial to r^10 on [-pi/2,pi/2] (max |err| 5e-7), sign by parity.
-__device__ __forceinline__ float cos_cw(float x) {
-  float q = rintf(x * 0.318309886183790672f);
-  float r = fmaf(q, -3.140625f, x);
-  r = fmaf(q, -9.67502593994140625e-4f, r);
-  r = fmaf(q, -1.509957990978376432e-7f, r);
-  float r2 = r * r;
-  float p = fmaf(r2, -2.7557319224e-07f, 2.4801587302e-05f);
-  p = fmaf(p, r2, -1.3888888889e-03f);
-  p = fmaf(p, r2, 4.1666666667e-02f);
-  p = fmaf(p, r2, -0.5f);
-  float c = fmaf(p, r2, 1.0f);
-  int qi = (int)q;
-  return (qi & 1) ? -c : c;
-}
-
 // sin and cos on one shared reduction (Fourier-feature prologue: 2 x 128 of them per sample)
 __device__ __forceinline__ void sincos_cw(float x, float& sn, float& cs) {
   float q = rintf(x * 0.318309886183790672f);

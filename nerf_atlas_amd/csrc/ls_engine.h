@@ -13,9 +13,6 @@
 #endif
 // NA_LS_TRACE: waves 0 and 4 of workgroup 0 stamp s_memtime before and after every barrier of their second pass
 // (tools/ls_trace.py).  Timing experiments only.
-#ifndef NA_LS_MIP_ABLATE
-#define NA_LS_MIP_ABLATE 0  // experiments (tools/ls_variant.py): 1 = MODEL 6 without its IPE generation (wrong output, timing only)
-#endif
 #ifndef NA_LS_TRACE
 #define NA_LS_TRACE 0
 #endif
@@ -83,14 +80,8 @@ constexpr int kPartialFloats = 8;
 //   halves of the K64 group sit in sixteen consecutive registers), so its slot order is the fragments' element order
 //   (slot 8 c + e <-> chunk c, element e) and the activation side packs the residual plane R in that order.  The MFMA phase
 //   is bound by the 64 B/clk the vector memory path delivers per CU (a record feeds 24 MFMAs = 768 cycles; four waves x
-//   14.25 KiB were 912 cycles of that path, 11.25 KiB are 720), so every byte counts.
-#ifndef NA_LSX_PRIO
-#define NA_LSX_PRIO 0  // experiments: 0 the MFMA phases run at s_setprio 1 (like the other precisions), 1 no priorities, 2 the epilogues
-#endif
-#ifndef NA_LSX_EXP
-#define NA_LSX_EXP 0  // timing experiments (tools/ls_variant.py): 2 no fp6 loads, 4 no f16 refills,
-                     // 8 no LDS reads of the T plane, 16 no LDS writes of the T plane, 32 no WT6 derivation
-#endif
+//   14.25 KiB were 912 cycles of that path, 11.25 KiB are 720), so every byte counts.  The MFMA phases run at s_setprio 1, like
+//   the other precisions.
 namespace x {
 constexpr int KQ = 4096 + 2 * 2048;          // LDS bytes per (block, K64 group)
 constexpr int BLKH = 4 * KQ;                 // hidden activations of one block (32 KiB)
@@ -198,17 +189,15 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 // it, writes the launch's id here, and a tiny kernel behind the renderer turns the WHOLE frame into NaN when it finds its id
 // (stream-ordered, no host synchronisation; ids instead of a reset: nothing to zero between launches).  Silence is never an
 // option for the parity mode: switch to bf16x3 (fp32 range) for such weights.  tests/test_gpu_range.py.
-// Round 5: the flag is PER LAUNCH, not per device -- a ring of NA_LSX_SAT_SLOTS words, launch id g owns slot g % SLOTS and a
+// Round 5: the flag is PER LAUNCH, not per device -- a ring of kSatSlots words, launch id g owns slot g % kSatSlots and a
 // slot only ever matches the exact id, so two f16x launches in flight on different streams of one device cannot mask each
 // other (one word, last writer wins, did: the earlier launch's poison pass found the later launch's id and left a clamped
 // frame).  Two launches share a slot only if their ids are a multiple of 256 apart AND both are in flight at once; a renderer
 // launch fills the chip (256 persistent workgroups), so 256 of them in flight is not a state the library can be driven into.
-#ifndef NA_LSX_SAT_SLOTS  // (-DNA_LSX_SAT_SLOTS=1 rebuilds round 4's single word: tests/test_gpu_range.py's two-stream test then fails)
-#define NA_LSX_SAT_SLOTS 256
-#endif
-static __device__ unsigned int g_lsx_saturated[NA_LSX_SAT_SLOTS] = {};
+constexpr int kSatSlots = 256;
+static __device__ unsigned int g_lsx_saturated[kSatSlots] = {};
 static __global__ void lsx_poison_kernel(uint32_t gen, float* __restrict__ out, int64_t n) {
-  if (g_lsx_saturated[gen % NA_LSX_SAT_SLOTS] != gen) return;
+  if (g_lsx_saturated[gen % kSatSlots] != gen) return;
   const float nan = __builtin_nanf("");
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = nan;
 }
@@ -297,10 +286,6 @@ __device__ __forceinline__ void mma_c(f32x16& acc, const f32x16& cin, const Frag
 __device__ __forceinline__ f32x16 bias_tile(__amdgpu_buffer_rsrc_t rs, int bias_soff, int slot, int lane) {
   const int voff = (lane >> 5) * 64;
   f32x16 a;
-#if defined(NA_LS_TRAIN_EXP) && (NA_LS_TRAIN_EXP & 16)  // timing experiment (wrong values): no bias loads at all
-  for (int q = 0; q < 16; ++q) a[q] = 0.f;
-  return a;
-#endif
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, bias_soff + slot * 128 + q * 16, 0));
@@ -587,7 +572,7 @@ template <int I0, int N, int NB, bool TAIL = false>
 __device__ __forceinline__ void pairs(f32x16 (&acc)[2][NB], const f32x16 (&cb)[2], Regs& R, __amdgpu_buffer_rsrc_t rs, int xbase,
                                       const char* ib, int lane) {
   constexpr int PREC = NA_PREC_F16X, FR = 2048;
-  if (NA_LSX_PRIO == 0) __builtin_amdgcn_s_setprio(1);
+  __builtin_amdgcn_s_setprio(1);
   Frag<PREC> Bq[2][NB];
 #pragma unroll
   for (int b = 0; b < NB; ++b) Bq[0][b] = fread<PREC>(ib + (b * 4) * FR + lane * 16);
@@ -614,7 +599,7 @@ __device__ __forceinline__ void pairs(f32x16 (&acc)[2][NB], const f32x16 (&cb)[2
     if (q + 2 < N + (TAIL ? 1 : 0)) R.pr[i & 1] = wpair(rs, lane, xbase, i + 2);  // (the phase's own pairs only, TAIL: + geometry)
     __builtin_amdgcn_sched_barrier(0);
   }
-  if (NA_LSX_PRIO == 0) __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_s_setprio(0);
 }
 // the first two pairs of the NEXT pair phase: issued at the end of the epilogue in front of it (holding them across the
 // epilogues of the hidden layers costs 32 registers the residual / fp6 conversion needs)
@@ -628,14 +613,14 @@ template <int I, int NB, class GeoRawT, class GeoMake>
 __device__ __forceinline__ void geo_pair(f32x16 (&acc)[2][NB], Regs& R, __amdgpu_buffer_rsrc_t rs, int xbase, int lane,
                                          const GeoRawT (&graw)[NB], GeoMake geo_make, bool act) {
   constexpr int PREC = NA_PREC_F16X;
-  if (NA_LSX_PRIO == 0) __builtin_amdgcn_s_setprio(1);
+  __builtin_amdgcn_s_setprio(1);
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const Frag<PREC> B = geo_make(b, graw[b], act);
     mma<PREC>(acc[0][b], R.pr[I & 1].t0, B);
     mma<PREC>(acc[1][b], R.pr[I & 1].t1, B);
   }
-  if (NA_LSX_PRIO == 0) __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_s_setprio(0);
 }
 
 // ---- NG records starting at record rec0: per K64 group the f16 chunks, then the two fp6 correction products.  NT tiles (2:
@@ -648,7 +633,7 @@ template <int NT, int NBk, bool CB, int NREC, int NG = 4, int G0 = 0, int PAR0 =
           int NCHL = 4, int NTAIL = 1>  // NCHL: live f16 chunks of the call's last NTAIL records (MODEL 6: an IPE group fills three)
 __device__ __forceinline__ void recs(f32x16 (&acc)[NT][NBk], const f32x16 (&cb)[NT], Regs& R, __amdgpu_buffer_rsrc_t rs, int xrec,
                                      int rec0, const char* hb0, int lane, const char* ib0 = nullptr) {
-  if (NA_LSX_PRIO == 0) __builtin_amdgcn_s_setprio(1);
+  __builtin_amdgcn_s_setprio(1);
   auto gbase = [&](int gi, int b) -> const char* {  // K64 group gi of this call, block b
     if (G0 != 0 && gi == 0) return ib0 + b * KQ;
     return hb0 + b * BSTR + (gi - G0) * KQ;  // (BSTR: MODEL 6 parks the two IPE groups of block b at groups 2 b, 2 b + 1 of block 0)
@@ -676,7 +661,7 @@ __device__ __forceinline__ void recs(f32x16 (&acc)[NT][NBk], const f32x16 (&cb)[
     const int asc = R.asc[(PAR0 + gi) & 1];
     // (LAST0: a schedule with an ODD number of records per pass -- the record behind this call's last one is record 0 of the next
     // pass, whose scale belongs in slot 0 although the parity says 1; `asc` above was read first)
-    if (!(NA_LSX_EXP & 2)) R.asc[(LAST0 && gi == NG - 1) ? 0 : (PAR0 + gi + 1) & 1] = wloadsc(rs, lane, noff);
+    R.asc[(LAST0 && gi == NG - 1) ? 0 : (PAR0 + gi + 1) & 1] = wloadsc(rs, lane, noff);
     i32x6 wt[NT];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -690,7 +675,7 @@ __device__ __forceinline__ void recs(f32x16 (&acc)[NT][NBk], const f32x16 (&cb)[
       }
       if (c == 1) {  // this group's fp6 B operands: two chunks of lead
 #pragma unroll
-        for (int b = 0; b < NBk; ++b) { B6[b][0] = b6(b, gi, 0); B6[b][1] = (NA_LSX_EXP & 8) ? B6[b][0] : b6(b, gi, 1); }
+        for (int b = 0; b < NBk; ++b) { B6[b][0] = b6(b, gi, 0); B6[b][1] = b6(b, gi, 1); }
       }
       __builtin_amdgcn_sched_barrier(0);
       const f16x8 A0 = a16frag(R.a16[0], c), A1 = a16frag(R.a16[1], c);
@@ -703,8 +688,7 @@ __device__ __forceinline__ void recs(f32x16 (&acc)[NT][NBk], const f32x16 (&cb)[
         if (c == 1 && b == 0) {
           __builtin_amdgcn_sched_barrier(0);
           const float sc = __builtin_bit_cast(float, (((uint32_t)asc >> 8) & 0xFFu) << 23);
-          wt[0] = (NA_LSX_EXP & 32) ? i32x6{(int)R.a16[0][0], (int)R.a16[0][1], (int)R.a16[0][2], (int)R.a16[0][3], (int)R.a16[0][4], (int)R.a16[0][5]}
-                                    : cvt_fp6_f16_disjoint(R.a16[0], sc);
+          wt[0] = cvt_fp6_f16_disjoint(R.a16[0], sc);
           __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (NT == 2) {
@@ -712,12 +696,11 @@ __device__ __forceinline__ void recs(f32x16 (&acc)[NT][NBk], const f32x16 (&cb)[
           if (c == 1 && b == 0) {
             __builtin_amdgcn_sched_barrier(0);
             const float sc = __builtin_bit_cast(float, (((uint32_t)asc >> 24) & 0xFFu) << 23);
-            wt[NT - 1] = (NA_LSX_EXP & 32) ? i32x6{(int)R.a16[1][0], (int)R.a16[1][1], (int)R.a16[1][2], (int)R.a16[1][3], (int)R.a16[1][4], (int)R.a16[1][5]}
-                                           : cvt_fp6_f16_disjoint(R.a16[1], sc);
+            wt[NT - 1] = cvt_fp6_f16_disjoint(R.a16[1], sc);
             __builtin_amdgcn_sched_barrier(0);
           }
         }
-        if (b == NBk - 1 && c >= 1 && !(NA_LSX_EXP & 4)) {  // (behind the chunk's last MFMA: chunks 0 and 1 only once WT6 exists)
+        if (b == NBk - 1 && c >= 1) {  // (behind the chunk's last MFMA: chunks 0 and 1 only once WT6 exists)
           if (c == 1) {
             a16set(R.a16[0], 0, wload16(rs, lane, noff, 0, 0));
             a16set(R.a16[1], 0, wload16(rs, lane, noff, 1, 0));
@@ -740,20 +723,17 @@ __device__ __forceinline__ void recs(f32x16 (&acc)[NT][NBk], const f32x16 (&cb)[
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (!(NA_LSX_EXP & 2)) R.a6 = wload6(rs, lane, noff);
+    R.a6 = wload6(rs, lane, noff);
     __builtin_amdgcn_sched_barrier(0);
   }
-  if (NA_LSX_PRIO == 0) __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_s_setprio(0);
 }
 
 // v_cvt_scalef32_2xpk16_fp6_f32 writes its six destination registers while it still reads its scale and the tails of its
 // sources (tools/hw/cvt_fp6_overlap.hip), and the compiler's builtin does not say so: this form marks the destination
 // early-clobber, i.e. disjoint from every operand.  (The builtin form lets the allocator put the destination on the first six
-// registers of a source, which the hardware handles and which saves six registers; nerf_atlas_amd/build.py checks every
-// instance of the listing either way.)
-#ifndef NA_LSX_CVT_ASM
-#define NA_LSX_CVT_ASM 1  // the activation stores of the render kernel: 1 early-clobber asm (450 against 454 Msamples/s, same frame bit for bit), 0 builtin
-#endif
+// registers of a source, which the hardware handles and which saves six registers: 454 against 450 Msamples/s, the same frame
+// bit for bit; nerf_atlas_amd/build.py checks every instance of the listing either way.)
 __device__ __forceinline__ i32x6 cvt_fp6_disjoint(const f32x16& a, const f32x16& b, float scale) {
   i32x6 d;
   asm("v_cvt_scalef32_2xpk16_fp6_f32 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(scale));
@@ -804,7 +784,7 @@ __device__ __forceinline__ void store_block(char* kq, const f32x16& a0, const f3
     const int ev = (int)(__builtin_bit_cast(uint32_t, m) >> 23);
     eT = ev > 3 ? ev - 2 : 1;
     eR = ev > 14 ? ev - 13 : 1;
-    if (__builtin_expect(!(m < 65504.0f), 0)) g_lsx_saturated[sat_gen % NA_LSX_SAT_SLOTS] = sat_gen;  // an activation sits at the half clamp (or is NaN)
+    if (__builtin_expect(!(m < 65504.0f), 0)) g_lsx_saturated[sat_gen % kSatSlots] = sat_gen;  // an activation sits at the half clamp (or is NaN)
   }
   const float sT = __builtin_bit_cast(float, (uint32_t)eT << 23);
   const float sR = __builtin_bit_cast(float, (uint32_t)eR << 23);
@@ -825,19 +805,17 @@ __device__ __forceinline__ void store_block(char* kq, const f32x16& a0, const f3
   }
   // v_cvt_scalef32_2xpk16_fp6_f32 divides by the scale's power of two, rounds to nearest even, saturates, and puts a[i] into
   // slot 2 i, b[i] into slot 2 i + 1 (probed on the hardware by the round-3 prototype: profiles/r03/f16x_proto_v1.log)
-  const i32x6 Rr = NA_LSX_CVT_ASM ? cvt_fp6_disjoint(r0, r1, sR) : __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(r0, r1, sR);
-  const i32x6 Tt = NA_LSX_CVT_ASM ? cvt_fp6_disjoint(v0, v1, sT) : __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(v0, v1, sT);
+  const i32x6 Rr = cvt_fp6_disjoint(r0, r1, sR);
+  const i32x6 Tt = cvt_fp6_disjoint(v0, v1, sT);
   char* p = kq + 4096 + lane * 16;
   *(u32x4*)p = u32x4{(uint32_t)Rr[0], (uint32_t)Rr[1], (uint32_t)Rr[2], (uint32_t)Rr[3]};
   *(u32x4*)(p + 1024) = u32x4{(uint32_t)Rr[4], (uint32_t)Rr[5], (uint32_t)eR, 0u};
-  if (!(NA_LSX_EXP & 16)) {
-    *(u32x4*)(p + 2048) = u32x4{(uint32_t)Tt[0], (uint32_t)Tt[1], (uint32_t)Tt[2], (uint32_t)Tt[3]};
-    if constexpr (KEEP7) {
-      typedef __attribute__((ext_vector_type(3))) uint32_t u32x3;
-      *(u32x3*)(p + 3072) = u32x3{(uint32_t)Tt[4], (uint32_t)Tt[5], (uint32_t)eT};
-    } else {
-      *(u32x4*)(p + 3072) = u32x4{(uint32_t)Tt[4], (uint32_t)Tt[5], (uint32_t)eT, 0u};
-    }
+  *(u32x4*)(p + 2048) = u32x4{(uint32_t)Tt[0], (uint32_t)Tt[1], (uint32_t)Tt[2], (uint32_t)Tt[3]};
+  if constexpr (KEEP7) {
+    typedef __attribute__((ext_vector_type(3))) uint32_t u32x3;
+    *(u32x3*)(p + 3072) = u32x3{(uint32_t)Tt[4], (uint32_t)Tt[5], (uint32_t)eT};
+  } else {
+    *(u32x4*)(p + 3072) = u32x4{(uint32_t)Tt[4], (uint32_t)Tt[5], (uint32_t)eT, 0u};
   }
 }
 // the latent rows (no activation in front of them: to_elem clamps them to the half range) are checked the same way
@@ -847,16 +825,14 @@ __device__ __forceinline__ void latent_range(const f32x16& v_in, uint32_t sat_ge
   float m = 0.f;
 #pragma unroll
   for (int r = 0; r < 16; r += 2) asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(m) : "v"(v[r]), "v"(v[r + 1]));
-  if (__builtin_expect(!(m < 65504.0f), 0)) g_lsx_saturated[sat_gen % NA_LSX_SAT_SLOTS] = sat_gen;
+  if (__builtin_expect(!(m < 65504.0f), 0)) g_lsx_saturated[sat_gen % kSatSlots] = sat_gen;
 }
 // (blocks B0 .. B1 - 1: an epilogue that also re-enters an init group stores block 0, converts the group -- whose raw values
 // wait in the wave's K64 region of block 1 -- with half of the accumulators already dead, then stores block 1)
 template <int ACT, int NB, int B0 = 0, int B1 = NB>
 __device__ __forceinline__ void store_acts(const f32x16 (&acc)[2][NB], char* hb, int rg, int lane, uint32_t sat_gen) {
-  if (NA_LSX_PRIO == 2) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
   for (int b = B0; b < B1; ++b) store_block<ACT>(hb + b * BLKH + rg * KQ, acc[0][b], acc[1][b], lane, sat_gen);
-  if (NA_LSX_PRIO == 2) __builtin_amdgcn_s_setprio(0);
 }
 }  // namespace x
 

@@ -5,18 +5,11 @@
 #pragma once
 #include "ls_engine.h"
 
-#ifndef NA_LS_TRAIN_EXP
-#define NA_LS_TRAIN_EXP 0  // timing experiments on MODEL 9 (tools/ls_variant.py; wrong or missing rows): 1 no plane stores, 2 the LDS staging
-                           // alone, 4 the store instructions into a 64-KiB window (no HBM stream), 16 no bias loads.  1 048 576 samples, one
-                           // box: 1: 3.20 ms, 2: 3.28, 4: 3.42, shipped 4.08 -- the staging costs 2.5 %, the instructions 4 %, the stream the rest
-#endif
-#ifndef NA_LS_TRAIN_AUX
-// cache policy of MODEL 9's row stores: 2 = nt (non-temporal).  The 2.7 GB a step writes otherwise pass through the L2 that holds the
-// weight stream and the hash tables: measured (one box, 262 144 / 1 048 576 samples) 0: 1.27 / 4.93 ms, 2: 1.12 / 4.00, 17 (sc0 sc1): 1.23 / 4.62
-#define NA_LS_TRAIN_AUX 2
-#endif
 namespace na {
 namespace ls {
+// cache policy of MODEL 9's row stores: 2 = nt (non-temporal).  The 2.7 GB a step writes otherwise pass through the L2 that holds the
+// weight stream and the hash tables: measured (one box, 262 144 / 1 048 576 samples) 0: 1.27 / 4.93 ms, 2: 1.12 / 4.00, 17 (sc0 sc1): 1.23 / 4.62
+constexpr int kTrainStoreAux = 2;
 
 template <int PREC, int MODEL = 0>
 __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
@@ -441,7 +434,7 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
     }
   };
   auto gen_ipe = [&](auto act_tag) {
-    if constexpr (MIP && PREC == NA_PREC_F16X && !(NA_LS_MIP_ABLATE & 1)) {
+    if constexpr (MIP && PREC == NA_PREC_F16X) {
       constexpr int ACT = decltype(act_tag)::value;
       const int g = rg & 1, b = rg >> 1;  // this wave's unit (NB = 2)
       float ry[6], rad = 0.f;
@@ -703,11 +696,12 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
       // tile's two activation fragments anyway (dead since the barrier that closed the MFMA phase; nobody else writes it): sample-major
       // [32][128 B], 16-byte piece q of sample s at slot q ^ (s & 7) -- conflict-free for the 8-lane groups of ds_write_b128 and the
       // 16-lane groups of ds_read_b128 (MI355X_MICROARCH "LDS").  LDS operations of one wave execute in order: no wait in between.
+      // (Ablated, 1 048 576 samples: of the 4.08 ms the staging costs 2.5 %, the store instructions 4 %, the HBM stream the rest.)
       const int s0 = lane >> 3, pc = lane & 7;
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         const Loc L = locate(pl, b);
-        if (!L.ok || (NA_LS_TRAIN_EXP & 1)) continue;
+        if (!L.ok) continue;
         const int t0 = L.tb * 32 + s0;
         const uint32_t vo = (uint32_t)((int64_t)t0 * a.R + L.ray) * 1024u + (uint32_t)(rg * 256 + pc * 16);
         const uint32_t step = (uint32_t)a.R * 8192u;  // 8 samples on
@@ -720,13 +714,7 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const f32x4 v = *(const f32x4*)(stg + (8 * k + s0) * 128 + ((pc ^ (s0 & 7)) * 16));
-#if NA_LS_TRAIN_EXP & 2   // (timing: the LDS staging alone -- the values are consumed, nothing is stored)
-            asm volatile("" :: "v"(v));
-#elif NA_LS_TRAIN_EXP & 4  // (timing: the same store instructions into a 64-KiB window per plane: no HBM stream behind them)
-            if (t0 + 8 * k < a.T) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4p, v), trs, (vo + k * step + t * 128) & 0xFFFFu, 0, NA_LS_TRAIN_AUX);
-#else
-            if (t0 + 8 * k < a.T) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4p, v), trs, vo + k * step + t * 128, 0, NA_LS_TRAIN_AUX);
-#endif
+            if (t0 + 8 * k < a.T) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4p, v), trs, vo + k * step + t * 128, 0, kTrainStoreAux);
           }
         }
       }

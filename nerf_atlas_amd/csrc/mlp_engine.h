@@ -16,11 +16,6 @@
 #pragma once
 #include "common.h"
 
-// Ablation switches for tools/ablate.py (timing experiments only; results are WRONG when any bit is set):
-//  1 no barrier/wait   2 identity activation   4 no MFMA   8 one LDS read per tile   16 no weight DMA   32 no hash
-#ifndef NA_ABLATE
-#define NA_ABLATE 0
-#endif
 // NA_TRACE: waves 0 and NWAVES/2 of workgroup 0 log (s_memtime << 8 | event id) into LDS during their first two
 // passes; the render kernel dumps the log to its workspace (tools/trace.py).  Timing experiments only.
 #ifndef NA_TRACE
@@ -75,10 +70,6 @@ __device__ __forceinline__ float sin_hw2(float x) {
   return __builtin_amdgcn_sinf(r);
 }
 
-#ifndef NA_F16X_FAST_SIN
-#define NA_F16X_FAST_SIN 1  // the f16x mode takes the three-instruction sine (v_mul, v_fract, v_sin) of the fast modes: measured the
-                            // same L-inf as the exact reduction (1.6e-5 golden / 9e-6 bench weights), 128 fewer VALU per sine epilogue
-#endif
 // precision traits: two operand planes (hi + lo) per fragment; IEEE-half elements in the 16-bit containers
 template <int PREC> constexpr bool kTwoPlane = PREC == NA_PREC_BF16X3 || PREC == NA_PREC_F16X;
 template <int PREC> constexpr bool kHalfElem = PREC == NA_PREC_F16 || PREC == NA_PREC_F16X;
@@ -86,11 +77,12 @@ template <int PREC> constexpr bool kHalfElem = PREC == NA_PREC_F16 || PREC == NA
 template <int ACT, int PREC = NA_PREC_BF16X3>
 __device__ __forceinline__ float act_apply(float v) {
   // leaky_relu(v) = max(v, 0.01 v) = median(v, 0.01 v, +big): v_med3_f32 needs no canonicalising v_max
-  if constexpr ((NA_ABLATE & 2) != 0) return v;
   // (f16 operands: the upper bound doubles as the clamp to the largest finite half, so a large pre-activation becomes 65504
   // instead of +inf -> NaN downstream; the negative side is safe down to v = -6.5e6)
   if constexpr (ACT == NA_ACT_LEAKY_RELU) return __builtin_amdgcn_fmed3f(v, v * 0.01f, kHalfElem<PREC> ? 65504.0f : 3.0e38f);
-  else if constexpr (ACT == NA_ACT_SIN) return (kTwoPlane<PREC> && !(PREC == NA_PREC_F16X && NA_F16X_FAST_SIN)) ? sin_hw2(v) : sin_hw(v);
+  // (sine: the exact reduction for bf16x3 only; f16x takes the three-instruction sine (v_mul, v_fract, v_sin) of the fast modes,
+  // measured the same L-inf as the exact reduction (1.6e-5 golden / 9e-6 bench weights), 128 fewer VALU per sine epilogue)
+  else if constexpr (ACT == NA_ACT_SIN) return PREC == NA_PREC_BF16X3 ? sin_hw2(v) : sin_hw(v);
   else return v;
 }
 
@@ -209,14 +201,12 @@ struct WeightStream {
     // waves per SIMD (waves w and w + NWAVES/2) only the first one issues DMA; its partner (the `late` half, which
     // takes the per-tile barrier at the END of its tile instead of the middle and so runs half a tile ahead)
     // keeps the matrix pipe busy meanwhile.
-    if ((NA_ABLATE & 16) == 0 || issued < 3) {
-      if constexpr (kSplitRoles) {
-        constexpr int HW = NWAVES / 2;
-        if (!late)
-          for (int b = wave; b < nblk; b += HW) glds16(src + (size_t)b * 1024, dst + b * 1024);
-      } else {
-        for (int b = wave; b < nblk; b += NWAVES) glds16(src + (size_t)b * 1024, dst + b * 1024);
-      }
+    if constexpr (kSplitRoles) {
+      constexpr int HW = NWAVES / 2;
+      if (!late)
+        for (int b = wave; b < nblk; b += HW) glds16(src + (size_t)b * 1024, dst + b * 1024);
+    } else {
+      for (int b = wave; b < nblk; b += NWAVES) glds16(src + (size_t)b * 1024, dst + b * 1024);
     }
     ++issued;
     next_t = next_t + 1 == ntiles ? 0 : next_t + 1;
@@ -259,11 +249,9 @@ struct WeightStream {
   // Once per tile, between two MFMAs of the resident tile.
   __device__ __forceinline__ void mid_sync() {
     mark(2);
-    if ((NA_ABLATE & 1) == 0) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      mark(3);
-      __builtin_amdgcn_s_barrier();
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    mark(3);
+    __builtin_amdgcn_s_barrier();
     mark(4);
     if (issued < total) issue_next((cur_slot + 2) % SLOTS);
     mark(5);
@@ -287,11 +275,7 @@ struct WeightStream {
 // two-value steps that are spread evenly over the tile's MFMAs in program order.
 // A fragments are read from LDS one stage (kStage chunks) ahead of their MFMAs.  2 chunks in the 8-wave bf16
 // kernels (256-VGPR budget: depth 4 spills ~11 registers, same speed), 4 in the 4-wave bf16x3 kernels.
-#ifdef NA_KSTAGE
-template <int PREC> constexpr int stage_depth() { return NA_KSTAGE; }
-#else
 template <int PREC> constexpr int stage_depth() { return PREC == NA_PREC_BF16X3 ? 4 : 2; }
-#endif
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
@@ -377,7 +361,6 @@ __device__ __forceinline__ void mma_chunks(WS& ws, f32x16 (&acc)[NB], const char
       for (int c = 0; c < kStage; ++c) {
         const int cc = (s + 1) * kStage + c;
         if (cc < NCH) {
-          if constexpr ((NA_ABLATE & 8) != 0) { ah[cur ^ 1][c] = ah[0][0]; al[cur ^ 1][c] = ah[0][0]; continue; }
           ah[cur ^ 1][c] = *(const bf16x8*)(a0 + cc * FB);
           if constexpr (PREC == NA_PREC_BF16X3) al[cur ^ 1][c] = *(const bf16x8*)(a0 + cc * FB + 1024);
         }
@@ -390,20 +373,16 @@ __device__ __forceinline__ void mma_chunks(WS& ws, f32x16 (&acc)[NB], const char
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
           const Frag<PREC>& Bf = B[b * BSTRIDE + cc];
-          if constexpr ((NA_ABLATE & 4) != 0) {
-            asm volatile("" ::"v"(ah[cur][c]), "v"(Bf.hi));
+          if constexpr (PREC == NA_PREC_BF16X3) {
+            acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur][c], Bf.hi, acc[b], 0, 0, 0);
+            acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][c], Bf.lo, acc[b], 0, 0, 0);
+          }
+          if constexpr (PREC == NA_PREC_F16) {
+            typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+            acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah[cur][c]), __builtin_bit_cast(f16x8, Bf.hi),
+                                                            acc[b], 0, 0, 0);
           } else {
-            if constexpr (PREC == NA_PREC_BF16X3) {
-              acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur][c], Bf.hi, acc[b], 0, 0, 0);
-              acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][c], Bf.lo, acc[b], 0, 0, 0);
-            }
-            if constexpr (PREC == NA_PREC_F16) {
-              typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-              acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah[cur][c]), __builtin_bit_cast(f16x8, Bf.hi),
-                                                              acc[b], 0, 0, 0);
-            } else {
-              acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][c], Bf.hi, acc[b], 0, 0, 0);
-            }
+            acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][c], Bf.hi, acc[b], 0, 0, 0);
           }
           const int m = (m0 + cc) * NB + b;
           if (m == 0) ws.mark(1);

@@ -39,12 +39,6 @@
 #include "train_shared.h"
 
 namespace na {
-#ifndef TBW_EXP
-#define TBW_EXP 0     // experiments: 1 non-temporal stores of g_x, 2 non-temporal row fetches
-#endif
-#ifndef TBW_ABLATE
-#define TBW_ABLATE 0  // timing experiments: 1 no row fetches, 2 no convert / LDS fill, 4 no MFMAs, 8 no g_x stores, 16 no partials
-#endif
 namespace lsbw {
 constexpr int SS = 32;                 // samples per stage
 constexpr int GP = 528;                // row pitch of a dY plane: 132 dwords = 4 mod 64
@@ -119,20 +113,19 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
     return lsnt::tile_rsrc(base, ld, m0, g.N, g.part);
   };
   auto load = [&](int st) __attribute__((always_inline)) {
-    if (TBW_ABLATE & 1) return;
     const __amdgpu_buffer_rsrc_t rg = stage_rsrc(g.dY, g.out, st), rx = stage_rsrc(g.x, g.ldx, st);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       // ONE 16-byte load per piece whatever the row length: raw-buffer loads of 16 bytes need only 4-byte alignment and are
       // range-checked per dword (profiles/r03/unaligned_probe.log); a piece that crosses the end of its row (65, 3 columns) brings
       // elements of the NEXT row along, which the conversion zeroes (og[1..3] keep the per-element validity)
-      gs[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, og[0], 8 * j * g.out * 4, (TBW_EXP & 2) ? 2 : 0));
+      gs[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, og[0], 8 * j * g.out * 4, 0));
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       // (one 16-byte load per piece here too; the elements of the next row a piece of a 38 / 69 wide source brings along are
       // zeroed at conversion.  The STORES of such a source stay dwords: a 16-byte store across the row end would clobber.)
-      xs[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, oxe[0], 16 * j * g.ldx * 4, (TBW_EXP & 2) ? 2 : 0));
+      xs[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, oxe[0], 16 * j * g.ldx * 4, 0));
     }
     if constexpr (!FULL) {  // the addend of the stage that is FINISHED in the next step (this fetch is for stage st = step + 2, the
       // next step finishes stage step = st - 2); no pointer: an empty buffer, zeros
@@ -145,7 +138,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
   const int gro = rho(r0) * GP + c4 * 8;            // sample r0 + 8 j -> row rho(r0) + 2 (j & 1) + 16 (j >> 1)
   const int xro = rho(xr0) * XP + xc * 8;           // sample xr0 + 16 j -> row rho(xr0) + 16 j
   auto convert = [&](f32x4 (&d)[2], char* buf) __attribute__((always_inline)) {
-    if (TBW_ABLATE & 2) return;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       char* p = buf + gro + (2 * (j & 1) + 16 * (j >> 1)) * GP;
@@ -180,7 +172,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
   };
   // g_x of stage st: the tile the dgrad waves left (rows = samples, 128 columns) x act'(x) of the pieces this thread fetched
   auto finish = [&](const f32x4 (&d)[2], int st) __attribute__((always_inline)) {
-    if (TBW_ABLATE & 8) return;
     const __amdgpu_buffer_rsrc_t ry = stage_rsrc(g.gx, g.ldx, st);
     const char* ot = otile + (st & 1) * OT + xr0 * OP + xc * 16;
 #pragma unroll
@@ -196,7 +187,7 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
       }
       // (the row step in the VECTOR offset, soffset 0: with an SGPR soffset the compiler inserts no wait between a 16-byte store
       // and a VALU write of its data registers, and gfx950 needs one -- build.check_store_data_overwrite, tools/hw/store_soffset_hazard.hip)
-      if constexpr (XA) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, oxe[0] + (uint32_t)(16 * j * g.ldx * 4), 0, (TBW_EXP & 1) ? 2 : 0);
+      if constexpr (XA) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, oxe[0] + (uint32_t)(16 * j * g.ldx * 4), 0, 0);
       else {
         const u32x4 u = __builtin_bit_cast(u32x4, v);  // (the whole vector: a bit cast of v[e] in an unrolled loop reads element 0 four times)
 #pragma unroll
@@ -242,7 +233,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
         if (FULL || ks < nks) {  // (wave-uniform: out = 65 / 3 have 5 / 1 k steps)
           const bf16x8 xh = *(const bf16x8*)(fr + ks * 32);
           const bf16x8 xl = *(const bf16x8*)(fr + GPLANE + ks * 32);
-          if (TBW_ABLATE & 4) { acc[ks] += (float)xh[0] + (float)xl[1] + (float)bl[ks][0] + (float)bh[ks][1]; continue; }
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[ks], xh, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[ks], xl, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[ks], xh, acc, 0, 0, 0);
@@ -327,7 +317,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
             for (int jj = 0; jj < 2; ++jj) {
               const int j = 2 * jh + jj;
               if (!FULL && (i >= NI || j >= NJ)) continue;
-              if (TBW_ABLATE & 4) { acc[i][j][0] += (float)al[i][0] + (float)bh[jj][1] + (float)ah[i][2] + (float)bl[jj][3]; continue; }
               acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[jj], acc[i][j], 0, 0, 0);
               acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[jj], acc[i][j], 0, 0, 0);
               acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[jj], acc[i][j], 0, 0, 0);
@@ -356,18 +345,16 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
     if ((nst - 1) & 1) finish(d1, nst - 1); else finish(d0, nst - 1);
     // partial gradient of this slice, columns of this half: register r of acc[i][j] = row 64 wm + 32 i + (r & 3) + 8 (r >> 2) +
     // 4 (lane >> 5), column 128 h + 32 j + (lane & 31)
-    if (!((TBW_ABLATE & 16) && acc[0][0][0] != 1.2345f)) {
-      float* part = g.part + (int64_t)slice * PART;
+    float* part = g.part + (int64_t)slice * PART;
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (!FULL && (i >= NI || j >= NJ)) continue;  // (the reduction reads rows < out, columns < in only)
+      for (int j = 0; j < 4; ++j) {
+        if (!FULL && (i >= NI || j >= NJ)) continue;  // (the reduction reads rows < out, columns < in only)
 #pragma unroll
-          for (int r = 0; r < 16; ++r)
-            part[(64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 256 + 128 * h + 32 * j + (lane & 31)] = acc[i][j][r];
-        }
-    }
+        for (int r = 0; r < 16; ++r)
+          part[(64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 256 + 128 * h + 32 * j + (lane & 31)] = acc[i][j][r];
+      }
   }
   if (g.want_db && h == 0) {
     float* part = g.part + (int64_t)slice * PART;

@@ -23,12 +23,6 @@
 #include "train_shared.h"
 
 namespace na {
-#ifndef TFW_ABLATE
-#define TFW_ABLATE 0  // timing experiments: 1 no row fetches, 2 no convert / LDS fill, 4 no MFMAs, 8 no stores
-#endif
-#ifndef TFW_EXP
-#define TFW_EXP 0     // experiments: 1 non-temporal stores of y, 2 non-temporal row fetches, 4 finish AFTER convert + fetch (MODE 0), 8 unconditional second half
-#endif
 namespace lsfw {
 constexpr int SS = 32;                  // samples per stage
 constexpr int KMAX = 336;               // 256 + 80
@@ -83,11 +77,10 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
     return lsnt::tile_rsrc(base, ld, m0, g.N, g.wp);
   };
   auto load = [&](f32x4 (&a)[4], f32x4 (&b)[2], int st) __attribute__((always_inline)) {  // (both sets have this shape when they exist)
-    if (TFW_ABLATE & 1) return;
     if constexpr (X0) {
       const __amdgpu_buffer_rsrc_t r0s = stage_rsrc(g.x0, 256, st);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) a[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r0s, o0, 8 * j * 256 * 4, (TFW_EXP & 2) ? 2 : 0));
+      for (int j = 0; j < 4; ++j) a[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r0s, o0, 8 * j * 256 * 4, 0));
     }
     if constexpr (X1) {
       const __amdgpu_buffer_rsrc_t r1s = stage_rsrc(g.x1, g.in1, st);
@@ -99,7 +92,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
   };
   const int ro0 = r0 * G::P + c4 * 8, ro1 = xr0 * G::P + (G::KOFF + 4 * xc) * 2;
   auto convert = [&](const f32x4 (&a)[4], const f32x4 (&b)[2], char* buf) __attribute__((always_inline)) {
-    if (TFW_ABLATE & 2) return;
     if constexpr (X0) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -142,7 +134,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
   }
   // y of stage st: the tile + bias, as whole row pieces (the thread's pieces = the ones it fetches of x0: same offsets)
   auto finish = [&](int st) __attribute__((always_inline)) {
-    if (TFW_ABLATE & 8) return;
     const __amdgpu_buffer_rsrc_t ry = stage_rsrc(g.y, g.out, st);
     if constexpr (NOUT) {
       const char* ot = otile + (st & 1) * OT + nrow0 * OP + ncol * 4;
@@ -161,7 +152,7 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] += bias4[e];
       // (row step in the vector offset, soffset 0: build.check_store_data_overwrite, tools/hw/store_soffset_hazard.hip)
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, o0 + (uint32_t)(8 * j * 256 * 4), 0, (TFW_EXP & 1) ? 2 : 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, o0 + (uint32_t)(8 * j * 256 * 4), 0, 0);
     }
   };
 
@@ -201,7 +192,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
       if ((X0 && i < 16) || i < g.nks) {  // (wave-uniform; K = 256: exactly 16)
         const bf16x8 xh = *(const bf16x8*)(fr + i * 32);
         const bf16x8 xl = *(const bf16x8*)(fr + G::PLANE + i * 32);
-        if (TFW_ABLATE & 4) { acc[i & 15] += (float)xh[0] + (float)xl[1] + (float)wl[i][0] + (float)wh[i][1]; continue; }
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[i], xh, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[i], xl, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[i], xh, acc, 0, 0, 0);
@@ -223,24 +213,21 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
     __syncthreads();
     for (int s = 0; s < nst; s += 2) {
       if (mfirst) { mma(smem, otile); __builtin_amdgcn_sched_barrier(0); }
-      if (!(TFW_EXP & 4)) finish(s - 1);
+      finish(s - 1);
       convert(a1, b1, smem + G::STAGE);
       load(a1, b1, s + 3);
       __builtin_amdgcn_sched_barrier(0);  // (the scheduler sinks the fetches below the MFMAs otherwise)
-      if (TFW_EXP & 4) { finish(s - 1); __builtin_amdgcn_sched_barrier(0); }
       if (!mfirst) mma(smem, otile);
       __syncthreads();
-      // (round 6) the second half is UNCONDITIONAL: a stage past the slice fetches from an empty buffer and its stores are dropped.
-      // Under `if (s + 1 < nst)` the control-flow graph had a path half A -> half A, and the compiler's waitcnt insertion, which
-      // must hold on every path, waited for this half's fetches with vmcnt(7) instead of vmcnt(15): every fetch had to be back
-      // ONE stage after its issue, not two -- fetch time and compute time added up (ablations: 49 + 67 us of 132)
-      if ((TFW_EXP & 8) || s + 1 < nst) {
+      // (The condition gives the control-flow graph a path half A -> half A, and the compiler's waitcnt insertion, which must
+      // hold on every path, waits for this half's fetches with vmcnt(7) instead of vmcnt(15): one stage after issue, not two.
+      // An unconditional second half, which avoids that, measured the same: 148.8 against 149.6 us.)
+      if (s + 1 < nst) {
         if (mfirst) { mma(smem + G::STAGE, otile + OT); __builtin_amdgcn_sched_barrier(0); }
-        if (!(TFW_EXP & 4)) finish(s);
+        finish(s);
         convert(a0, b0, smem);
         load(a0, b0, s + 4);
         __builtin_amdgcn_sched_barrier(0);
-        if (TFW_EXP & 4) { finish(s); __builtin_amdgcn_sched_barrier(0); }
         if (!mfirst) mma(smem + G::STAGE, otile + OT);
         __syncthreads();
       }
@@ -258,7 +245,7 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
       __builtin_amdgcn_sched_barrier(0);
       if (!mfirst) mma(smem, otile);
       __syncthreads();
-      if ((TFW_EXP & 8) || s + 1 < nst) {
+      if (s + 1 < nst) {
         if (mfirst) { mma(smem + G::STAGE, otile + OT); __builtin_amdgcn_sched_barrier(0); }
         finish(s);
         convert(a0, b0, smem);
@@ -269,7 +256,7 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
       }
     }
   }
-  if (!(TFW_EXP & 8) || !(nst & 1)) finish(nst - 1);  // (TFW_EXP & 8, an odd count: the unconditional second half of the last iteration has stored stage nst - 1)
+  finish(nst - 1);
 }
 
 // NA_TRAIN_FUSED_FWD=0: never (the streaming kernel lsnt::kernel<0> for A/B runs).

@@ -45,41 +45,8 @@ namespace na {
 // in front of every conversion, the prefetch one unit deep whatever the code said).
 // A unit = (tile, pass over 256 columns of C, k chunk), one barrier per unit.  Inside a unit a consumer finishes its column tile
 // t = 0 before it starts t = 1.
-#ifndef TGL_ABLATE
-#define TGL_ABLATE 0  // timing experiments: 1 no row fetches, 2 no epilogue stores, 4 no MFMAs, 8 no weight refills, 16 no LDS fill, 32 fill from constants, 64 conversion without its LDS writes
-#endif
 #ifndef TGL_TRACE
 #define TGL_TRACE 0  // experiment builds (tools/ls_variant.py): s_memtime stamps of workgroup 0, waves 0 (consumer) and 4 (loader)
-#endif
-#ifndef TGL_PRIO
-#define TGL_PRIO 0   // s_setprio of the loader and mover waves
-#endif
-#ifndef TGL_CPRIO
-#define TGL_CPRIO 0  // s_setprio of the consumer waves (1, 3: 147-151 against 153-160 us forward alone, 7.5-7.9 ms in the step either way)
-#endif
-#ifndef TGL_P0F
-#define TGL_P0F 6   // of the 16 pieces a mover thread stores per tile, those that go out in the first of the tile's two units: forward
-#endif
-#ifndef TGL_P0D
-#define TGL_P0D 2   // ... input gradient with an activation (the first unit also parks x: 8 / 8 -> 2 / 14: 210 -> 189 us)
-#endif
-// Cache policies (gfx950 buffer aux bits: 2 = nt), experiment switches.  Timed alone in a loop, non-temporal stores of the
-// output tile take the forward from 151-156 to 136-137 us and, with the parked x fetched non-temporal too, the input gradient
-// from 200-205 to 177-180 -- but that is the loop: the same 268-MB inputs are read again by the next iteration and survive in
-// the 256-MB memory-side cache when the outputs do not pass through it.  In the training step, where every tensor is
-// written once and read by the next kernel, the three policies give 7.49 / 7.56 / 7.45 ms (tools/train_bench_ab.py): nothing.
-#ifndef TGL_ST_AUX
-#define TGL_ST_AUX 0     // the output tile's stores
-#endif
-#ifndef TGL_X_AUX
-#define TGL_X_AUX 0      // the fetches of the forward inputs x an input gradient parks
-#endif
-#ifndef TGL_RIDE
-#define TGL_RIDE 0   // 1: the first column tile's epilogue rides under the second one's MFMAs, an item per k step (measured SLOWER:
-                     // forward 151 -> 154 us, input gradient 191 -> 206: its LDS traffic and waits land inside the k steps)
-#endif
-#ifndef TGL_RD
-#define TGL_RD 4     // weight fragment ring of a consumer wave, in k steps (8 = a whole segment, or 4)
 #endif
 namespace lsnt {
 #if TGL_TRACE
@@ -188,15 +155,15 @@ struct Src2 {
 // the end of its row brings the first elements of the NEXT row along, which the caller zeroes when it USES the piece (zeroing
 // here would wait for the load).  WHICH 0: both sources, summed element by element on the spot: exact zeros outside, but it
 // waits for its loads (only the STRADDLE instantiation uses it).
-template <int WHICH = 0, int AUX = 0>
+template <int WHICH = 0>
 __device__ __forceinline__ f32x4 load_piece(const Src2& s, int row, int col) {
   if (WHICH == 1) {
     const uint32_t o = col < s.k0 ? (uint32_t)((row * s.k0 + col) * 4) : OOB;
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(s.r0, o, 0, AUX));
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(s.r0, o, 0, 0));
   }
   if (WHICH == 2) {
     const uint32_t o = (col >= s.k0 && col < s.k0 + s.k1) ? (uint32_t)((row * s.k1 + col - s.k0) * 4) : OOB;
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(s.r1, o, 0, AUX));
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(s.r1, o, 0, 0));
   }
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
   if ((s.k0 & 3) == 0) {
@@ -226,7 +193,7 @@ __device__ __forceinline__ f32x4 load_piece(const Src2& s, int row, int col) {
 // pass to give up on the whole loop (vmcnt(0) in front of every conversion): it gets its own instantiation.
 template <int MODE, bool DACT, bool STRADDLE>
 __global__ __launch_bounds__(NTHR) void kernel(Args g) {
-  constexpr int RD = TGL_RD;  // depth of the weight fragment ring (8 = the k steps of one segment)
+  constexpr int RD = 4;       // depth of the weight fragment ring, in k steps (8 would be a whole segment)
   constexpr int KS = 8;       // k steps of a segment
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -255,7 +222,6 @@ __global__ __launch_bounds__(NTHR) void kernel(Args g) {
 
   if (wave >= 4) {
     // ------------------------------------------------------------------------------------- loaders (4-7) and movers (8-11)
-    if (TGL_PRIO) __builtin_amdgcn_s_setprio(TGL_PRIO);
     // Two roles of four waves each, so that every wave's vector memory queue holds ONE kind of long-latency work and the
     // compiler's s_waitcnt counts stay exact: vmcnt counts loads and stores in order, and with the tile's stores, the x fetches
     // and the row fetches of several uniform branches in one wave the pass fell back to vmcnt(0) in front of the conversion --
@@ -270,7 +236,6 @@ __global__ __launch_bounds__(NTHR) void kernel(Args g) {
     // fetches are still ISSUED, against an empty buffer: conditional fetches cost the wait-count pass its precision.)
     auto resident = [&](int u) __attribute__((always_inline)) { return NCH == 2 && u < nunits && (u / NCH) % NP >= 1; };
     auto load = [&](f32x4 (&pf)[NPF], int u) {
-      if (TGL_ABLATE & 1) return;
       const int64_t m0 = (resident(u) ? g.ntiles : tile_of(u)) * TS;
       const int k = (u % NCH) * KC + c4 * 4;
       const Src2 src{tile_rsrc(g.a.p0, g.a.k0, m0, g.a.rows, g.wp), tile_rsrc(g.a.p1, g.a.k1, m0, g.a.rows, g.wp), g.a.k0, g.a.k1};
@@ -298,7 +263,6 @@ __global__ __launch_bounds__(NTHR) void kernel(Args g) {
 #pragma unroll
       for (int j = 0; j < NPF; ++j) {
         f32x4 v = pf[j];
-        if (TGL_ABLATE & 32) v = f32x4{(float)c4, (float)(r0 + j), 1.5f, 2.5f};  // (no wait for the rows)
         if (RAGGED) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = kq + e < K ? v[e] : 0.f;
@@ -307,13 +271,11 @@ __global__ __launch_bounds__(NTHR) void kernel(Args g) {
         for (int e = 0; e < 4; ++e) v[e] = tact(v[e], ACT);
         bf16x4 hi, lo;
         split4(v, hi, lo);
-        if (TGL_ABLATE & 64) { asm volatile("" ::"v"(hi), "v"(lo)); continue; }  // (no LDS writes)
         *(bf16x4*)(d + RS * j * PITCH) = hi;
         *(bf16x4*)(d + RS * j * PITCH + PLANE) = lo;
       }
     };
     auto convert = [&](const f32x4 (&pf)[NPF], char* buf, int u) __attribute__((always_inline)) {
-      if (TGL_ABLATE & 16) return;
       const int kq = (u % NCH) * KC + c4 * 4;
       const int act = MODE == 0 ? g.act : NA_ACT_NONE;
       if (ragged) {
@@ -334,10 +296,10 @@ __global__ __launch_bounds__(NTHR) void kernel(Args g) {
       const int c_lo = 256 * ((u / NCH) % NP);
       if (c_lo + 256 <= g.c0 || g.c1 == 0) {
 #pragma unroll
-        for (int j = 0; j < NXF; ++j) xs[j] = load_piece<1, TGL_X_AUX>(src, xr0 + XS * j, col);
+        for (int j = 0; j < NXF; ++j) xs[j] = load_piece<1>(src, xr0 + XS * j, col);
       } else if (c_lo >= g.c0) {
 #pragma unroll
-        for (int j = 0; j < NXF; ++j) xs[j] = load_piece<2, TGL_X_AUX>(src, xr0 + XS * j, col);
+        for (int j = 0; j < NXF; ++j) xs[j] = load_piece<2>(src, xr0 + XS * j, col);
       } else {
 #pragma unroll
         for (int j = 0; j < NXF; ++j) xs[j] = load_piece<0>(src, xr0 + XS * j, col);
@@ -348,19 +310,21 @@ __global__ __launch_bounds__(NTHR) void kernel(Args g) {
       for (int j = 0; j < NXF; ++j) *(f32x4*)(xbuf + (xr0 + XS * j) * XP + 4 * xc4) = xs[j];
     };
     // the finished output tile of unit u's (tile, pass), from LDS to HBM: whole rows, 16 bytes per lane (the thread's pieces are the
-    // ones it parks x in, so its own program order is all the synchronisation the shared buffer needs)
+    // ones it parks x in, so its own program order is all the synchronisation the shared buffer needs).  Default cache policy:
+    // non-temporal stores and x fetches won only in an isolated loop; in the training step 7.49 / 7.56 / 7.45 ms, nothing.
     const int ncols = g.c0 + g.c1;
     // (two steps: the tile leaves LDS for registers at once, then goes out in NCH parts, one per unit of the next (tile, pass) --
     // 64 KB in one burst kept every wave of the CU, the loaders' fetches and the consumers' weight refills included, queued
     // behind it for ~9 k cycles of every other unit)
     f32x4 ot[NXF];
-    constexpr int P0 = DACT ? TGL_P0D : TGL_P0F;  // pieces stored in the first of a tile's two units, the rest in the second
+    // of the 16 pieces a mover thread stores per tile, those that go out in the first of the tile's two units, the rest in the
+    // second (an input gradient with an activation also parks x in the first unit: 8 / 8 -> 2 / 14 took it from 210 to 189 us)
+    constexpr int P0 = DACT ? 2 : 6;
     auto take_out = [&]() __attribute__((always_inline)) {
 #pragma unroll
       for (int j = 0; j < NXF; ++j) ot[j] = *(const f32x4*)(xbuf + (xr0 + XS * j) * XP + 4 * xc4);
     };
     auto store_out = [&](int u, int part) __attribute__((always_inline)) {  // part < 0: all of it
-      if (TGL_ABLATE & 2) return;
       const int64_t m0 = tile_of(u) * TS;
       const int c_lo = 256 * ((u / NCH) % NP);
       const int col = c_lo + 4 * xc4;
@@ -376,36 +340,36 @@ __global__ __launch_bounds__(NTHR) void kernel(Args g) {
         if (side0) {
           if (vec0) {
             const uint32_t o0 = col < g.c0 ? (uint32_t)((xr0 * g.c0 + col) * 4) : OOB;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry0, o0, XS * j * g.c0 * 4, TGL_ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry0, o0, XS * j * g.c0 * 4, 0);
           } else {
             // rows of a length that is no multiple of four: a piece that lies inside its row still leaves as ONE 16-byte store
             // (4-byte aligned: tools/hw/unaligned_probe.hip), only the piece across the row's end element by element --
             // 38 four-byte stores per row of a skip layer's second gradient kept the mover's queue busy for 10 k cycles
             const bool whole = col + 3 < g.c0;
             const uint32_t o0 = whole ? (uint32_t)((xr0 * g.c0 + col) * 4) : OOB;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry0, o0, XS * j * g.c0 * 4, TGL_ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry0, o0, XS * j * g.c0 * 4, 0);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const uint32_t p0 = (!whole && col + e < g.c0) ? (uint32_t)((xr0 * g.c0 + col + e) * 4) : OOB;
               const float w = e == 0 ? v[0] : e == 1 ? v[1] : e == 2 ? v[2] : v[3];
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, w), ry0, p0, XS * j * g.c0 * 4, TGL_ST_AUX);
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, w), ry0, p0, XS * j * g.c0 * 4, 0);
             }
           }
         }
         if (side1) {
           if (vec1) {
             const uint32_t o1 = (col >= g.c0 && col < ncols) ? (uint32_t)((xr0 * g.c1 + col - g.c0) * 4) : OOB;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry1, o1, XS * j * g.c1 * 4, TGL_ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry1, o1, XS * j * g.c1 * 4, 0);
           } else {
             const bool whole = col >= g.c0 && col + 3 < ncols;
             const uint32_t o1 = whole ? (uint32_t)((xr0 * g.c1 + col - g.c0) * 4) : OOB;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry1, o1, XS * j * g.c1 * 4, TGL_ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry1, o1, XS * j * g.c1 * 4, 0);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const int ce = col + e;
               const uint32_t p1 = (!whole && ce >= g.c0 && ce < ncols) ? (uint32_t)((xr0 * g.c1 + ce - g.c0) * 4) : OOB;
               const float w = e == 0 ? v[0] : e == 1 ? v[1] : e == 2 ? v[2] : v[3];
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, w), ry1, p1, XS * j * g.c1 * 4, TGL_ST_AUX);
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, w), ry1, p1, XS * j * g.c1 * 4, 0);
             }
           }
         }
@@ -474,7 +438,6 @@ __global__ __launch_bounds__(NTHR) void kernel(Args g) {
   }
 
   // -------------------------------------------------------------------------------------------------- consumers
-  if (TGL_CPRIO) __builtin_amdgcn_s_setprio(TGL_CPRIO);
   const int ncols = g.c0 + g.c1;
   bf16x8 ring[RD][2];    // [k step of the segment][plane]
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)g.wp, 0, nrg * NCH * 2 * SEG, 0x00020000);
@@ -529,8 +492,8 @@ __global__ __launch_bounds__(NTHR) void kernel(Args g) {
     // Epilogue of column tile t, one quad of columns of one sample block at a time: bias / activation derivative in the
     // accumulator layout -- register 4 q + e of acc[.][.] = column 64 R + 32 t + 8 q + 4 (lane >> 5) + e, sample 32 b +
     // (lane & 31) -- then the quad goes to the output tile in LDS (row-major; x, where it is needed, sits at the very same
-    // place and is overwritten by the result).  (TGL_RIDE: with two column tiles the first one's eight items under the second
-    // one's k steps, one per step.)
+    // place and is overwritten by the result).  (Tile 0's items under tile 1's k steps, one per step, measured slower: forward
+    // 151 -> 154 us, input gradient 191 -> 206 -- their LDS traffic and waits land inside the k steps.)
     auto epi_item = [&](const f32x16& a, int t, int q, int bk) __attribute__((always_inline)) {
       const int cl = 64 * (R & 3) + 32 * t + 8 * q + 4 * (lane >> 5);  // column inside the pass
       float* o = xbuf + (32 * bk + (lane & 31)) * XP + cl;
@@ -548,7 +511,6 @@ __global__ __launch_bounds__(NTHR) void kernel(Args g) {
       }
       *(f32x4*)o = v;
     };
-    constexpr bool ride = last && NT == 2 && TGL_RIDE;  // tile 0's epilogue under tile 1's MFMAs
 #pragma unroll
     for (int tt = 0; tt < NT; ++tt) {
       const int t = NT == 2 ? tt : tsel;
@@ -576,22 +538,18 @@ __global__ __launch_bounds__(NTHR) void kernel(Args g) {
         const bf16x8 wh = ring[sl][0], wl = ring[sl][1];
 #pragma unroll
         for (int bb = 0; bb < NB; ++bb) {
-          if (TGL_ABLATE & 4) { acc[tt][bb][0] += (float)wl[0] + (float)xh[cur][bb][0] + (float)wh[1] + (float)xl[cur][bb][1]; continue; }
           acc[tt][bb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xh[cur][bb], acc[tt][bb], 0, 0, 0);
           acc[tt][bb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl[cur][bb], acc[tt][bb], 0, 0, 0);
           acc[tt][bb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh[cur][bb], acc[tt][bb], 0, 0, 0);
         }
         // refill in place, behind the slot's MFMAs: needed RD k steps from now
-        if (!(TGL_ABLATE & 8)) {
-          const int so = i + RD < KS ? cso : nso, j = (i + RD) % KS;
-          ring[sl][0] = wfrag(so, j, 0); ring[sl][1] = wfrag(so, j, 1);
-        }
-        if (ride && tt == 1 && i < 4 * NB) epi_item(acc[0][NB == 2 ? (i & 1) : 0], 0, NB == 2 ? (i >> 1) : i, NB == 2 ? (i & 1) : bsel);
+        const int so = i + RD < KS ? cso : nso, j = (i + RD) % KS;
+        ring[sl][0] = wfrag(so, j, 0); ring[sl][1] = wfrag(so, j, 1);
         __builtin_amdgcn_sched_barrier(0);
       }
       cso = nso;
       if (wave == 0 && tt == NT - 1) TGL_STAMP(0, u, 1);
-      if (last && !(ride && tt == 0)) {
+      if (last) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -707,15 +665,6 @@ extern "C" int na_debug_tgl_trace(unsigned long long* host_out) {
 // j = 0..3: with lane i pointing at row i >> 2, columns 4 (i & 3).. of a [4 samples][16 features] block it gets column i).
 // Workgroup w reduces its slice of samples into a partial gradient in a workspace; a second kernel sums the partials in a
 // fixed order (bit-reproducible without the fixed-point path, and 17 M float atomics cheaper).
-#ifndef TGW_ABLATE
-#define TGW_ABLATE 0  // timing experiments: 1 no row fetches, 2 no convert / LDS fill, 4 no MFMAs, 8 no fragment reads, 16 no partials
-#endif
-#ifndef TGW_G_AUX
-#define TGW_G_AUX 0  // cache policy of the dY fetches
-#endif
-#ifndef TGW_X_AUX
-#define TGW_X_AUX 0  // ... of the x fetches
-#endif
 namespace lstn {
 constexpr int SS = 32;                // samples per stage
 constexpr int PW = 576;               // row pitch of a plane: 144 dwords = 16 mod 64 -> the 4 rows of a transposing read do not collide
@@ -776,21 +725,20 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
   }
   f32x4 gs0[NPC], xs0[NPC], gs1[NPC], xs1[NPC];
   auto load = [&](f32x4 (&gs)[NPC], f32x4 (&xs)[NPC], int st) __attribute__((always_inline)) {
-    if (TGW_ABLATE & 1) return;
     const int64_t m0 = st < nst ? (st0 + st) * SS : g.N;  // past the slice: an empty buffer
     // (column counts are multiples of 4 here: whole 16-byte pieces; out-of-range pieces return zero)
     const __amdgpu_buffer_rsrc_t rg = lsnt::tile_rsrc(g.dY, g.out, m0, g.N, g.part), rx = lsnt::tile_rsrc(g.x, g.in, m0, g.N, g.part);
 #pragma unroll
     for (int j = 0; j < NPC; ++j) {  // rows r0 + 8 j: one lane offset, the row step in the scalar offset
-      if constexpr (GA) gs[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, og[0], 8 * j * g.out * 4, TGW_G_AUX));
+      if constexpr (GA) gs[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, og[0], 8 * j * g.out * 4, 0));
       else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) gs[j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rg, og[e & (GA ? 0 : 3)], 8 * j * g.out * 4, TGW_G_AUX));
+        for (int e = 0; e < 4; ++e) gs[j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rg, og[e & (GA ? 0 : 3)], 8 * j * g.out * 4, 0));
       }
-      if constexpr (XA) xs[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, ox[0], 8 * j * g.in * 4, TGW_X_AUX));
+      if constexpr (XA) xs[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, ox[0], 8 * j * g.in * 4, 0));
       else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) xs[j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, ox[e & (XA ? 0 : 3)], 8 * j * g.in * 4, TGW_X_AUX));
+        for (int e = 0; e < 4; ++e) xs[j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, ox[e & (XA ? 0 : 3)], 8 * j * g.in * 4, 0));
       }
     }
   };
@@ -815,7 +763,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
     }
   };
   auto convert = [&](const f32x4 (&gs)[NPC], const f32x4 (&xs)[NPC], char* buf) __attribute__((always_inline)) {
-    if (TGW_ABLATE & 2) return;
     if (g.act == NA_ACT_LEAKY_RELU) convert_as(gs, xs, buf, std::integral_constant<int, NA_ACT_LEAKY_RELU>{});
     else if (g.act == NA_ACT_SIN) convert_as(gs, xs, buf, std::integral_constant<int, NA_ACT_SIN>{});
     else convert_as(gs, xs, buf, std::integral_constant<int, NA_ACT_NONE>{});
@@ -831,12 +778,14 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
     return __builtin_bit_cast(bf16x8, v8s{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]});
   };
   auto mma = [&](const char* buf) __attribute__((always_inline)) {
+    // (`lane` stays the first capture of this closure although the body does not read it: without it the compiler lays out the
+    // closure differently and emits another schedule of the whole kernel -- not the one that was measured)
+    (void)lane;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 ah[2], al[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        if (TGW_ABLATE & 8) { ah[i] = al[i] = *(const bf16x8*)(buf + lane * 16); continue; }
         if (i < NI) { ah[i] = frag(buf, ks, 2 * wm + i); al[i] = frag(buf + PLANE, ks, 2 * wm + i); }
       }
 #pragma unroll
@@ -845,7 +794,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
           const int j = 2 * jh + jj;
-          if (TGW_ABLATE & 8) { bh[jj] = bl[jj] = *(const bf16x8*)(buf + lane * 16); continue; }
           if (j < NJ) { bh[jj] = frag(buf + 2 * PLANE, ks, 4 * wn + j); bl[jj] = frag(buf + 3 * PLANE, ks, 4 * wn + j); }
         }
 #pragma unroll
@@ -854,7 +802,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
           for (int jj = 0; jj < 2; ++jj) {
             const int j = 2 * jh + jj;
             if (i >= NI || j >= NJ) continue;
-            if (TGW_ABLATE & 4) { acc[i][j][0] += (float)al[i][0] + (float)bh[jj][1] + (float)ah[i][2] + (float)bl[jj][3]; continue; }
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[jj], acc[i][j], 0, 0, 0);
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[jj], acc[i][j], 0, 0, 0);
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[jj], acc[i][j], 0, 0, 0);
@@ -883,7 +830,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
   // partial gradient of this workgroup: register r of acc[i][j] = row 64 wm + 32 i + (r & 3) + 8 (r >> 2) + 4 (lane >> 5),
   // column 128 wn + 32 j + (lane & 31): 128 contiguous bytes per row
   float* part = g.part + (int64_t)blockIdx.x * PART;
-  if ((TGW_ABLATE & 16) && acc[0][0][0] != 1.2345f) return;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1053,13 +999,7 @@ constexpr int PLANE = TS * PITCH;
 constexpr int BUF = 2 * PLANE;         // hi | lo
 constexpr int LDS = 2 * BUF;           // 66 KiB
 constexpr int NP = TS * (K / 4) / 256; // 16-byte pieces per loader thread and tile (8)
-#ifndef NRW_AHEAD
-#define NRW_AHEAD 4
-#endif
-#ifndef NRW_ABLATE
-#define NRW_ABLATE 0  // experiments only: 1 no MFMAs, 2 no conversion / LDS stash, 4 no result stores / derivative loads, 8 no row fetches
-#endif
-constexpr int AHEAD = NRW_AHEAD;       // tiles a loader keeps in flight (even; 32 KiB each: the launch is bound by bytes in flight)
+constexpr int AHEAD = 4;               // tiles a loader keeps in flight (even; 32 KiB each: the launch is bound by bytes in flight)
 
 struct Args {
   const float* a;      // [N, 256]
@@ -1106,10 +1046,9 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
 #pragma unroll
       for (int j = 0; j < NP; ++j) {
         const int p = lt + 256 * j;
-        if (NRW_ABLATE & 8) pre[slot][j] = f32x4{1.f, 2.f, 3.f, (float)i};
-        else pre[slot][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)(p * 16), 0, 0));
+        pre[slot][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)(p * 16), 0, 0));
       }
-      if (deriv && !(NRW_ABLATE & 4)) {
+      if (deriv) {
         const __amdgpu_buffer_rsrc_t rx = lsnt::tile_rsrc(i < nt ? g.xd : nullptr, g.M, m0 < g.N ? m0 : g.N, g.N, g.a);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -1124,7 +1063,6 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
       for (int j = 0; j < NP; ++j) {
         const int p = lt + 256 * j;
         f32x4 v = pre[slot][j];
-        if (NRW_ABLATE & 2) { if (v[0] == 1.2345f) *(float*)buf = v[1] + v[2] + v[3]; continue; }
         if (MODE == 0 && g.act != NA_ACT_NONE) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = tact(v[e], g.act);
@@ -1135,7 +1073,7 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
         *(bf16x4*)o = hi;
         *(bf16x4*)(o + PLANE) = lo;
       }
-      if (deriv && !(NRW_ABLATE & 4)) {
+      if (deriv) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int p = lt + 256 * j;
@@ -1189,12 +1127,10 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
     for (int ks = 0; ks < 16; ++ks) {
       const bf16x8 xh = *(const bf16x8*)(fr + ks * 32);
       const bf16x8 xl = *(const bf16x8*)(fr + PLANE + ks * 32);
-      if (NRW_ABLATE & 1) { acc[ks] += (float)xh[0] + (float)xl[1] + (float)bl[ks][0] + (float)bh[ks][1]; continue; }
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[ks], xh, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[ks], xl, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[ks], xh, acc, 0, 0, 0);
     }
-    if ((NRW_ABLATE & 4) && acc[0] != 1.2345f) return;
     float* ot = (float*)(otile + (i & 1) * OT) + s * g.M;
     const float* xt = (const float*)(xtile + (i & 1) * OT) + s * g.M;
 #pragma unroll
@@ -1211,7 +1147,7 @@ __global__ __launch_bounds__(512) void kernel(Args g) {
   // waves (also those without a column tile): their memory queue holds nothing but these stores
   const int ctid = tid - 256;
   auto carry = [&](int i) __attribute__((always_inline)) {
-    if (i < 0 || i >= nt || (NRW_ABLATE & 4)) return;
+    if (i < 0 || i >= nt) return;
     const int64_t m0 = (t0 + i) * TS;
     const __amdgpu_buffer_rsrc_t ry = lsnt::tile_rsrc(g.y, g.M, m0, g.N, g.a);
 #pragma unroll

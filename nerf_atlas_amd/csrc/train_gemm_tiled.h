@@ -7,9 +7,6 @@
 
 namespace na {
 
-#ifndef TG_ABLATE
-#define TG_ABLATE 0  // experiments only: 1 no MFMA, 2 no global loads, 4 no LDS stash, 8 no fragment reads
-#endif
 constexpr int TK = 32;   // K per stage
 constexpr int TLD = 80;  // LDS row pitch, bytes
 
@@ -24,7 +21,6 @@ struct RowSrc {
 // 4 consecutive k of one row (zero outside), vectorised when the 16-byte alignment is provable
 __device__ __forceinline__ f32x4 load_k4(const RowSrc& s, int64_t row, int k) {
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (TG_ABLATE & 2) return v;
   if (row >= s.rows) return v;
   if (k + 4 <= s.k0 && (s.k0 & 3) == 0) return *(const f32x4*)(s.p0 + row * s.k0 + k);
   if (k >= s.k0 && k + 4 <= s.k0 + s.k1 && ((s.k0 | s.k1) & 3) == 0) return *(const f32x4*)(s.p1 + row * s.k1 + (k - s.k0));
@@ -45,9 +41,6 @@ __device__ __forceinline__ void mma_stage(const char* At, const char* Bt, int a_
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
     bf16x8 ah[2], al[2], bh[2], bl[2];
-    if (TG_ABLATE & 8) {
-      for (int t = 0; t < 2; ++t) { ah[t] = al[t] = bh[t] = bl[t] = *(const bf16x8*)(At + off); }
-    } else
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       ah[t] = *(const bf16x8*)(At + t * 32 * TLD + off + ks * 32);
@@ -59,7 +52,6 @@ __device__ __forceinline__ void mma_stage(const char* At, const char* Bt, int a_
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
-        if (TG_ABLATE & 1) { acc[mi][ni][0] += (float)al[mi][0] + (float)bh[ni][0] + (float)ah[mi][1] + (float)bl[ni][1]; continue; }
         acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
         acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
         acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
@@ -121,7 +113,6 @@ __global__ __launch_bounds__(64 * WM * WN) void linear_nt_kernel(NtArgs g) {
   };
   auto stash = [&](const int slot, int stage) {
     char* base = smem + stage * STAGE;
-    if (TG_ABLATE & 4) { if (ra[slot][0][0] == 1.2345f && rb[slot][0][0] == 2.345f) base[tid] = 1; return; }
 #pragma unroll
     for (int j = 0; j < NA4; ++j) {
       const int idx = tid + j * NT;

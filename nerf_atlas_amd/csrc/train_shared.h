@@ -17,10 +17,7 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 // end-to-end L-inf as the Cody-Waite polynomial there).  One shared reduction for the pair: where a kernel needs act(x) AND act'(x)
 // of the same element (lsbw: the weight gradient's operand and the input gradient's factor) the compiler keeps one.  ~1e-6
 // absolute, far inside the 2^-16 relative error of the three bf16 products downstream; the polynomial pair cost 48 us per sin
-// layer in lsbw (243 against 195 us for LeakyReLU).  NA_TRAIN_POLY_SIN=1 at build time restores the polynomials for A/B runs.
-#ifndef NA_TRAIN_POLY_SIN
-#define NA_TRAIN_POLY_SIN 0
-#endif
+// layer in lsbw (243 against 195 us for LeakyReLU).
 __device__ __forceinline__ float trev(float x) {
   const float q = rintf(x * 0.15915493667125702f);
   float r = fmaf(x, 0.15915493667125702f, -q);
@@ -28,12 +25,12 @@ __device__ __forceinline__ float trev(float x) {
 }
 __device__ __forceinline__ float tact(float v, int act) {
   if (act == NA_ACT_LEAKY_RELU) return __builtin_amdgcn_fmed3f(v, v * 0.01f, 3.0e38f);
-  if (act == NA_ACT_SIN) return NA_TRAIN_POLY_SIN ? sin_cw(v) : __builtin_amdgcn_sinf(trev(v));
+  if (act == NA_ACT_SIN) return __builtin_amdgcn_sinf(trev(v));
   return v;
 }
 __device__ __forceinline__ float tact_grad(float v, int act) {
   if (act == NA_ACT_LEAKY_RELU) return v > 0.f ? 1.f : 0.01f;
-  if (act == NA_ACT_SIN) return NA_TRAIN_POLY_SIN ? cos_cw(v) : __builtin_amdgcn_cosf(trev(v));
+  if (act == NA_ACT_SIN) return __builtin_amdgcn_cosf(trev(v));
   return 1.f;
 }
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Run-to-run reproducibility of the one-launch mip renderer (render_ls.hip MODEL 6): the same 96 x 800 band N times, mismatching
-pixels against the first run.  NA_LIB_PATH selects an experiment library (tools/ls_variant.py build NAME -DNA_LS_MIP_ABLATE=..)."""
+pixels against the first run.  NA_LIB_PATH selects an experiment library (tools/ls_variant.py build NAME -DNA_FOO=..)."""
 import math
 import os
 import sys

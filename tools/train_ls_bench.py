@@ -1,5 +1,5 @@
 """Timing of the one-launch training forward alone (ops.train_plain_view_ls, 262 144 and 1 048 576 samples); NA_LIB_PATH picks a variant
-library built by tools/ls_variant.py (e.g. `build tr_nostore --prec bf16x3 -DNA_LS_TRAIN_EXP=1`): the ablation table of DESIGN 3d."""
+library built by tools/ls_variant.py (`build NAME --prec bf16x3 -DNA_FOO=1 ...`)."""
 import math, os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import nerf_atlas_amd.nerf as nerf
