@@ -188,6 +188,43 @@ int na_bezier_warp_latent(const float* est, int est_stride, const float* pts, co
  * of two buffers (skip connection): x = [x0 (in0 cols) | x1 (in1 cols)].                      */
 int na_linear_f32(const float* x0, int in0, const float* x1, int in1, int64_t N,
                   const float* W, const float* b, int out, int pre_act, float* y, void* stream);
+/* na_linear_f32 for rows that live inside wider buffers and for a per-RAY bias (the hoisted spherical-harmonic head below:
+ * src/neural_blocks.py:279-296 with the ray-constant columns of `init` folded into the bias).  x0 / x1 are read with the row
+ * pitches ld0 >= in0 / ld1 >= in1 (floats), so a column slice such as `first_out[..., 1:]` goes in without a copy.  Bias: `b` [out]
+ * broadcast, or `b_rows` [R, out] added as b_rows[n % R] (rows sample-major, n = t R + r, N a multiple of R), or neither; passing
+ * both is NA_EINVAL.  Same kernel template and the same arithmetic as na_linear_f32.                                            */
+int na_linear_f32_rows(const float* x0, int in0, int64_t ld0, const float* x1, int in1, int64_t ld1, int64_t N,
+                       const float* W, const float* b, const float* b_rows, int64_t R, int out, int pre_act, float* y,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Spherical-harmonic colour head, refl kind "sph-har" (src/refl.py:696-731; csrc/sh_head.hip).  Rows sample-major: the ray of
+ * row n is n % R.  All arithmetic fp32.
+ *
+ * na_sh_shade           eval_sh + F.normalize + the head's activation (src/spherical_harmonics.py:55-106, src/refl.py:726-731):
+ *                       rgb[n, c] = sigmoid_kind( sum_k coeffs[n, c K + k] Y_k(dirs[n % R] / max(|dirs[n % R]|, 1e-12)) ),
+ *                       K = (order + 1)^2, order 0..4 (NA_EINVAL otherwise), the 3 K coefficients channel-major like the
+ *                       reference's reshape(..., 3, K).  coeffs [N, 3 K] with row pitch ld; dirs [R, 3] un-normalised (R = N for
+ *                       one direction per sample); pre: NULL or [N, 3], the sums in front of the activation (for the backward).
+ *                       The basis is evaluated in registers; kind: every NA_SIG_*, anything else NA_EUNSUPPORTED.
+ * na_sh_shade_backward  g_coeffs[n, c K + k] = g_rgb[n, c] * sigmoid_kind'(pre[n, c]) * Y_k (contiguous [N, 3 K]).  The
+ *                       directions receive no gradient.
+ * na_sh_view_terms      the ray-only part of the head's SkipConnMLP (src/neural_blocks.py:279-296 with
+ *                       init = [v | enc(v) | latent], v = dir_to_elev_azim(view) of src/utils.py:247-254 and enc the FourierEncoder
+ *                       of src/neural_blocks.py:36-55): with f = [elev, azim | sin(v B) | cos(v B)] (2 + 2 F values, bit-identical
+ *                       to na_view_elaz + na_fourier_encode) of every ray,
+ *                           terms[0, r, :] = w_init . f + b_init;   terms[1, r, :] = w_a . leaky_relu(f) + b_a;   terms[2] likewise (w_b),
+ *                       w_init [hidden, 2 + 2 F] with row pitch ld_init = the view columns of `init.weight`; w_a / w_b with row
+ *                       pitch ld_skip = the view columns of the two skip Linears (`layers.0`, `layers.3`); basis [2, F], scale =
+ *                       the encoder's extra_scale; terms [3, R, hidden].  F <= 128 and hidden in {32, 64, 96, 128}, else
+ *                       NA_EUNSUPPORTED.  The terms are the `b_rows` of na_linear_f32_rows over the remaining (latent) columns. */
+int na_sh_shade(const float* coeffs, int64_t ld, const float* dirs, int64_t N, int64_t R, int order, int kind,
+                float* rgb, float* pre, void* stream);
+int na_sh_shade_backward(const float* g_rgb, const float* pre, const float* dirs, int64_t N, int64_t R, int order,
+                         int kind, float* g_coeffs, void* stream);
+int na_sh_view_terms(const float* dirs, int64_t R, const float* basis, int F, float scale, const float* w_init,
+                     int64_t ld_init, const float* b_init, const float* w_a, const float* b_a, const float* w_b,
+                     const float* b_b, int64_t ld_skip, int hidden, float* terms, void* stream);
 
 typedef struct NaMlpDesc {
   int32_t in_size;     /* raw input width (p)                                         */

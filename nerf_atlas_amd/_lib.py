@@ -70,6 +70,12 @@ SIGNATURES = {
                                         c_f32p, C.c_void_p]),
     "na_linear_f32": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_i64, c_f32p, c_f32p, C.c_int, C.c_int, c_f32p,
                                 C.c_void_p]),
+    "na_linear_f32_rows": (C.c_int, [c_f32p, C.c_int, c_i64, c_f32p, C.c_int, c_i64, c_i64, c_f32p, c_f32p, c_f32p, c_i64, C.c_int,
+                                     C.c_int, c_f32p, C.c_void_p]),
+    "na_sh_shade": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, c_i64, C.c_int, C.c_int, c_f32p, c_f32p, C.c_void_p]),
+    "na_sh_shade_backward": (C.c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_i64, C.c_int, C.c_int, c_f32p, C.c_void_p]),
+    "na_sh_view_terms": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_int, C.c_float, c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p,
+                                   c_f32p, c_i64, C.c_int, c_f32p, C.c_void_p]),
     "na_mlp_packed_bytes": (C.c_size_t, [C.POINTER(NaMlpDesc), C.c_int]),
     "na_mlp_pack": (C.c_int, [C.POINTER(NaMlpDesc), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                               C.c_void_p, C.c_void_p]),

@@ -226,6 +226,26 @@ class PosLinearCombineFn(Function):
         return g_lin, g_pos, None
 
 
+class ShShadeFn(Function):
+    """act(eval_sh(order, coeffs.reshape(..., 3, K), normalize(dirs))) (src/refl.py:726-731, src/spherical_harmonics.py:55-106) as one
+    node: coeffs [..., 3 K], dirs [R, 3] (row n -> ray n % R).  The directions carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, coeffs, dirs, order, kind):
+        ctx.order, ctx.kind, ctx.shape = order, kind, coeffs.shape
+        rgb, pre = ops.sh_shade(coeffs, dirs, order, kind, want_pre=True)
+        ctx.save_for_backward(pre, dirs)
+        return rgb
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError("ShShadeFn: d(colour)/d(view direction) has no HIP backward")
+        pre, dirs = ctx.saved_tensors
+        g_c = ops.sh_shade_backward(g.contiguous().reshape(-1, 3), pre.reshape(-1, 3), dirs, ctx.order, ctx.kind)
+        return g_c.reshape(ctx.shape), None, None, None
+
+
 class ActDerivFn(Function):
     """m = act'(x) as a differentiable node (its own derivative is act''(x): -sin for sin, 0 for LeakyReLU)."""
 

@@ -33,6 +33,7 @@ ARCH = "gfx950"
 UNITS = [
     ("basic_ops.hip", [], ""),
     ("linear_f32.hip", [], ""),
+    ("sh_head.hip", [], ""),
     ("backward.hip", [], ""),
     ("train_gemm.hip", [], ""),
     ("train_bwd.hip", [], ""),

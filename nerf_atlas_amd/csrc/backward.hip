@@ -85,24 +85,7 @@ __global__ void eikonal_backward_kernel(const float* __restrict__ nrm, int64_t N
   }
 }
 
-__device__ __forceinline__ float sigmoid_kind_grad(float v, int kind) {
-  const float s = sigmoidf_(v);
-  switch (kind) {
-    case NA_SIG_NORMAL: return s * (1.f - s);
-    case NA_SIG_THIN: return s * (1.f - s) * (1.f + 2.f * -1e-2f);
-    case NA_SIG_FAT: return s * (1.f - s) * (1.f + 2.f * 1e-2f);
-    case NA_SIG_TANH: { float t = tanhf(v); return 1.f - t * t; }
-    case NA_SIG_UPSHIFTED: return s * (1.f - s);
-    case NA_SIG_RELU: return v > 0.f ? 1.f : 0.f;
-    case NA_SIG_SIN: return cosf(v);
-    case NA_SIG_LEAKY_RELU: return v > 0.f ? 1.f : 0.01f;
-    case NA_SIG_UPSHIFTED_SOFTPLUS: return s;
-    case NA_SIG_UPSHIFTED_RELU: return v > 0.f ? 1.f : 0.f;
-    case NA_SIG_CYCLIC: return cosf(v / 5.f) / 5.f / 2.f * (1.f + 2.f * -1e-2f);
-    default: return 1.f;
-  }
-}
-
+// (sigmoid_kind_grad: common.h, shared with csrc/sh_head.hip)
 __global__ void sigmoid_backward_kernel(const float* __restrict__ x, const float* __restrict__ g, int64_t n, int kind,
                                         float* __restrict__ out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)

@@ -268,12 +268,7 @@ __global__ void hash_encode_kernel(const float* __restrict__ x, int64_t N, const
 
 // ------------------------------------------------------------------------------------ fourier / positional
 // src/utils.py:14-17: [sin(x@B) | cos(x@B)], accurate sinf/cosf (arguments reach 1e3).
-__device__ __forceinline__ void fourier_sincos(float m, float& sn, float& cs) {
-  // Cody-Waite reduction + polynomials (common.h: 1.6e-7 / 5e-7 for |m| <= 3e3, the same pair the fused prologues use in the
-  // parity mode); larger arguments (a basis far beyond the reference's sigma 16 / 32) take libm's large-argument path
-  if (fabsf(m) <= 3.0e3f) sincos_cw(m, sn, cs);
-  else { sn = sinf(m); cs = cosf(m); }
-}
+// (fourier_sincos: common.h -- the per-ray view terms of csrc/sh_head.hip produce the same features)
 // VEC: F is a multiple of 4 -- a thread owns 4 consecutive frequencies of one sample: 16-byte stores, a quarter of the store
 // instructions (the one-frequency-per-thread form ran at 30 % of the HBM rate whatever the sine cost)
 template <bool VEC>

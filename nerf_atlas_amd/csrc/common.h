@@ -233,6 +233,33 @@ __device__ __forceinline__ uint32_t hash_index(int lx, int ly, int lz) {
   return (((uint32_t)lx) ^ ((uint32_t)ly * 2654435761u) ^ ((uint32_t)lz * 805459861u)) & 0xFFFFu;
 }
 
+// sin / cos of one Fourier feature (src/utils.py:14-17; arguments reach 1e3): Cody-Waite reduction + polynomials (1.6e-7 / 5e-7 for
+// |m| <= 3e3, the same pair the fused prologues use in the parity mode); larger arguments (a basis far beyond the reference's
+// sigma 16 / 32) take libm's large-argument path.  Shared by na_fourier_encode and na_sh_view_terms: bit-identical features.
+__device__ __forceinline__ void fourier_sincos(float m, float& sn, float& cs) {
+  if (fabsf(m) <= 3.0e3f) sincos_cw(m, sn, cs);
+  else { sn = sinf(m); cs = cosf(m); }
+}
+
+// d/dv of apply_sigmoid_kind (src/utils.py:484-518)
+__device__ __forceinline__ float sigmoid_kind_grad(float v, int kind) {
+  const float s = sigmoidf_(v);
+  switch (kind) {
+    case NA_SIG_NORMAL: return s * (1.f - s);
+    case NA_SIG_THIN: return s * (1.f - s) * (1.f + 2.f * -1e-2f);
+    case NA_SIG_FAT: return s * (1.f - s) * (1.f + 2.f * 1e-2f);
+    case NA_SIG_TANH: { float t = tanhf(v); return 1.f - t * t; }
+    case NA_SIG_UPSHIFTED: return s * (1.f - s);
+    case NA_SIG_RELU: return v > 0.f ? 1.f : 0.f;
+    case NA_SIG_SIN: return cosf(v);
+    case NA_SIG_LEAKY_RELU: return v > 0.f ? 1.f : 0.01f;
+    case NA_SIG_UPSHIFTED_SOFTPLUS: return s;
+    case NA_SIG_UPSHIFTED_RELU: return v > 0.f ? 1.f : 0.f;
+    case NA_SIG_CYCLIC: return cosf(v / 5.f) / 5.f / 2.f * (1.f + 2.f * -1e-2f);
+    default: return 1.f;
+  }
+}
+
 // dir_to_elev_azim (src/utils.py:247-254)
 __device__ __forceinline__ void elev_azim(float dx, float dy, float dz, float& elev, float& azim) {
   const float lim = 1.f - 1e-6f;

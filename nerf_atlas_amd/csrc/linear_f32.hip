@@ -20,10 +20,15 @@ __device__ __forceinline__ float act_in(float v, int act) {
   return v;
 }
 
+// ROWS (na_linear_f32_rows): x0 / x1 are read with the row pitches ld0 / ld1 (column slices of wider buffers), and the bias of row n
+// is b_rows[(n % R) * out + j] when b_rows is given -- a per-RAY bias for sample-major rows n = t R + r (csrc/sh_head.hip).  Without
+// ROWS the extra arguments are unused and the kernel is the one na_linear_f32 has always launched.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict__ x0, int in0,
                                                          const float* __restrict__ x1, int in1, int64_t N,
                                                          const float* __restrict__ W, const float* __restrict__ b,
-                                                         int out, int act, float* __restrict__ y) {
+                                                         int out, int act, float* __restrict__ y, int64_t ld0, int64_t ld1,
+                                                         const float* __restrict__ b_rows, int R) {
   __shared__ float Xs[LBM * LLD];
   __shared__ float Ws[LBN * LLD];
   const int in = in0 + in1;
@@ -45,7 +50,9 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict
       float xv = 0.f, wv = 0.f;
       if (k < in) {
         if (n < N) {
-          float raw = k < in0 ? x0[n * in0 + k] : x1[n * in1 + (k - in0)];
+          float raw;
+          if constexpr (ROWS) raw = k < in0 ? x0[n * ld0 + k] : x1[n * ld1 + (k - in0)];
+          else raw = k < in0 ? x0[n * in0 + k] : x1[n * in1 + (k - in0)];
           xv = act_in(raw, act);
         }
         int o = o0 + lrow;
@@ -64,6 +71,20 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict
   const int j = o0 + wc * 32 + (lane & 31);
   if (j < out) {
     float bj = b != nullptr ? b[j] : 0.f;
+    if constexpr (ROWS) {
+      if (b_rows != nullptr) {
+        // the tile's 64 consecutive rows are consecutive rays (wrapping at R): one 64-bit remainder per workgroup
+        const int ray0 = (int)(n0 % R);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int off = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          const int64_t n = n0 + off;
+          const int ray = (ray0 + off) % R;
+          if (n < N) y[n * out + j] = acc[r] + b_rows[(int64_t)ray * out + j];
+        }
+        return;
+      }
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int64_t n = n0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
@@ -86,7 +107,29 @@ extern "C" int na_linear_f32(const float* x0, int in0, const float* x1, int in1,
   int64_t gx = (N + LBM - 1) / LBM;
   NA_REQUIRE(gx < (1ll << 31), NA_EINVAL, "na_linear_f32: N too large");
   dim3 grid((unsigned)gx, (unsigned)((out + LBN - 1) / LBN));
-  hipLaunchKernelGGL(linear_f32_kernel, grid, dim3(256), 0, (hipStream_t)stream, x0, in0, x1, in1, N, W, b, out, pre_act,
-                     y);
+  hipLaunchKernelGGL(linear_f32_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x0, in0, x1, in1, N, W, b, out, pre_act,
+                     y, (int64_t)0, (int64_t)0, (const float*)nullptr, 1);
   return check_launch("na_linear_f32");
+}
+
+extern "C" int na_linear_f32_rows(const float* x0, int in0, int64_t ld0, const float* x1, int in1, int64_t ld1, int64_t N,
+                                  const float* W, const float* b, const float* b_rows, int64_t R, int out, int pre_act, float* y,
+                                  void* stream) {
+  using namespace na;
+  NA_REQUIRE(x0 && W && y, NA_ENULL, "na_linear_f32_rows: null pointer");
+  NA_REQUIRE(in0 >= 1 && in1 >= 0 && out >= 1 && N >= 0, NA_EINVAL, "na_linear_f32_rows: bad shape in0=%d in1=%d out=%d", in0,
+             in1, out);
+  NA_REQUIRE(in1 == 0 || x1 != nullptr, NA_ENULL, "na_linear_f32_rows: in1>0 needs x1");
+  NA_REQUIRE(ld0 >= in0 && (in1 == 0 || ld1 >= in1), NA_EINVAL, "na_linear_f32_rows: a row pitch is smaller than its width");
+  NA_REQUIRE(!(b && b_rows), NA_EINVAL, "na_linear_f32_rows: pass the broadcast bias or the per-ray bias, not both");
+  NA_REQUIRE(b_rows == nullptr || (R >= 1 && R < (1ll << 30) && N % R == 0), NA_EINVAL,
+             "na_linear_f32_rows: per-ray bias needs 1 <= R < 2^30 and N a multiple of R (N=%lld R=%lld)", (long long)N, (long long)R);
+  NA_REQUIRE(pre_act >= NA_ACT_NONE && pre_act <= NA_ACT_SIN, NA_EUNSUPPORTED, "na_linear_f32_rows: activation %d", pre_act);
+  if (N == 0) return NA_OK;
+  int64_t gx = (N + LBM - 1) / LBM;
+  NA_REQUIRE(gx < (1ll << 31), NA_EINVAL, "na_linear_f32_rows: N too large");
+  dim3 grid((unsigned)gx, (unsigned)((out + LBN - 1) / LBN));
+  hipLaunchKernelGGL(linear_f32_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x0, in0, x1, in1, N, W, b, out, pre_act, y,
+                     ld0, ld1, b_rows, b_rows ? (int)R : 1);
+  return check_launch("na_linear_f32_rows");
 }

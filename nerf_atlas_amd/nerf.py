@@ -414,7 +414,9 @@ class PlainNeRF(CommonNeRF):
             # explicit sample positions (D-NeRF: warped points, + its per-sample reflectance latent) through the one-launch renderer
             out, self.alpha, self.weights = self._render_head(head, rays.contiguous(), ts, True, pts=pts.contiguous(), refl_latent=refl_latent)
             return self._finish_sky(out)
-        if not self.training and not ag.needs_grad(pts, *self.parameters()) and refl_latent is None and self.mip is None:
+        # (refl.SphericalHarmonic: the generic branch below IS its fast path -- per-ray hoisted kernels inside the head)
+        if (not self.training and not ag.needs_grad(pts, *self.parameters()) and refl_latent is None and self.mip is None
+                and not isinstance(self.refl, refl.SphericalHarmonic)):
             utils.note_fallback(f"plain-unfused-{type(self.refl).__name__}-{self.intermediate_size}",
                                 f"PlainNeRF with {type(self.refl).__name__} reflectance / intermediate size {self.intermediate_size} is not one of the "
                                 "fused renderer's schedules (View head, intermediate 64, 3 channels): inference runs the generic MLP kernels "

@@ -501,6 +501,108 @@ def linear_f32(x0: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor], pre
     return y
 
 
+def linear_f32_rows(x0: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor], pre_act: str = "none",
+                    x1: Optional[torch.Tensor] = None, b_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [N, out] = W . act([x0 | x1]) + bias, exact fp32 like linear_f32 (na_linear_f32_rows).  x0 [..., in0] / x1 [..., in1] may be
+    column slices of wider buffers (`first_out[..., 1:]`): their row pitch goes down, no copy.  bias: b [out], or b_rows [R, out]
+    added as b_rows[n % R] (sample-major rows n = t R + r), or none."""
+    lib = _lib.load()
+    W = _f32(W, "W")
+    out = W.shape[0]
+    x0, ld0 = _rows(x0, x0.shape[-1], "x0")
+    N, in0 = x0.shape
+    in1, ld1 = 0, 0
+    if x1 is not None:
+        x1, ld1 = _rows(x1, x1.shape[-1], "x1")
+        in1 = x1.shape[1]
+        assert x1.shape[0] == N, (x1.shape, N)
+    assert W.dim() == 2 and W.shape[1] == in0 + in1, (W.shape, in0, in1)
+    assert b is None or b_rows is None, "pass the broadcast bias or the per-ray bias, not both"
+    R = 1
+    if b is not None:
+        b = _f32(b, "b")
+        assert b.shape == (out,), b.shape
+    if b_rows is not None:
+        b_rows = _f32(b_rows, "b_rows")
+        assert b_rows.dim() == 2 and b_rows.shape[1] == out and b_rows.shape[0] >= 1 and N % b_rows.shape[0] == 0, (b_rows.shape, N, out)
+        R = b_rows.shape[0]
+    y = torch.empty(N, out, device=x0.device, dtype=torch.float32)
+    check(lib.na_linear_f32_rows(_ptr(x0), in0, ld0, _ptr(x1), in1, ld1, N, _ptr(W), _ptr(b), _ptr(b_rows), R, out, ACT[pre_act],
+                                 _ptr(y), _stream()))
+    return y
+
+
+# ------------------------------------------------------------------------------------------------- spherical-harmonic head
+def _sh_dirs(dirs: torch.Tensor, N: int):
+    dirs = _f32(dirs, "dirs")
+    assert dirs.dim() == 2 and dirs.shape[1] == 3 and dirs.shape[0] >= 1 and N % dirs.shape[0] == 0, (dirs.shape, N)
+    return dirs
+
+
+def sh_shade(coeffs: torch.Tensor, dirs: torch.Tensor, order: int, kind: str, want_pre: bool = False):
+    """rgb [..., 3] = sigmoid_kind(eval_sh(order, coeffs.reshape(..., 3, K), normalize(dirs))) (na_sh_shade).  coeffs [..., 3 K]
+    channel-major, a column slice of a wider buffer allowed; dirs [R, 3] un-normalised, one per ray of the sample-major rows
+    (row n -> ray n % R; R = N: one direction per sample).  want_pre: also the [..., 3] sums in front of the activation."""
+    lib = _lib.load()
+    if kind not in SIGMOID:
+        raise NotImplementedError(f"Unknown sigmoid kind({kind})")
+    if not 0 <= order <= 4:
+        raise ValueError(f"spherical-harmonic order {order} outside 0..4")
+    K3 = 3 * (order + 1) ** 2
+    assert coeffs.shape[-1] == K3, (coeffs.shape, order)
+    c2, ld = _rows(coeffs, K3, "coeffs")
+    N = c2.shape[0]
+    dirs = _sh_dirs(dirs, N)
+    rgb = torch.empty(tuple(coeffs.shape[:-1]) + (3,), device=coeffs.device, dtype=torch.float32)
+    pre = torch.empty_like(rgb) if want_pre else None
+    check(lib.na_sh_shade(_ptr(c2), ld, _ptr(dirs), N, dirs.shape[0], order, SIGMOID[kind], _ptr(rgb), _ptr(pre), _stream()))
+    return (rgb, pre) if want_pre else rgb
+
+
+def sh_shade_backward(g_rgb: torch.Tensor, pre: torch.Tensor, dirs: torch.Tensor, order: int, kind: str) -> torch.Tensor:
+    """g_coeffs [N, 3 K] of sh_shade given g_rgb [N, 3] and the saved pre-activation sums [N, 3] (na_sh_shade_backward)."""
+    lib = _lib.load()
+    g_rgb, pre = _f32(g_rgb, "g_rgb"), _f32(pre, "pre")
+    assert g_rgb.shape == pre.shape and g_rgb.shape[-1] == 3 and 0 <= order <= 4, (g_rgb.shape, pre.shape, order)
+    N = g_rgb.numel() // 3
+    dirs = _sh_dirs(dirs, N)
+    out = torch.empty(N, 3 * (order + 1) ** 2, device=g_rgb.device, dtype=torch.float32)
+    check(lib.na_sh_shade_backward(_ptr(g_rgb), _ptr(pre), _ptr(dirs), N, dirs.shape[0], order, SIGMOID[kind], _ptr(out), _stream()))
+    return out
+
+
+def _view_cols(w: torch.Tensor, width: int, name: str):
+    """the view columns of a Linear's weight, as the column slice they are: (tensor, row pitch)"""
+    if not w.is_cuda or w.dtype != torch.float32:
+        raise ValueError(f"{name} must be a float32 CUDA(HIP) tensor")
+    assert w.dim() == 2 and w.shape[1] == width, (name, w.shape, width)
+    if w.stride(1) != 1 or w.stride(0) < width:
+        w = w.contiguous()
+    return w, w.stride(0)
+
+
+def sh_view_terms(dirs: torch.Tensor, basis: torch.Tensor, scale: float, w_init: torch.Tensor, b_init: torch.Tensor,
+                  w_a: torch.Tensor, b_a: torch.Tensor, w_b: torch.Tensor, b_b: torch.Tensor) -> torch.Tensor:
+    """terms [3, R, hidden] (na_sh_view_terms): the per-ray part of the spherical-harmonic head's three wide Linears.  dirs [R, 3];
+    basis [2, F]; w_init [hidden, 2 + 2 F] = init.weight[:, :2 + 2 F] and w_a / w_b = the view columns of the two skip Linears, all
+    three passed as the column slices they are; b_*: the Linears' biases."""
+    lib = _lib.load()
+    dirs, basis = _f32(dirs, "dirs"), _f32(basis, "basis")
+    assert dirs.dim() == 2 and dirs.shape[1] == 3 and basis.dim() == 2 and basis.shape[0] == 2, (dirs.shape, basis.shape)
+    R, F = dirs.shape[0], basis.shape[1]
+    hidden = w_init.shape[0]
+    w_init, ld_init = _view_cols(w_init, 2 + 2 * F, "w_init")
+    w_a, ld_a = _view_cols(w_a, 2 + 2 * F, "w_a")
+    w_b, ld_b = _view_cols(w_b, 2 + 2 * F, "w_b")
+    assert w_a.shape[0] == hidden and w_b.shape[0] == hidden and ld_a == ld_b, (w_a.shape, w_b.shape, ld_a, ld_b)
+    b_init, b_a, b_b = _f32(b_init, "b_init"), _f32(b_a, "b_a"), _f32(b_b, "b_b")
+    assert b_init.shape == b_a.shape == b_b.shape == (hidden,), (b_init.shape, b_a.shape, b_b.shape)
+    terms = torch.empty(3, R, hidden, device=dirs.device, dtype=torch.float32)
+    check(lib.na_sh_view_terms(_ptr(dirs), R, _ptr(basis), F, float(scale), _ptr(w_init), ld_init, _ptr(b_init), _ptr(w_a), _ptr(b_a),
+                               _ptr(w_b), _ptr(b_b), ld_a, hidden, _ptr(terms), _stream()))
+    return terms
+
+
 def train_gemm_packed_ok(N: int, M: int) -> bool:
     """Does a batch of N rows with M output columns run the training GEMMs that take packed operands (na_train_gemm_packed_ok)?"""
     return bool(_lib.load().na_train_gemm_packed_ok(int(N), int(M)))

@@ -1,4 +1,4 @@
-"""Colour heads on the hot path (src/refl.py:17-49,100-122,190-290,733-751): View, Positional, PosLinearView.
+"""Colour heads on the hot path (src/refl.py:17-49,100-122,190-290,696-751): View, Positional, PosLinearView, SphericalHarmonic.
 The relighting heads of the reference (Basic, Diffuse, CookTorrance, Rusin*, ...) keep their registry keys and
 raise NotImplementedError (out of scope)."""
 import torch
@@ -6,7 +6,8 @@ import torch.nn as nn
 
 from . import autograd as ag
 from . import ops
-from .neural_blocks import HashEncoder, SkipConnMLP
+from . import utils
+from .neural_blocks import FourierEncoder, HashEncoder, SkipConnMLP
 from .utils import load_sigmoid
 
 
@@ -108,6 +109,94 @@ class PosLinearView(Reflectance):
         return ops.pos_linear_combine(raw, pos_all, self.out_features)
 
 
+class SphericalHarmonic(Reflectance):
+    """src/refl.py:696-731: act(eval_sh(order, mlp(elaz(view), latent).reshape(..., 3, K), normalize(view))), K = (order + 1)^2; the MLP
+    is 5 x 128, LeakyReLU, xavier, over [elaz(view) (2) | Fourier(elaz(view)) (256) | latent].  No light, no normal, no position.
+
+    Exact fp32 in every precision mode (the head is 128 wide: no packed form for the fused MFMA kernels).  Two routes:
+      hoisted  inference with the directions broadcast along the sample axis (PlainNeRF / DynamicNeRF): the 258 ray-constant input
+               columns of `init`, `layers.0` and `layers.3` are multiplied once per RAY (ops.sh_view_terms) and enter the per-sample
+               Linears as a per-ray bias (ops.linear_f32_rows over the latent columns, read where `first` left them); no [N, 2],
+               [N, 256] or [N, 322] tensor exists.
+      plain    training, or one direction per sample: the MLP through SkipConnMLP's own paths, then the expansion as one kernel
+               (autograd.ShShadeFn / ops.sh_shade)."""
+
+    def __init__(self, space=None, order: int = 2, view="elaz", **kwargs):
+        super().__init__(**kwargs)
+        if not (isinstance(order, int) and 0 <= order <= 4):
+            raise ValueError(f"spherical-harmonic order must be an integer in 0..4, got {order!r}")
+        if view != "elaz":
+            raise NotImplementedError(f"SphericalHarmonic(view={view!r}): only the reference's default view encoding 'elaz' is built")
+        self.order = order
+        self.mlp = SkipConnMLP(in_size=2, out=self.out_features * (order + 1) * (order + 1), latent_size=self.latent_size,
+                               enc=FourierEncoder(input_dims=2), num_layers=5, hidden_size=128, init="xavier")
+
+    def _hoistable(self, view, latent):
+        m = self.mlp
+        return (self.out_features == 3 and view.is_cuda and view.dim() >= 2 and (view.stride(0) == 0 or view.shape[0] == 1)
+                and torch.is_tensor(latent) and latent.is_cuda and latent.dtype == torch.float32
+                and latent.shape[:-1] == view.shape[:-1] and latent.shape[-1] == m.latent_size and m.latent_size >= 1
+                and not m.last_layer_act and len(m.layers) == 5 and m.skip == 3 and m.act_name == "leaky_relu"
+                and isinstance(m.enc, FourierEncoder) and m.enc.input_dims == 2 and m.enc.freqs <= 128
+                and m.init.out_features in (32, 64, 96, 128)
+                and not ag.needs_grad(view, latent, *self.parameters()))
+
+    def _latent_weights(self):
+        """[init.weight[:, 258:], [layers.0.weight[:, :128] | [:, 386:]], the same of layers.3] as contiguous matrices: what is left of
+        the three wide Linears once their view columns are per-ray terms (cached; rebuilt when a parameter changed)."""
+        m = self.mlp
+        lins = [m.init, m.layers[0], m.layers[3]]
+        stamp = utils.pack_stamp(lins)
+        hit = self.__dict__.get("_lat_w")
+        if hit is None or stamp is None or hit[0] != stamp:
+            H, vc = m.init.out_features, m.in_size + m.enc.output_dims()
+            ws = [m.init.weight.data[:, vc:].contiguous()]
+            ws += [torch.cat([l.weight.data[:, :H], l.weight.data[:, H + vc:]], dim=1).contiguous() for l in lins[1:]]
+            hit = self.__dict__["_lat_w"] = (stamp, ws)
+        return hit[1]
+
+    def _forward_hoisted(self, dirs, latent, kind):
+        m = self.mlp
+        H, vc = m.init.out_features, m.in_size + m.enc.output_dims()
+        L = m.layers
+        terms = ops.sh_view_terms(dirs, m.enc.basis.data, float(m.enc.extra_scale), m.init.weight.data[:, :vc], m.init.bias.data,
+                                  L[0].weight.data[:, H:H + vc], L[0].bias.data, L[3].weight.data[:, H:H + vc], L[3].bias.data)
+        w_init, w_0, w_3 = self._latent_weights()
+        lat = latent  # (`first_out[..., 1:]`: a column slice, read with its row pitch)
+        x = ops.linear_f32_rows(lat, w_init, None, "none", b_rows=terms[0])
+        x = ops.linear_f32_rows(x, w_0, None, "leaky_relu", x1=lat, b_rows=terms[1])
+        x = ops.linear_f32_rows(x, L[1].weight.data, L[1].bias.data, "leaky_relu")
+        x = ops.linear_f32_rows(x, L[2].weight.data, L[2].bias.data, "leaky_relu")
+        x = ops.linear_f32_rows(x, w_3, None, "leaky_relu", x1=lat, b_rows=terms[2])
+        x = ops.linear_f32_rows(x, L[4].weight.data, L[4].bias.data, "leaky_relu")
+        coeffs = ops.linear_f32_rows(x, m.out.weight.data, m.out.bias.data, "leaky_relu")
+        return ops.sh_shade(coeffs, dirs, self.order, kind)
+
+    def forward(self, x, view, normal=None, light=None, latent=None):
+        if hasattr(latent, "tensor") and not torch.is_tensor(latent):
+            latent = latent.tensor()  # lazy IPE latent (utils.MipLatent): these kernels read materialised columns
+        if view.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("SphericalHarmonic: d(colour)/d(view direction) has no HIP backward")
+        kind = self.act_kind if self.act_kind in ops.SIGMOID else "identity"
+        finish = (lambda t: t) if self.act_kind in ops.SIGMOID else self.act  # (an activation passed as a callable runs behind the kernel)
+        batches = view.shape[:-1]
+        per_ray = view.dim() >= 2 and (view.stride(0) == 0 or view.shape[0] == 1)
+        if self._hoistable(view, latent):
+            dirs = view[0].reshape(-1, 3).contiguous()
+            return finish(self._forward_hoisted(dirs, latent, kind).reshape(batches + (3,)))
+        if per_ray:
+            # directions broadcast along the sample axis: one elev / azim and one basis per RAY
+            dirs = view[0].reshape(-1, 3).contiguous()
+            v = ops.view_elaz(dirs).reshape((1,) + batches[1:] + (2,)).expand(batches + (2,))
+        else:
+            dirs = view.reshape(-1, 3).contiguous()
+            v = ops.view_elaz(dirs).reshape(batches + (2,))
+        coeffs = self.mlp(v, latent)
+        if ag.needs_grad(coeffs):
+            return finish(ag.ShShadeFn.apply(coeffs, dirs, self.order, kind))
+        return finish(ops.sh_shade(coeffs, dirs, self.order, kind))
+
+
 def _out_of_scope(name):
     def cons(*a, **k):
         raise NotImplementedError(f"refl kind '{name}' is a relighting head outside the volume-rendering hot path")
@@ -116,9 +205,9 @@ def _out_of_scope(name):
 
 # src/refl.py:733-751: same keys
 refl_kinds = {
-    "pos": Positional, "view": View, "pos-linear-view": PosLinearView,
+    "pos": Positional, "view": View, "pos-linear-view": PosLinearView, "sph-har": SphericalHarmonic,
     **{k: _out_of_scope(k) for k in ["view-light", "basic", "diffuse", "cook-torrance", "rusin", "rusin-helmholtz",
-                                     "sph-har", "fourier", "weighted"]},
+                                     "fourier", "weighted"]},
 }
 
 
@@ -131,5 +220,8 @@ def load(args, refl_kind: str, space_kind: str, latent_size: int):
         raise NotImplementedError(f"refl kind: {refl_kind}")
     if getattr(args, "light_kind", None) is not None:
         raise NotImplementedError("lights are outside the volume-rendering hot path")
+    kwargs = {}
+    if refl_kind == "sph-har":
+        kwargs["order"] = getattr(args, "refl_order", 2)  # src/refl.py:33
     return cons(latent_size=latent_size, act=args.sigmoid_kind, out_features=args.feature_space,
-                normal=getattr(args, "normal_kind", None), bidirectional=getattr(args, "refl_bidirectional", True))
+                normal=getattr(args, "normal_kind", None), bidirectional=getattr(args, "refl_bidirectional", True), **kwargs)

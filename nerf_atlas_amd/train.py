@@ -30,7 +30,7 @@ DEFAULTS = dict(
     data=None, data_kind="original", derive_kind=True, size=32, render_size=16, epochs=30000, batch_size=8,
     crop_size=16, test_crop_size=0, steps=64, mip=None, sigmoid_kind="upshifted", feature_space=3, model="plain",
     dyn_model=None, bg="black", learning_rate=5e-4, seed=1337, decay=0.0, loss_fns=["l2"], sched_min=5e-5,
-    no_sched=False, shape_to_refl_size=64, refl_kind="view", space_kind="identity", normal_kind=None,
+    no_sched=False, shape_to_refl_size=64, refl_kind="view", refl_order=2, space_kind="identity", normal_kind=None,
     refl_bidirectional=True, sdf_kind="mlp", near=2.0, far=6.0, spline=0, dyn_refl_latent=0, time_gamma=False,
     volsdf_scale_decay=0.0, delta_x_decay=0.0, opt_step=1, clip_gradients=0.0, train_imgs=-1, serial_idxs=False,
     higher_end_chance=0, opt_kind="adam", light_kind=None, occ_kind=None, volsdf_alternate=False, test_white_bg=False,

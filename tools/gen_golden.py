@@ -704,9 +704,83 @@ def g19():
          fn_weights=g3w, fn_rand=rand3, fn_sky=sky, **spec(names, shapes))
 
 
+# ------------------------------------------------------------------ G20 spherical-harmonic colour head (src/refl.py:696-731)
+SH_KINDS = ["normal", "thin", "fat", "tanh", "upshifted", "relu", "sin", "leaky_relu", "upshifted_softplus", "upshifted_relu",
+            "cyclic", "identity"]  # nerf_atlas_amd.ops.SIGMOID; "identity" = eval_sh itself (the reference has no such key)
+SH_GRAD_ROWS = 8   # the gradient is recorded for the first rows only (the special directions + 4 random): file size
+
+
+def g20():
+    """g20_sh_eval: act(eval_sh(deg, coeffs, normalize(dirs))) of the reference in fp32 and fp64 for degrees 0..4 and every activation
+    kind, + the gradient of sum(out * probe) w.r.t. the coefficients in fp32 and fp64 (first SH_GRAD_ROWS directions).  Coefficients
+    [257, 3 K] and probe [257, 3] are proc_uniform(shape, seed, 1.0) of the stored seeds.
+    g20_plain_sph-har_o{0..4}: the g11 recipe with the sph-har head, fp32 and fp64.  g20_plain_sph-har_grads: order 2, fp64 gradients."""
+    import copy
+    import src.spherical_harmonics as rsh
+    F = torch.nn.functional
+    act_of = lambda k: (lambda v: v) if k == "identity" else rutils.load_sigmoid(k)
+    n = 257
+    dirs = torch.from_numpy(proc_uniform((n, 3), 2001, 1.5)).float()
+    dirs[0] = torch.tensor([0.0, 0.0, 2.0])      # both poles
+    dirs[1] = torch.tensor([0.0, 0.0, -0.5])
+    dirs[2] = torch.tensor([1.5, 0.0, 0.0])      # axis-aligned
+    dirs[3] = torch.tensor([0.0, 0.7, -0.3])     # zero x
+    kw = dict(dirs=dirs, kinds=np.array(SH_KINDS), grad_rows=SH_GRAD_ROWS)
+    for deg in range(5):
+        K = (deg + 1) ** 2
+        co = torch.from_numpy(proc_uniform((n, 3 * K), 2010 + deg, 1.0)).float()
+        probe = torch.from_numpy(proc_uniform((n, 3), 2020 + deg, 1.0)).float()
+        # (not stored: the test regenerates both with oracle.procedural.proc_uniform from these seeds)
+        kw[f"coeffs_seed{deg}"], kw[f"probe_seed{deg}"] = 2010 + deg, 2020 + deg
+        for dt, tag in ((torch.float32, "32"), (torch.float64, "64")):
+            outs, grads = [], []
+            for kind in SH_KINDS:
+                with torch.enable_grad():
+                    c = co.detach().to(dt).clone().requires_grad_()
+                    o = act_of(kind)(rsh.eval_sh(deg, c.reshape(n, 3, K), F.normalize(dirs.to(dt), dim=-1)))
+                    (o * probe.to(dt)).sum().backward()
+                outs.append(o.detach())
+                grads.append(c.grad[:SH_GRAD_ROWS].clone())
+            kw[f"out{tag}_{deg}"] = torch.stack(outs)
+            kw[f"grad{tag}_{deg}"] = torch.stack(grads)
+    save("g20_sh_eval", **kw)
+
+    size, T = 6, 16
+    recipe = [("upshifted", "black"), ("normal", "black"), ("leaky_relu", "white"), ("thin", "black"), ("upshifted", "black")]
+    c, focal = cam(POSES[:2], size)
+    rays = c.sample_positions(ref_pixel_grid(size, (0, 0, size, size)), size=size)
+    for order, (act, bg) in enumerate(recipe):
+        m = rnerf.PlainNeRF(steps=T, t_near=2.0, t_far=6.0, intermediate_size=64, sigmoid_kind=act, bg=bg)
+        m.set_refl(rrefl.refl_kinds["sph-har"](latent_size=64, act=act, out_features=3, order=order))
+        m.eval()
+        names, shapes = fill_procedural(m)
+        out = m(rays)
+        ts, alpha, weights = m.ts, m.alpha, m.weights
+        m64 = copy.deepcopy(m).double()
+        out64 = m64(rays.double())
+        dev, devw = float((out.double() - out64).abs().max()), float((weights.double() - m64.weights).abs().max())
+        print(f"g20 order {order} ({act}/{bg}): |out - out64| {dev:.2e}, |weights - weights64| {devw:.2e}")
+        assert dev <= 5e-5, dev  # a fixture whose fp32 value is itself noisy is never written
+        save(f"g20_plain_sph-har_o{order}", rays=rays, out=out, out64=out64, steps=T, near=2.0, far=6.0, bg=bg, act=act, order=order,
+             ts=ts, alpha=alpha, alpha64=m64.alpha, weights=weights, weights64=m64.weights, **spec(names, shapes))
+        if order == 2:
+            keys = ["refl.mlp.out.weight", "refl.mlp.out.bias", "refl.mlp.layers.3.weight", "refl.mlp.init.weight", "first.out.weight"]
+            # a weighted MEAN (|loss| < 1): a sum over 216 entries could not be compared to 1e-6 absolute in fp32
+            probe = torch.from_numpy(proc_uniform(tuple(out.shape), 2030, 1.0)).double() / out.numel()
+            with torch.enable_grad():
+                for p_ in m64.parameters():
+                    p_.requires_grad_(p_.is_floating_point())
+                loss = (m64(rays.double()) * probe).sum()
+                loss.backward()
+            named = dict(m64.named_parameters())
+            save("g20_plain_sph-har_grads", rays=rays, probe=probe, loss=loss.detach(), steps=T, near=2.0, far=6.0, bg=bg, act=act,
+                 order=order, grad_names=np.array(keys), **{"grad_" + k: named[k].grad.float() for k in keys},
+                 **spec(names, shapes))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20"]
     for g in which:
         globals()[g]()
     with open(os.path.join(OUT, "PROVENANCE.txt"), "w") as f:

@@ -40,6 +40,9 @@ RECIPES = {
     "plain": (False, ["--model", "plain", "--refl-kind", "view"]),
     # `make original` (reference makefile:8-13: --model plain --refl-kind pos -lr 2e-4 --loss-fns l2) on the small scene
     "original": (False, ["--model", "plain", "--refl-kind", "pos", "--loss-fns", "l2", "-lr", "2e-4"]),
+    # `make nerf-sh` (reference makefile:64-72: --model plain --refl-kind sph-har --sigmoid-kind leaky_relu -lr 1e-3) on the small
+    # scene, recorded with --epochs 200
+    "nerf_sh": (False, ["--model", "plain", "--refl-kind", "sph-har", "--sigmoid-kind", "leaky_relu", "-lr", "1e-3"]),
     "dnerf": (True, ["--model", "plain", "--refl-kind", "view", "--data-kind", "dnerf", "--dyn-model", "plain",
                      "--spline", "4"]),
     # `make dnerf`'s regularisers (reference makefile:106-114) on the small scene: NR-NeRF offset decay + the FFJORD
