@@ -503,7 +503,9 @@ int na_render_tiny_ls(const float* rays, const float* pts, int64_t R, const floa
  * t * R + ray, row pitch feat_ld >= 65 floats): column 0 the signed distance, columns 1..64 the latent the SDF network
  * produced; the kernel turns the distance into the Laplace density with scale beta[0] (device pointer), evaluates
  * refl.View (x, elev / azim of the ray, latent -> sigmoid_kind(rgb)) and composites with the density used as it is (no
- * softplus).  na_render_view_ls_pack takes View.mlp's 6 Linears {init, layers.0..3, out}.  Workspace and `pts` as for
+ * softplus).  beta == NULL: column 0 is a density LOGIT instead, sigma = softplus(column 0 - 1) as PlainNeRF's
+ * alpha_from_density (src/nerf.py:60-73) -- NeRFAE's rows from na_ae_front; bg_kind black / white as na_render_plain_view_ls.
+ * na_render_view_ls_pack takes View.mlp's 6 Linears {init, layers.0..3, out}.  Workspace and `pts` as for
  * na_render_plain_view_ls.                                                                                          */
 size_t na_render_view_ls_packed_bytes(int precision);
 int na_render_view_ls_pack(int precision, const float* const* w, const float* const* b, void* packed, void* stream);
@@ -669,6 +671,39 @@ int na_render_plain_plv_ls(const float* rays, const float* pts, int64_t R, const
                            const float* hash_tables_refl, const float* refl_latent, int64_t rl_ld, int n_rl, const void* packed,
                            int precision, int sigmoid_kind, int bg_kind, float* alpha, float* weights, float* out,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * NeRFAE, `--model ae` (the reference's src/nerf.py:766-840; csrc/ae_front.hip).  The model's FRONT as one launch: per sample
+ *     encoded   = encode(p)            SkipConnMLP(in 3, FourierEncoder 128 frequencies, 5 x 128, skip 3, out E)   (src/nerf.py:784-788,822)
+ *     encoded   = F.normalize(encoded) when `normalize` != 0 (divide by max(|encoded|, 1e-12))                     (src/nerf.py:824)
+ *     first_out = density_tform(encoded)  SkipConnMLP(in E, 5 x 64, skip 3, out 1 + I)                             (src/nerf.py:790-793,826)
+ * with the 256 Fourier features generated in the kernel wherever a Linear consumes them and every hidden activation of both
+ * networks in registers: only the finished row of a sample reaches memory,
+ *     y[(t * R + ray) * y_ld + 0] = first_out[0] (the density logit) | + 1 .. 1 + E = encoded | + 1 + E .. 1 + E + I = first_out[1:],
+ * which for E + I = 64 is the `feat` row of na_render_view_ls (column 0 | the 64 latent columns in the order refl.View receives
+ * them, src/nerf.py:832-836).  Positions: rays [R,6] x ts [T], or explicit pts [T,R,3] (rays may then be NULL).  basis [3,128] fp32
+ * with any extra_scale multiplied in.  na_ae_front_pack takes the 7 Linears {init, layers.0..4, out} of each network (nn.Linear
+ * layout, reference column order [hidden | p 3 | sin 128 | cos 128] in the skip layers; biases may be NULL).
+ * Arithmetic: the three-product bf16 split (hi * hi + hi * lo + lo * hi, fp32 accumulation) under every `precision` NA_PREC_BF16 /
+ * NA_PREC_BF16X3 / NA_PREC_F16X -- operands with fp32's range, so there is no range guard.  E in {16, 32, 64}, I in {32, 64},
+ * y_ld >= 1 + E + I; everything else NA_EUNSUPPORTED (the host then runs the per-layer path).
+ *
+ * The two row operators of the model's differentiable path (widths 1..64, row pitches in floats):
+ * na_row_normalize            y = F.normalize(x, dim=-1)  (src/nerf.py:824);  _backward: g_x = (g_y - y <y, g_y>) / max(|x|, 1e-12)
+ * na_row_sqnorm_mean          out[0] += mean_n |x_n|^2  (torch.linalg.norm(encoded, dim=-1).square().mean(), src/nerf.py:811); `out`
+ *                             zeroed by the caller; reduced through the fixed-point accumulator under na_set_deterministic;
+ *                             _backward: g_x = g[0] * 2 x / N.                                                          */
+size_t na_ae_front_packed_bytes(int precision, int E, int I);
+int na_ae_front_pack(int precision, int E, int I, const float* const* w_enc, const float* const* b_enc,
+                     const float* const* w_den, const float* const* b_den, void* packed, void* stream);
+int na_ae_front(const float* rays, const float* pts, int64_t R, const float* ts, int T, const float* basis, const void* packed,
+                int precision, int E, int I, int normalize, float* y, int64_t y_ld, void* stream);
+int na_row_normalize(const float* x, int64_t x_ld, int64_t N, int W, float* y, int64_t y_ld, void* stream);
+int na_row_normalize_backward(const float* x, int64_t x_ld, const float* g_y, int64_t g_ld, int64_t N, int W, float* g_x,
+                              int64_t gx_ld, void* stream);
+int na_row_sqnorm_mean(const float* x, int64_t x_ld, int64_t N, int W, float* out, void* stream);
+int na_row_sqnorm_mean_backward(const float* x, int64_t x_ld, const float* g, int64_t N, int W, float* g_x, int64_t gx_ld,
+                                void* stream);
 
 #ifdef __cplusplus
 }

@@ -162,6 +162,14 @@ SIGNATURES = {
     "na_mlp_fourier_ls_packed_bytes": (C.c_size_t, [C.c_int]),
     "na_mlp_fourier_ls_pack": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "na_mlp_fourier_ls": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_int, c_f32p, c_i64, C.c_void_p]),
+    "na_ae_front_packed_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "na_ae_front_pack": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "na_ae_front": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
+                              c_i64, C.c_void_p]),
+    "na_row_normalize": (C.c_int, [c_f32p, c_i64, c_i64, C.c_int, c_f32p, c_i64, C.c_void_p]),
+    "na_row_normalize_backward": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, c_i64, C.c_int, c_f32p, c_i64, C.c_void_p]),
+    "na_row_sqnorm_mean": (C.c_int, [c_f32p, c_i64, c_i64, C.c_int, c_f32p, C.c_void_p]),
+    "na_row_sqnorm_mean_backward": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.c_int, c_f32p, c_i64, C.c_void_p]),
     "na_resample_ts_lds_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "na_resample_ts": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, C.c_void_p]),
     "na_render_plain_view_ls_rayts": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int,

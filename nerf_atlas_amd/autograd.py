@@ -294,6 +294,34 @@ class EikonalFn(Function):
         return ops.eikonal_loss_backward(normals, g.contiguous())
 
 
+class RowNormalizeFn(Function):
+    """F.normalize(x, dim=-1) over rows of width <= 64 (NeRFAE --normalize-latent, src/nerf.py:824)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return ops.row_normalize(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return ops.row_normalize_backward(x, g.contiguous())
+
+
+class RowSqnormMeanFn(Function):
+    """torch.linalg.norm(x, dim=-1).square().mean() (NeRFAE's latent_l2_loss, src/nerf.py:811)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return ops.row_sqnorm_mean(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return ops.row_sqnorm_mean_backward(x, g.contiguous())
+
+
 class CompositeFn(Function):
     """alpha_from_density + volumetric_integrate + sky (src/nerf.py:60-80,96-98).  Returns (out, alpha, weights);
     alpha/weights are auxiliary (non-differentiable) outputs."""

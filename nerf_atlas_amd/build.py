@@ -34,6 +34,7 @@ UNITS = [
     ("basic_ops.hip", [], ""),
     ("linear_f32.hip", [], ""),
     ("sh_head.hip", [], ""),
+    ("ae_front.hip", [], ""),
     ("backward.hip", [], ""),
     ("train_gemm.hip", [], ""),
     ("train_bwd.hip", [], ""),

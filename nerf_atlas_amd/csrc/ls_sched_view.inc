@@ -23,7 +23,11 @@
         }
         own_setup(pass);
         if (prev >= 0) composite(prev_geom(prev, tprev), oc[0], density);
-        {  // Laplace density of this pass's sample (src/utils.py:50-58, src/nerf.py:1000-1003), composited one pass later
+        if (a.beta == nullptr) {
+          // column 0 is a density logit (NeRFAE's rows): PlainNeRF's law sigma = softplus(d - 1) (src/nerf.py:60-73), computed as the
+          // PlainNeRF schedules compute it; `composite` takes the result as it is (max(sigma, 0) changes nothing)
+          density = fast_softplus(sdfv - 1.0f);
+        } else {  // Laplace density of this pass's sample (src/utils.py:50-58, src/nerf.py:1000-1003), composited one pass later
           const float sc = a.beta[0];
           const float scaled = (-sdfv) / sc;
           const float cdf = scaled <= 0.f ? fast_exp(fminf(scaled, 0.f)) * 0.5f : 1.f - fast_exp(-fmaxf(scaled, 0.f)) * 0.5f;

@@ -406,7 +406,7 @@ extern "C" int na_render_view_ls(const float* rays, const float* pts, int64_t R,
                                  size_t workspace_bytes, void* stream) {
   NA_REQUIRE(T >= 1 && R >= 0, NA_EINVAL, "na_render_view_ls: bad shape T=%d R=%lld", T, (long long)R);
   if (R == 0) return NA_OK;
-  NA_REQUIRE(rays && ts && feat && beta && packed && out && workspace, NA_ENULL, "na_render_view_ls: null pointer");
+  NA_REQUIRE(rays && ts && feat && packed && out && workspace, NA_ENULL, "na_render_view_ls: null pointer");  // (beta NULL: density logit)
   NA_REQUIRE(feat_ld >= 65, NA_EINVAL, "na_render_view_ls: feat_ld %d < 65 (signed distance + 64 latent columns)", feat_ld);
   NA_REQUIRE(precision == NA_PREC_BF16 || precision == NA_PREC_BF16X3 || precision == NA_PREC_F16 || precision == NA_PREC_F16X, NA_EUNSUPPORTED,
              "na_render_view_ls: precision %d", precision);

@@ -1,5 +1,5 @@
 """Model-variant plugins of the hot path with the reference's protocol (src/nerf.py):
-TinyNeRF, PlainNeRF, VolSDF, DynamicNeRF(spline) + the registries model_kinds / dyn_model_kinds / load_nerf /
+TinyNeRF, PlainNeRF, NeRFAE, VolSDF, DynamicNeRF(spline) + the registries model_kinds / dyn_model_kinds / load_nerf /
 load_dyn.  Every forward runs HIP kernels only; PlainNeRF with the View head takes the fully fused renderer.
 
 Protocol kept for callers (runner.py): forward(rays) / forward((rays, times)), from_pts(...), .nerf, .refl,
@@ -452,6 +452,130 @@ class PlainNeRF(CommonNeRF):
         return self._composite(density, rgb, ts, rays)
 
 
+# ------------------------------------------------------------------------------------------------- NeRFAE
+class NeRFAE(CommonNeRF):
+    """src/nerf.py:766-840: NeRF with a thin middle layer.  encode (Fourier, 5 x 128) -> [F.normalize] -> density_tform (5 x 64) ->
+    density | intermediate; refl.View on cat[encoded, intermediate].
+
+    Inference routes of `from_pts` (eval mode, no gradients wanted, engine "ls"):
+      fused        both narrow networks as ONE launch (ops.ae_front, csrc/ae_front.hip) writing the [N, 1 + E + I] rows, then the View
+                   head + compositing as one launch (ops.render_view_ls with beta=None: MODEL 2 on a density logit): E + I = 64
+      front-only   the same front launch, then the generic head and compositing (a 96-wide latent, another head, refl_latent)
+    Everything else -- training, E / I without a front kernel -- runs the SkipConnMLP operator path.  `latent_l2_loss` is a training
+    term: the inference routes leave it as it is.  `--mip` raises (the reference's mip latent would enter `encode`; not built)."""
+
+    def __init__(self, out_features: int = 3, encoding_size: int = 32, normalize_latent: bool = False, **kwargs):
+        if kwargs.get("mip") is not None:
+            raise NotImplementedError("--model ae with --mip: the IPE latent as an input of `encode` is not implemented")
+        super().__init__(r=lambda _: refl.View(out_features=out_features, latent_size=encoding_size + self.intermediate_size),
+                         **kwargs)
+        from .neural_blocks import FourierEncoder
+        self.latent_size = self.total_latent_size()
+        self.encode = SkipConnMLP(in_size=3, out=encoding_size, latent_size=self.latent_size, num_layers=5, hidden_size=128,
+                                  enc=FourierEncoder(input_dims=3), init="xavier")
+        self.density_tform = SkipConnMLP(in_size=encoding_size, out=1 + self.intermediate_size, latent_size=0, num_layers=5,
+                                         hidden_size=64, init="xavier")
+        self.encoding_size = encoding_size
+        self.regularize_latent = False
+        self.normalize_latent = normalize_latent
+
+    def set_regularize_latent(self):
+        self.regularize_latent = True
+        self.latent_l2_loss = 0
+
+    # ---- fused inference
+    def _front_ok(self, pts):
+        wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        e = self.encode
+        return (config.engine == "ls" and config.precision in ("bf16", "bf16x3", "f16x") and not self.training and not wants_grad
+                and not ag.needs_grad(pts) and pts.is_cuda and ops.ae_front_supported(self.encoding_size, self.intermediate_size)
+                and e.enc.freqs == 128 and e.latent_size == 0 and e.act_name == "leaky_relu"
+                and self.density_tform.act_name == "leaky_relu")
+
+    def _head_ok(self, refl_latent):
+        r = self.refl
+        return (type(r) is refl.View and refl_latent is None and self.encoding_size + self.intermediate_size == 64
+                and r.latent_size == 64 and r.out_features == 3 and getattr(r, "act_kind", None) in ops.SIGMOID)
+
+    def packed_front(self, precision: str):
+        lin = self.encode._linears() + self.density_tform._linears()
+        stamp = utils.pack_stamp(lin)
+        cache = self.__dict__.setdefault("_packed_front", {})
+        hit = cache.get(precision)
+        if hit is None or stamp is None or hit[0] != stamp:
+            wb = lambda m: ([l.weight.data for l in m._linears()], [l.bias.data for l in m._linears()])
+            cache[precision] = (stamp, ops.ae_front_pack(precision, self.encoding_size, self.intermediate_size, wb(self.encode),
+                                                         wb(self.density_tform)))
+        return cache[precision][1]
+
+    def packed_view_ls(self, precision: str):
+        lin = self.refl.mlp._linears()
+        stamp = utils.pack_stamp(lin)
+        cache = self.__dict__.setdefault("_packed_view_ls", {})
+        hit = cache.get(precision)
+        if hit is None or stamp is None or hit[0] != stamp:
+            cache[precision] = (stamp, ops.render_view_ls_pack(precision, [l.weight.data for l in lin], [l.bias.data for l in lin]))
+        return cache[precision][1]
+
+    def _basis(self):
+        enc = self.encode.enc
+        return (enc.basis.data * float(enc.extra_scale)).contiguous() if float(enc.extra_scale) != 1.0 else enc.basis.data
+
+    def front_rows(self, rays, ts, pts=None):
+        """[T, ..., 1 + E + I] rows [density logit | encoded | intermediate] by the one-launch front."""
+        prec = config.kernel_precision(has_f16x=True)
+        return ops.ae_front(rays.contiguous(), ts, self._basis(), self.packed_front(prec), prec, self.encoding_size,
+                            self.intermediate_size, self.normalize_latent, pts=None if pts is None else pts.contiguous())
+
+    @_f16x_policy
+    def forward(self, rays):
+        pts, self.ts, r_o, r_d, _ = compute_pts_ts(rays, self.t_near, self.t_far, self.steps, perturb=self._perturb())
+        return self.from_pts(pts, self.ts, r_o, r_d, rays=rays)
+
+    def compute_encoded(self, pts, ts, r_o, r_d):
+        """src/nerf.py:814-822 (no instance latents, no mip: `encode` sees the positions only)."""
+        return self.encode(pts, None)
+
+    def from_pts(self, pts, ts, r_o, r_d, refl_latent=None, rays=None):
+        if rays is None: rays = torch.cat([r_o, r_d], dim=-1).contiguous()
+        self.ts, self.ts_ray = ts, None
+        if self._front_ok(pts) and (refl_latent is None or not ag.needs_grad(refl_latent)):
+            rows = self.front_rows(rays, ts, pts)
+            if self._head_ok(refl_latent):
+                prec = config.kernel_precision(has_f16x=True)
+                out, self.alpha, self.weights = ops.render_view_ls(rays.contiguous(), ts, rows, None, self.packed_view_ls(prec), prec,
+                                                                    self.refl.act_kind, self._kernel_bg(), True, pts=pts.contiguous())
+                return self._finish_sky(out)
+            utils.note_fallback(f"ae-front-only-{type(self.refl).__name__}-{self.encoding_size}-{self.intermediate_size}",
+                                f"NeRFAE with {type(self.refl).__name__} reflectance over a {self.encoding_size} + {self.intermediate_size} "
+                                "wide latent is not the fused View schedule (View head, 64 latent columns): the front runs as one "
+                                "kernel, the head and the compositing run the generic kernels")
+            density = rows[..., 0].contiguous()
+            view = r_d.unsqueeze(0).expand_as(pts)
+            rgb = self.refl(x=pts, view=view, latent=cat_not_none(rows[..., 1:], refl_latent))  # column slice: passed by pitch
+            return self._composite(density, rgb, ts, rays)
+        encoded = self.compute_encoded(pts, ts, r_o, r_d)
+        if self.regularize_latent:
+            self.latent_l2_loss = ag.RowSqnormMeanFn.apply(encoded) if ag.needs_grad(encoded) else ops.row_sqnorm_mean(encoded)
+        return self.from_encoded(encoded, ts, r_d, pts, refl_latent, rays=rays)
+
+    def from_encoded(self, encoded, ts, r_d, pts, refl_latent=None, rays=None):
+        """src/nerf.py:823-840 on the operator path (HIP forward and backward kernels per Linear)."""
+        if rays is None: raise ValueError("NeRFAE.from_encoded needs the rays [..., 6] (compositing reads the directions)")
+        if self.normalize_latent:
+            encoded = ag.RowNormalizeFn.apply(encoded) if ag.needs_grad(encoded) else ops.row_normalize(encoded)
+        first_out = self.density_tform(encoded)
+        if ag.needs_grad(first_out):
+            density, intermediate = ag.SplitHeadFn.apply(first_out)
+        else:
+            density, intermediate = first_out[..., 0].contiguous(), first_out[..., 1:]
+        if self.training and self.noise_std > 0:
+            density = density + utils.randn(density.shape, density.device) * self.noise_std
+        view = r_d.unsqueeze(0).expand_as(pts)
+        rgb = self.refl(x=pts, view=view, latent=torch.cat([encoded, cat_not_none(intermediate, refl_latent)], dim=-1))
+        return self._composite(density, rgb, ts, rays)
+
+
 # ------------------------------------------------------------------------------------------------- VolSDF
 class VolSDF(CommonNeRF):
     """src/nerf.py:861-1018, volume path only (uniform samples, Laplace density, relu, no sky term)."""
@@ -731,8 +855,8 @@ def _experimental(name):
 
 
 # src/nerf.py:1706-1720 / 1698-1704: same keys
-model_kinds = {"tiny": TinyNeRF, "plain": PlainNeRF, "volsdf": VolSDF,
-               **{k: _experimental(k) for k in ["ae", "coarse_fine", "mpi", "voxel", "rig", "hist"]}}
+model_kinds = {"tiny": TinyNeRF, "plain": PlainNeRF, "ae": NeRFAE, "volsdf": VolSDF,
+               **{k: _experimental(k) for k in ["coarse_fine", "mpi", "voxel", "rig", "hist"]}}
 dyn_model_kinds = {"plain": DynamicNeRF, **{k: _experimental(k) for k in ["ae", "rig", "long", "voxel"]}}
 
 
@@ -742,16 +866,25 @@ def load_nerf(args):
     kwargs = {"mip": load_mip(args), "out_features": args.feature_space, "steps": args.steps, "t_near": args.near,
               "t_far": args.far, "intermediate_size": args.shape_to_refl_size, "sigmoid_kind": args.sigmoid_kind,
               "bg": args.bg}
+    if args.model != "ae": args.latent_l2_weight = 0  # src/nerf.py:113
     cons = model_kinds.get(args.model, None)
     if cons is None: raise NotImplementedError(args.model)
+    if args.model == "ae":
+        kwargs["normalize_latent"] = getattr(args, "normalize_latent", False)
+        kwargs["encoding_size"] = getattr(args, "encoding_size", 32)
     if args.model == "volsdf":
         kwargs["sdf"] = load_sdf(args, with_integrator=False)
         kwargs["occ_kind"] = getattr(args, "occ_kind", None)
-    return cons(**kwargs)
+    model = cons(**kwargs)
+    if args.model == "ae" and getattr(args, "latent_l2_weight", 0) > 0: model.set_regularize_latent()  # src/nerf.py:143
+    return model
 
 
 def load_dyn(args, model, device=None):
     """src/nerf.py:1680-1696."""
     cons = dyn_model_kinds.get(args.dyn_model, None)
     if cons is None: raise NotImplementedError(f"Unknown dyn kind: {args.dyn_model}")
+    if isinstance(model, NeRFAE) and cons is DynamicNeRF:
+        raise NotImplementedError("--model ae under --dyn-model plain: training the deformation needs d(FourierEncoder)/d(position), which "
+                                  "has no HIP backward (DESIGN.md 8); the reference's own pairing, --dyn-model ae, is broken at HEAD")
     return cons(canonical=model, spline=args.spline, refl_latent=args.dyn_refl_latent)

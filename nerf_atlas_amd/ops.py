@@ -1358,6 +1358,97 @@ def mlp_fourier_ls(rays: torch.Tensor, ts: torch.Tensor, basis: torch.Tensor, pa
     return y
 
 
+AE_SIZES = ((16, 32, 64), (32, 64))  # (encoding sizes, intermediate sizes) na_ae_front is instantiated for
+
+
+def ae_front_supported(E: int, I: int) -> bool:
+    return E in AE_SIZES[0] and I in AE_SIZES[1]
+
+
+def ae_front_pack(precision: str, E: int, I: int, enc_wb, den_wb) -> torch.Tensor:
+    """Pack NeRFAE's two narrow SkipConnMLPs -- encode (Fourier, 5 x 128, out E) and density_tform (5 x 64, out 1 + I), each
+    ({init, layers.0..4, out} weights, biases) -- into the weight stream of na_ae_front."""
+    lib = _lib.load()
+    (w1, b1), (w2, b2) = enc_wb, den_wb
+    assert len(w1) == 7 and len(b1) == 7 and len(w2) == 7 and len(b2) == 7
+    w1 = [_f32(w.detach(), "weight") for w in w1]
+    w2 = [_f32(w.detach(), "weight") for w in w2]
+    b1 = [None if b is None else _f32(b.detach(), "bias") for b in b1]
+    b2 = [None if b is None else _f32(b.detach(), "bias") for b in b2]
+    shapes = [(128, 259), (128, 387), (128, 128), (128, 128), (128, 387), (128, 128), (E, 128),
+              (64, E), (64, 64 + E), (64, 64), (64, 64), (64, 64 + E), (64, 64), (1 + I, 64)]
+    for w, shp in zip(w1 + w2, shapes):
+        if tuple(w.shape) != shp:
+            raise ValueError(f"NeRFAE front: weight shape {tuple(w.shape)} != {shp}")
+    nbytes = int(lib.na_ae_front_packed_bytes(PREC[precision], E, I))
+    if nbytes == 0:
+        raise _lib.NaError(f"NeRFAE front: precision {precision} / E {E} / I {I} not supported")
+    ptrs = lambda ts: (C.c_void_p * 7)(*[0 if t is None else t.data_ptr() for t in ts])
+    packed = torch.empty(nbytes, device=w1[0].device, dtype=torch.uint8)
+    check(lib.na_ae_front_pack(PREC[precision], E, I, ptrs(w1), ptrs(b1), ptrs(w2), ptrs(b2), _ptr(packed), _stream()))
+    return packed
+
+
+def ae_front(rays: torch.Tensor, ts: torch.Tensor, basis: torch.Tensor, packed: torch.Tensor, precision: str, E: int, I: int,
+             normalize: bool = False, pts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """NeRFAE's front in one launch at the samples of rays [..., 6] x ts [T] (or explicit pts [T, ..., 3]) -> rows [T, ..., 1 + E + I] =
+    [density logit | encoded (normalised if asked) | first_out[1:]]: with E + I = 64 what `render_view_ls(beta=None)` takes as feat.
+    basis [3, 128] (FourierEncoder.basis x extra_scale)."""
+    lib = _lib.load()
+    rays, ts, basis = _f32(rays, "rays"), _f32(ts, "ts"), _f32(basis, "basis")
+    assert tuple(basis.shape) == (3, 128), basis.shape
+    T = ts.shape[0]
+    R = rays.numel() // 6
+    if pts is not None:
+        pts = _f32(pts, "pts")
+        assert pts.numel() == T * R * 3, (pts.shape, T, R)
+    ld = 1 + E + I
+    y = torch.empty((T,) + tuple(rays.shape[:-1]) + (ld,), device=rays.device, dtype=torch.float32)
+    check(lib.na_ae_front(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(basis), _ptr(packed), PREC[precision], E, I, int(bool(normalize)),
+                          _ptr(y), ld, _stream()))
+    return y
+
+
+def row_normalize(x: torch.Tensor) -> torch.Tensor:
+    """F.normalize(x, dim=-1) for rows of width <= 64 (column slices go down with their pitch)."""
+    lib = _lib.load()
+    W = x.shape[-1]
+    x2, ld = _rows(x, W, "x")
+    y = torch.empty(x2.shape, device=x.device, dtype=torch.float32)
+    check(lib.na_row_normalize(_ptr(x2), ld, x2.shape[0], W, _ptr(y), W, _stream()))
+    return y.reshape(x.shape)
+
+
+def row_normalize_backward(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    lib = _lib.load()
+    W = x.shape[-1]
+    x2, ld = _rows(x, W, "x")
+    g2, gld = _rows(g, W, "g")
+    gx = torch.empty(x2.shape, device=x.device, dtype=torch.float32)
+    check(lib.na_row_normalize_backward(_ptr(x2), ld, _ptr(g2), gld, x2.shape[0], W, _ptr(gx), W, _stream()))
+    return gx.reshape(x.shape)
+
+
+def row_sqnorm_mean(x: torch.Tensor) -> torch.Tensor:
+    """torch.linalg.norm(x, dim=-1).square().mean() -> 0-dim tensor (fixed-point reduction in the deterministic mode)."""
+    lib = _lib.load()
+    W = x.shape[-1]
+    x2, ld = _rows(x, W, "x")
+    out = torch.zeros(1, device=x.device, dtype=torch.float32)
+    check(lib.na_row_sqnorm_mean(_ptr(x2), ld, x2.shape[0], W, _ptr(out), _stream()))
+    return out.reshape(())
+
+
+def row_sqnorm_mean_backward(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    lib = _lib.load()
+    W = x.shape[-1]
+    x2, ld = _rows(x, W, "x")
+    g = _f32(g.reshape(1), "g")
+    gx = torch.empty(x2.shape, device=x.device, dtype=torch.float32)
+    check(lib.na_row_sqnorm_mean_backward(_ptr(x2), ld, _ptr(g), x2.shape[0], W, _ptr(gx), W, _stream()))
+    return gx.reshape(x.shape)
+
+
 def render_tiny_ls_pack(precision: str, weights, biases) -> torch.Tensor:
     """Pack TinyNeRF.estim ({init, layers.0..5, out}) into the weight stream of the layer-synchronous renderer."""
     lib = _lib.load()
@@ -1418,14 +1509,15 @@ def render_view_ls(rays: torch.Tensor, ts: torch.Tensor, feat: torch.Tensor, bet
                    precision: str, sigmoid_kind: str = "thin", bg: str = "black", want_weights: bool = False,
                    pts: Optional[torch.Tensor] = None):
     """View head + compositing in one kernel.  feat [T, *rays.shape[:-1], >= 65]: column 0 signed distance, 1..64 latent
-    (the SDF network's output, rows may be wider); beta: the Laplace scale (0-dim or 1-element device tensor)."""
+    (the SDF network's output, rows may be wider); beta: the Laplace scale (0-dim or 1-element device tensor), or None: column 0
+    is a density logit, sigma = softplus(column 0 - 1) (NeRFAE's rows from `ae_front`)."""
     lib = _lib.load()
     rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
     R = rays.numel() // 6
     T = ts.shape[0]
     feat, ld = _rows(feat, feat.shape[-1], "feat")
     assert feat.shape[0] == T * R and ld >= 65, (feat.shape, T, R, ld)
-    beta = _f32(beta.reshape(1), "beta")
+    beta = None if beta is None else _f32(beta.reshape(1), "beta")
     if bg not in BG:
         raise NotImplementedError(bg)
     workspace = torch.empty(int(lib.na_render_ls_workspace_bytes(T, R)), device=rays.device, dtype=torch.uint8)

@@ -37,6 +37,7 @@ DEFAULTS = dict(
     sdf_eikonal=0.0, ffjord_div_decay=0.0, offset_decay=0.0, dyn_diverge_decay=0.0, smooth_normals=0.0, smooth_eps=1e-3,
     smooth_eps_rng=False, smooth_n_ord=[2],
     neural_upsample=False, quiet=False,
+    encoding_size=32, normalize_latent=False, latent_l2_weight=0.0,  # NeRFAE (runner.py:412-416)
 )
 
 loss_map = {
@@ -104,7 +105,10 @@ def load_model(args, is_dyn=False, device="cuda"):
     model = nerf.load_nerf(args)
     if is_dyn:
         model = nerf.load_dyn(args, model, device)
-    model.set_refl(refl.load(args, args.refl_kind, args.space_kind, model.intermediate_size))
+    # (--model ae: the head sees cat[encoded, intermediate], src/nerf.py:775-778, 832-836 -- the reference's runner drops the encoded
+    # columns here, runner.py:1182-1183, and dies at the first forward: DESIGN.md 7)
+    latent = model.intermediate_size + (args.encoding_size if args.model == "ae" else 0)
+    model.set_refl(refl.load(args, args.refl_kind, args.space_kind, latent))
     return model.to(device)
 
 
@@ -256,6 +260,9 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
         loss = loss_fn(out, ref)
         assert loss.isfinite(), f"Got {loss.item()} loss"
         losses.append(loss.item())
+        if getattr(args, "latent_l2_weight", 0) > 0:
+            # runner.py:681 (which names a bare `latent_l2_weight`: the intended args.latent_l2_weight)
+            loss = loss + args.latent_l2_weight * model.nerf.latent_l2_loss
         if args.volsdf_scale_decay > 0 and isinstance(model, nerf.VolSDF):
             loss = loss + args.volsdf_scale_decay * model.scale_post_act
         if args.delta_x_decay > 0:

@@ -778,9 +778,118 @@ def g20():
                  **spec(names, shapes))
 
 
+AE_CASES = {  # name: (E, I, B, crop (t, l, h, w) of the 6 x 6 frame, bg, act, normalize_latent)
+    "e32_i32_black": (32, 32, 1, (0, 0, 6, 6), "black", "thin", False),
+    "e32_i32_white": (32, 32, 1, (0, 0, 6, 6), "white", "upshifted", False),
+    "e32_i32_norm": (32, 32, 1, (0, 0, 6, 6), "black", "thin", True),
+    "e16_i32": (16, 32, 1, (0, 0, 6, 6), "black", "thin", False),
+    "e32_i64": (32, 64, 2, (2, 0, 3, 5), "black", "thin", False),                # B = 2; the CLI default width, head latent 96
+    "e32_i32_ragged": (32, 32, 1, (0, 1, 5, 5), "white", "thin", False),   # 25 rays: not a multiple of 32
+    "e64_i32_ragged": (64, 32, 1, (1, 0, 5, 6), "black", "normal", True),  # 30 rays
+}
+AE_GRAD_CAP = 6000  # entries kept per gradient tensor (whole rows, evenly spaced): keeps the fixture inside the committed-file limit
+
+
+def _ae_build(E, I, bg, act, norm, T=16):
+    m = rnerf.NeRFAE(steps=T, t_near=2.0, t_far=6.0, intermediate_size=I, encoding_size=E, normalize_latent=norm, sigmoid_kind=act, bg=bg)
+    m.eval()
+    names, shapes = fill_procedural(m)
+    return m, names, shapes
+
+
+def _ae_parts(m, rays):
+    """(out, encoded as the head sees it, first_out, alpha, weights) of the reference class, through its own methods"""
+    out = m(rays)
+    pts, ts, r_o, r_d, _ = rnerf.compute_pts_ts(rays, m.t_near, m.t_far, m.steps)
+    enc = m.compute_encoded(pts, ts, r_o, r_d).reshape(pts.shape[:-1] + (-1,))
+    if m.normalize_latent: enc = torch.nn.functional.normalize(enc, dim=-1)
+    return out, enc, m.density_tform(enc), m.alpha, m.weights, ts
+
+
+def g21():
+    """g21_ae_{case}: the reference's NeRFAE (src/nerf.py:766-840) constructed directly, procedural weights (Fourier basis at sigma 32),
+    eval mode, steps 16, near 2 / far 6, in fp32 AND fp64: encoded (after normalisation where on), first_out, out, alpha, weights.
+    g21_ae_grad: training mode, density noise off, the stratified steps `ts` of one seeded draw stored; loss = mse(out, target) + 0.1 *
+    latent_l2_loss and its fp64 gradient w.r.t. EVERY parameter -- per tensor the L2 norm of the whole gradient and evenly spaced whole
+    rows of it (at most AE_GRAD_CAP entries: two full sets would be 4 MB)."""
+    import copy
+    size = 6
+    for name, (E, I, B, crop, bg, act, norm) in AE_CASES.items():
+        c, focal = cam(POSES[:B], size)
+        rays = c.sample_positions(ref_pixel_grid(size, crop), size=size)
+        m, names, shapes = _ae_build(E, I, bg, act, norm)
+        out, enc, fo, alpha, weights, ts = _ae_parts(m, rays)
+        m64 = copy.deepcopy(m).double()
+        out64, enc64, fo64, alpha64, weights64, _ = _ae_parts(m64, rays.double())
+        opac = weights64[:-1].sum(0)
+        frac = float(((opac > 0.05) & (opac < 0.95)).float().mean())
+        print(f"g21 {name}: opacity before the last sample {float(opac.min()):.2f}..{float(opac.max()):.2f} ({frac:.0%} of rays in 0.05..0.95); "
+              f"fp32 vs fp64: out {float((out.double() - out64).abs().max()):.2e} weights {float((weights.double() - weights64).abs().max()):.2e} "
+              f"encoded {float((enc.double() - enc64).abs().max()):.2e} first_out {float((fo.double() - fo64).abs().max()):.2e}")
+        assert frac >= 0.5, f"{name}: degenerate case (the 1e-4 bar would test nothing)"
+        save(f"g21_ae_{name}", rays=rays, E=E, I=I, steps=16, near=2.0, far=6.0, bg=bg, act=act, normalize=int(norm), ts=ts,
+             encoded=enc, encoded64=enc64, first_out=fo, first_out64=fo64, out=out, out64=out64, alpha=alpha, alpha64=alpha64,
+             weights=weights, weights64=weights64, **spec(names, shapes))
+    kw = {}
+    for name in ("e32_i32_black", "e32_i32_norm"):
+        E, I, B, crop, bg, act, norm = AE_CASES[name]
+        c, focal = cam(POSES[:B], size)
+        rays = c.sample_positions(ref_pixel_grid(size, crop), size=size)
+        m, names, shapes = _ae_build(E, I, bg, act, norm)
+        m.train()
+        m.noise_std = 0
+        m.set_regularize_latent()
+        target = torch.from_numpy(proc_uniform(tuple(rays.shape[:-1]) + (3,), 2101, 0.5)).double() + 0.5
+
+        def step(mm, dt, pts, ts, r_o, r_d):
+            with torch.enable_grad():
+                for p_ in mm.parameters():
+                    p_.requires_grad_(p_.is_floating_point() and p_ is not mm.encode.enc.basis)
+                out = mm.from_pts(pts.to(dt), ts.to(dt), r_o.to(dt), r_d.to(dt))
+                mse = torch.nn.functional.mse_loss(out, target.to(dt))
+                loss = mse + 0.1 * mm.latent_l2_loss
+                loss.backward()
+            return out.detach(), mse.detach(), loss.detach()
+        # The stratified draw decides which pre-activations sit within fp32 rounding of a LeakyReLU kink; one such sample moves a
+        # gradient summed over 576 samples by ~1/576 whatever computes it in fp32 (seed 2100: the reference's OWN fp32 autograd is
+        # 2.2e-3 of the largest entry off its fp64 run on encode.init.weight).  Such a draw measures the kink, not an implementation:
+        # the first seed from 2100 on is taken at which the reference's fp32 gradients are within 1.25e-4 (a quarter of the fp32 bar
+        # of tests/test_gpu_backward.py) of its fp64 gradients on every tensor.
+        for seed in range(2100, 2110):
+            torch.manual_seed(seed)
+            pts, ts, r_o, r_d, _ = rnerf.compute_pts_ts(rays, m.t_near, m.t_far, m.steps, perturb=1)
+            m32, m64 = copy.deepcopy(m), copy.deepcopy(m).double()
+            _, _, loss32 = step(m32, torch.float32, pts, ts, r_o, r_d)
+            out, mse, loss = step(m64, torch.float64, pts, ts, r_o, r_d)
+            g32 = dict(m32.named_parameters())
+            own = max(float((g32[k].grad.double() - p_.grad).abs().max() / p_.grad.abs().max()) for k, p_ in m64.named_parameters() if p_.grad is not None)
+            print(f"g21 grad {name}: seed {seed}: the reference's fp32 gradients are {own:.2e} of the largest entry off its fp64 gradients")
+            if own <= 1.25e-4:
+                break
+        else:
+            raise AssertionError("no usable stratified draw in ten seeds")
+        gnames = [k for k, p_ in m64.named_parameters() if p_.grad is not None]
+        missing = [k for k, p_ in m64.named_parameters() if p_.grad is None]
+        assert missing == ["empty_latent", "encode.enc.basis"], f"every parameter but the zero-size latent and the fixed Fourier basis has a gradient: {missing}"
+        kw.update({f"{name}.rays": rays, f"{name}.ts": ts, f"{name}.ts_seed": seed, f"{name}.target_seed": 2101, f"{name}.loss": loss.detach(), f"{name}.loss32": loss32.detach(), f"{name}.mse": mse.detach(),
+                   f"{name}.latent_l2": m64.latent_l2_loss.detach(), f"{name}.out64": out.detach(), f"{name}.grad_names": np.array(gnames)})
+        named = dict(m64.named_parameters())
+        for k in gnames:
+            g = named[k].grad
+            g2 = g.reshape(g.shape[0], -1)
+            stride = max(1, -(-g2.numel() // AE_GRAD_CAP))
+            kw[f"{name}.grad.{k}"] = g2[::stride].float()
+            kw[f"{name}.stride.{k}"] = stride
+            kw[f"{name}.norm.{k}"] = g.norm()
+        for k, v in spec(names, shapes).items():
+            kw[f"{name}.{k}"] = v
+        print(f"g21 grad {name}: loss {float(loss):.6f} (mse {float(mse):.6f}, latent l2 {float(m64.latent_l2_loss):.6f}; the fp32 run: {float(loss32):.7f}, {abs(float(loss32) - float(loss)):.2e} off), {len(gnames)} gradients")
+    save("g21_ae_grad", **kw)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21"]
     for g in which:
         globals()[g]()
     with open(os.path.join(OUT, "PROVENANCE.txt"), "w") as f:

@@ -9,6 +9,10 @@ tests/test_gpu_train.py derives its end-point bars (a bar must come 
                   arithmetic (tools/train_spread.py on the GPU box -> profiles/r04/train_spread_build.json).
 
     python tools/make_train_spread_fixture.py /tmp/spread_*.json      (build container; the build side is read from profiles/r04)
+
+tests/golden/train_spread_ae.json: the same for the `ae` recipe (reference runs only), a file of its own:
+
+    python tools/make_train_spread_fixture.py --ae /tmp/ae_threads_*.json
 """
 import json
 import os
@@ -17,7 +21,33 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def reference_runs(name, paths):
+    fx = json.load(open(os.path.join(REPO, "tests", "golden", f"train_parity_{name}.json")))
+    runs = [{"threads": fx.get("threads", 8), "test_psnr": fx["test_psnr"], "test_psnr_mean": fx["test_psnr_mean"],
+             "loss_last20_mean": sum(fx["losses"][-20:]) / 20, "source": f"tests/golden/train_parity_{name}.json"}]
+    for path in sorted(paths):
+        d = json.load(open(path))
+        if d.get("name") != name or d.get("seed") != fx.get("seed") or any(r["threads"] == d["threads"] for r in runs):
+            continue
+        assert d["argv"] == fx["argv"] and len(d["losses"]) == len(fx["losses"]), path
+        first = next((i for i, (a, b) in enumerate(zip(d["losses"], fx["losses"])) if abs(a - b) > 1e-3), None)
+        runs.append({"threads": d["threads"], "test_psnr": d["test_psnr"], "test_psnr_mean": d["test_psnr_mean"],
+                     "loss_last20_mean": sum(d["losses"][-20:]) / 20, "first10_max_loss_diff": max(abs(a - b) for a, b in zip(d["losses"][:10], fx["losses"][:10])),
+                     "first_iteration_1e-3_apart": first, "max_loss_diff": max(abs(a - b) for a, b in zip(d["losses"], fx["losses"])),
+                     "source": "tools/ref_train_fixture.py --threads %d" % d["threads"]})
+    return runs
+
+
+def main_ae(paths):
+    runs = reference_runs("ae", paths)
+    path = os.path.join(REPO, "tests", "golden", "train_spread_ae.json")
+    json.dump({"ae": {"reference_runs": runs}}, open(path, "w"), indent=1)
+    print("ae reference runs:", [(r["threads"], [round(x, 3) for x in r["test_psnr"]]) for r in runs], "wrote", path)
+
+
 def main():
+    if "--ae" in sys.argv[1:]:
+        return main_ae([a for a in sys.argv[1:] if a != "--ae"])
     out = {}
     build = json.load(open(os.path.join(REPO, "profiles", "r04", "train_spread_build.json")))
     for name in ("dnerf", "dnerf_div"):

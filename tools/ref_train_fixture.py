@@ -43,6 +43,12 @@ RECIPES = {
     # `make nerf-sh` (reference makefile:64-72: --model plain --refl-kind sph-har --sigmoid-kind leaky_relu -lr 1e-3) on the small
     # scene, recorded with --epochs 200
     "nerf_sh": (False, ["--model", "plain", "--refl-kind", "sph-har", "--sigmoid-kind", "leaky_relu", "-lr", "1e-3"]),
+    # `make ae` (reference makefile:380-384: --model ae -lr 1e-3 --no-sched --loss-fns l2, crop 20) on the small scene, with the
+    # 32 + 32 wide latent of the class's own defaults; recorded with --epochs 200 --crop-size 20.  The reference's runner cannot run
+    # `--model ae` as shipped (runner.py:1182-1183 installs a head without the encoded columns, the first forward raises): the
+    # load_model hook below installs the head the class's constructor builds (src/nerf.py:775-778) and everything else is runner.main
+    "ae": (False, ["--model", "ae", "--refl-kind", "view", "--loss-fns", "l2", "-lr", "1e-3", "--no-sched",
+                   "--shape-to-refl-size", "32"]),
     "dnerf": (True, ["--model", "plain", "--refl-kind", "view", "--data-kind", "dnerf", "--dyn-model", "plain",
                      "--spline", "4"]),
     # `make dnerf`'s regularisers (reference makefile:106-114) on the small scene: NR-NeRF offset decay + the FFJORD
@@ -154,6 +160,9 @@ def main():
 
     def load_model(args, light, is_dyn=False):
         m = real_load_model(args, light, is_dyn)
+        if args.model == "ae":  # (see RECIPES["ae"])
+            import src.refl as rrefl
+            m.set_refl(rrefl.load(args, args.refl_kind, args.space_kind, args.encoding_size + m.intermediate_size))
         fill_procedural(m)
         torch.manual_seed(cfg.seed + 1)
         return m
