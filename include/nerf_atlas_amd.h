@@ -426,6 +426,25 @@ int na_hash_encode_backward_input_rows(const float* x, int64_t N, const float* t
                                        int include_input, int lead, float* g_x, void* stream);
 int na_plain_head_rows_backward(const float* g_density, const float* g_rows, int64_t N, int C, float* g_first_out, float* g_pts,
                                 void* stream);
+/* The Fourier encoder as a training node (csrc/fourier_grad.hip; src/utils.py:14-17 under autograd).  1 <= D <= 8, basis [D, F], `scale`
+ * as na_fourier_encode takes it.
+ * na_fourier_rows       rows [N, D + 2F + L] = [x | sin(x B) | cos(x B) | latent]: the init rows cat([p, enc(p), latent]) of a Fourier-encoded
+ *                       SkipConnMLP (src/neural_blocks.py:283-287) by one launch, bit-identical to na_fourier_encode's features.  latent
+ *                       [N, L] at row pitch lat_ld (NULL with L = 0).
+ * na_fourier_encode_backward_input   g_x [N, D] = (lead ? g[:, 0:D] : 0) + sum_f be[:, f] (cos(m_f) g_sin[:, f] - sin(m_f) g_cos[:, f]),
+ *                       be = scale * basis, m = x be: the 2F feature-gradient columns [g_sin | g_cos] are read in place at column col0 of rows of pitch g_ld (the standalone
+ *                       encoder: g_ld = 2F, col0 = 0, lead = 0; init rows: g_ld = D + 2F + L, col0 = D, lead = 1 adds the raw columns'
+ *                       gradient).  No atomics: bitwise reproducible, and the same bits for every pitch and column offset (F a multiple
+ *                       of 4: 16-byte loads at 4-byte alignment; any other F a lane-strided form).
+ * na_fourier_encode_backward_input_saved   the same with sin / cos read back from the forward's rows (`saved`, pitch s_ld, the sine
+ *                       columns at s_col0) instead of recomputed: the alternative tools/fourier_grad_bench.py times against it. */
+int na_fourier_rows(const float* x, int64_t N, int D, const float* basis, int F, float scale, const float* latent, int L, int64_t lat_ld,
+                    float* rows, void* stream);
+int na_fourier_encode_backward_input(const float* x, int64_t N, int D, const float* basis, int F, float scale, const float* g, int g_ld,
+                                     int col0, int lead, float* g_x, void* stream);
+int na_fourier_encode_backward_input_saved(const float* x, int64_t N, int D, const float* basis, int F, float scale, const float* g,
+                                           int g_ld, int col0, int lead, const float* saved, int s_ld, int s_col0, float* g_x,
+                                           void* stream);
 /* The optimiser step of runner.py:448-458 (optim.Adam(params, lr, eps = 1e-7); amsgrad / maximize / weight decay off) for n tensors
  * by ONE launch: per element the operations of torch's foreach Adam in its order and rounding (fma_mask: which of its three
  * multiply-adds ATen contracts -- bit 0 lerp, bit 1 addcmul, bit 2 addcdiv; nerf_atlas_amd/train.py holds the value pinned against

@@ -142,6 +142,11 @@ SIGNATURES = {
                                           c_f32p, C.c_void_p, C.c_void_p]),
     "na_hash_encode_backward": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_void_p]),
     "na_hash_encode_backward_input": (C.c_int, [c_f32p, c_i64, c_f32p, c_f32p, C.c_int, c_f32p, C.c_void_p]),
+    "na_fourier_rows": (C.c_int, [c_f32p, c_i64, C.c_int, c_f32p, C.c_int, C.c_float, c_f32p, C.c_int, c_i64, c_f32p, C.c_void_p]),
+    "na_fourier_encode_backward_input": (C.c_int, [c_f32p, c_i64, C.c_int, c_f32p, C.c_int, C.c_float, c_f32p, C.c_int, C.c_int, C.c_int,
+                                                   c_f32p, C.c_void_p]),
+    "na_fourier_encode_backward_input_saved": (C.c_int, [c_f32p, c_i64, C.c_int, c_f32p, C.c_int, C.c_float, c_f32p, C.c_int, C.c_int,
+                                                         C.c_int, c_f32p, C.c_int, C.c_int, c_f32p, C.c_void_p]),
     "na_hash_encode_jvp": (C.c_int, [c_f32p, c_i64, c_f32p, c_f32p, C.c_int, c_f32p, C.c_void_p]),
     "na_hash_encode_jvp_backward": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_void_p]),
     "na_ffjord_div": (C.c_int, [c_f32p, c_f32p, C.c_int, c_f32p, c_f32p, c_i64, C.c_int, c_f32p, C.c_void_p]),

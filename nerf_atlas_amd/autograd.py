@@ -127,6 +127,44 @@ class HashInitFn(Function):
         return gx, gt, None
 
 
+class FourierEncodeFn(Function):
+    """FourierEncoder.forward (src/neural_blocks.py:52, src/utils.py:14-17) with the gradient w.r.t. the positions (a deformation field
+    in front of a Fourier-encoded canonical model).  The basis is a frozen parameter: no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, basis, scale):
+        ctx.save_for_backward(x, basis)
+        ctx.scale = scale
+        return ops.fourier_encode(x, basis, scale)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, basis = ctx.saved_tensors
+        gx = ops.fourier_encode_backward_input(x, basis, ctx.scale, g.contiguous()) if ctx.needs_input_grad[0] else None
+        return gx, None, None
+
+
+class FourierInitFn(Function):
+    """The init rows cat([p, enc(p), latent]) = [x | sin | cos | latent] of a Fourier-encoded SkipConnMLP (src/neural_blocks.py:283-287)
+    as ONE node and ONE kernel each way (the counterpart of HashInitFn): the backward reads the rows' gradient in place -- positions
+    through the input-gradient kernel, which adds the raw columns' gradient; the latent's gradient is the view of its columns."""
+
+    @staticmethod
+    def forward(ctx, x, basis, scale, latent):
+        ctx.save_for_backward(x, basis)
+        ctx.scale = scale
+        return ops.fourier_rows(x, basis, scale, latent)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, basis = ctx.saved_tensors
+        g = g.contiguous()
+        D, F = basis.shape
+        gx = ops.fourier_encode_backward_input(x, basis, ctx.scale, g, col0=D, lead=True) if ctx.needs_input_grad[0] else None
+        gl = g[:, D + 2 * F:] if ctx.needs_input_grad[3] else None
+        return gx, None, None, gl
+
+
 class PlainHeadFn(Function):
     """PlainNeRF between its two networks in training (src/nerf.py:338-357, src/refl.py:190-207): first_out [N, 1 + C] ->
     (density [N], the View MLP's init rows [N, 5 + C]) by one kernel; the backward writes [g_density | g_rows[:, 5:]] side by side

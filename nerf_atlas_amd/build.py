@@ -35,6 +35,7 @@ UNITS = [
     ("linear_f32.hip", [], ""),
     ("sh_head.hip", [], ""),
     ("ae_front.hip", [], ""),
+    ("fourier_grad.hip", [], ""),
     ("backward.hip", [], ""),
     ("train_gemm.hip", [], ""),
     ("train_bwd.hip", [], ""),

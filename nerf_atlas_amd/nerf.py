@@ -887,4 +887,7 @@ def load_dyn(args, model, device=None):
     if isinstance(model, NeRFAE) and cons is DynamicNeRF:
         raise NotImplementedError("--model ae under --dyn-model plain: training the deformation needs d(FourierEncoder)/d(position), which "
                                   "has no HIP backward (DESIGN.md 8); the reference's own pairing, --dyn-model ae, is broken at HEAD")
+    if isinstance(model, VolSDF) and cons is DynamicNeRF and args.dyn_refl_latent > 0:
+        raise NotImplementedError("--dyn-refl-latent over --model volsdf: VolSDF.from_pts drops the reflectance latent (src/nerf.py:995-1013) "
+                                  "while the head is built for it (runner.py:1182-1183), so the reference's first forward raises a shape error")
     return cons(canonical=model, spline=args.spline, refl_latent=args.dyn_refl_latent)

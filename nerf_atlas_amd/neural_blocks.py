@@ -55,7 +55,9 @@ class FourierEncoder(nn.Module):
 
     def forward(self, x):
         if ag.needs_grad(x):
-            raise NotImplementedError("d(%s)/d(position) has no HIP backward yet (DESIGN.md 9a)" % type(self).__name__)
+            # a deformation field in front of this encoder (D-NeRF over VolSDF's MLP SDF network): the position gradient kernel
+            flat = x.reshape(-1, x.shape[-1]).contiguous()
+            return ag.FourierEncodeFn.apply(flat, self.basis.data, float(self.extra_scale)).reshape(x.shape[:-1] + (self.output_dims(),))
         return ops.fourier_encode(x, self.basis.data, float(self.extra_scale))
 
     def scale_freqs(self, amt: 1 + 1e-5, cap=2):
@@ -323,6 +325,10 @@ class SkipConnMLP(utils.PackedCacheMixin, nn.Module):
             # (pre[2]: the stacked tables of this step, when the caller has built them already)
             tables = pre[2] if pre is not None and len(pre) > 2 else torch.stack([e.weight for e in self.enc.embs])
             init = ag.HashInitFn.apply(flat, tables, self.enc.include_input)
+        elif type(self.enc) is FourierEncoder and flat.is_cuda and os.environ.get("NA_TRAIN_ROWS") != "0":
+            # [p | sin | cos | latent] written by one kernel, the positions' gradient read from the rows' gradient in place
+            # (autograd.FourierInitFn); without a gradient on p or the latent the node only costs its forward
+            init = ag.FourierInitFn.apply(flat, self.enc.basis.data, float(self.enc.extra_scale), lat)
         else:
             init = flat
             if self.enc is not None:

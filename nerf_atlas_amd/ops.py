@@ -189,6 +189,52 @@ def fourier_encode(x: torch.Tensor, basis: torch.Tensor, scale: float = 1.0) -> 
     return out
 
 
+def _fourier_args(x: torch.Tensor, basis: torch.Tensor):
+    x, basis = _f32(x, "x"), _f32(basis, "basis")
+    D, F = basis.shape
+    assert x.dim() == 2 and x.shape[1] == D and 1 <= D <= 8, (x.shape, basis.shape)
+    return x, basis, D, F
+
+
+def fourier_rows(x: torch.Tensor, basis: torch.Tensor, scale: float = 1.0, latent: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[N, D + 2F + L] rows [x | sin(x B) | cos(x B) | latent]: the init rows cat([p, enc(p), latent]) of a Fourier-encoded SkipConnMLP,
+    written by one launch (na_fourier_rows).  latent [N, L]: a column slice of a wider buffer goes down with its row pitch."""
+    lib = _lib.load()
+    x, basis, D, F = _fourier_args(x, basis)
+    N, L, lat_ld = x.shape[0], 0, 0
+    if latent is not None and latent.shape[-1] > 0:
+        latent, lat_ld = _rows(latent, latent.shape[-1], "latent")
+        L = latent.shape[1]
+        assert latent.shape[0] == N, (latent.shape, N)
+    else:
+        latent = None
+    rows = torch.empty(N, D + 2 * F + L, device=x.device, dtype=torch.float32)
+    check(lib.na_fourier_rows(_ptr(x), N, D, _ptr(basis), F, float(scale), _ptr(latent), L, lat_ld, _ptr(rows), _stream()))
+    return rows
+
+
+def fourier_encode_backward_input(x: torch.Tensor, basis: torch.Tensor, scale: float, g: torch.Tensor, col0: int = 0, lead: bool = False,
+                                  saved: Optional[torch.Tensor] = None, saved_col0: int = 0) -> torch.Tensor:
+    """g_x [N, D] of the Fourier features w.r.t. the positions: the 2F columns [g_sin | g_cos] at col0 of the gradient rows g [N, g_ld],
+    read in place; lead: g[:, :D] (the raw columns of init rows) is added.  saved [N, s_ld]: read sin / cos back from these rows (their
+    sine columns at saved_col0) instead of recomputing them -- the alternative tools/fourier_grad_bench.py measures."""
+    lib = _lib.load()
+    x, basis, D, F = _fourier_args(x, basis)
+    g = _f32(g, "g")
+    N = x.shape[0]
+    assert g.dim() == 2 and g.shape[0] == N and g.shape[1] >= col0 + 2 * F and col0 >= (D if lead else 0), (g.shape, col0, lead, D, F)
+    gx = torch.empty_like(x)
+    if saved is None:
+        check(lib.na_fourier_encode_backward_input(_ptr(x), N, D, _ptr(basis), F, float(scale), _ptr(g), g.shape[1], col0, int(lead),
+                                                   _ptr(gx), _stream()))
+    else:
+        saved = _f32(saved, "saved")
+        assert saved.dim() == 2 and saved.shape[0] == N and saved.shape[1] >= saved_col0 + 2 * F, (saved.shape, saved_col0, F)
+        check(lib.na_fourier_encode_backward_input_saved(_ptr(x), N, D, _ptr(basis), F, float(scale), _ptr(g), g.shape[1], col0, int(lead),
+                                                         _ptr(saved), saved.shape[1], saved_col0, _ptr(gx), _stream()))
+    return gx
+
+
 def positional_encode(x: torch.Tensor, bands: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     x, bands = _f32(x, "x"), _f32(bands, "bands")

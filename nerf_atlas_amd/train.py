@@ -224,6 +224,10 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
                          "reference reads model.pts / model.rigid_dp (runner.py:698-699)")
     if args.sdf_eikonal > 0 and not hasattr(model, "sdf"):
         raise ValueError("--sdf-eikonal needs an SDF model (--model volsdf)")
+    if args.sdf_eikonal > 0 and isinstance(model, nerf.DynamicNeRF):
+        raise NotImplementedError("--sdf-eikonal under a dynamic model: the reference's second, dynamic-only eikonal term (runner.py:804-808) "
+                                  "adds the points to the (dp, enc) tuple of DynamicNeRF.time_estim and raises a TypeError in its first "
+                                  "iteration; `make dnerf_volsdf` (makefile:127-133) trains without --sdf-eikonal")
     device = next(model.parameters()).device
     loss_fn = load_loss_fn(args)
     times = None

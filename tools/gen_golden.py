@@ -887,9 +887,129 @@ def g21():
     save("g21_ae_grad", **kw)
 
 
+# ------------------------------------------------------------------ G22 Fourier position gradient + D-NeRF over VolSDF(mlp)
+FG_N = 257        # rows per encoder case (the GPU test takes the leading N of them: 1 .. 257)
+DVS_GRAD_CAP = 1000  # entries kept per gradient tensor and precision (evenly spaced over the flattened tensor; hash tables: over the touched entries)
+DVS_BETA = 0.7
+# (no `--dyn-refl-latent` case: the reference cannot run one over VolSDF -- VolSDF.from_pts drops `refl_latent` (src/nerf.py:995-1013) while
+# runner.py:1182-1183 builds the head for intermediate_size + refl_latent columns: "shape '[-1, 67]' is invalid" in the first forward)
+DVS_CASES = {"view_s4": ("view", 4, 0), "plv_s6": ("pos-linear-view", 6, 0)}
+
+
+def _dvs_build(kind, spline, rl, T):
+    under = rsdf.sdf_kinds["mlp"](intermediate_size=64)
+    sdf = rsdf.SDF(under, rrefl.View(latent_size=64, act="upshifted", out_features=3), isect=None, t_near=0.3, t_far=1.8)
+    canon = rnerf.VolSDF(sdf=sdf, steps=T, t_near=0.3, t_far=1.8, sigmoid_kind="upshifted")
+    m = rnerf.DynamicNeRF(canonical=canon, spline=spline, refl_latent=rl)
+    # runner.py:1182-1183: the head's latent is model.intermediate_size wide (the canonical model's + --dyn-refl-latent)
+    m.set_refl(rrefl.refl_kinds[kind](latent_size=m.intermediate_size, act="upshifted", out_features=3))
+    m.eval()
+    names, shapes = fill_procedural(m)  # (delta_estim.out included: the warp is live)
+    # beta = 0.7 instead of the initial 0.1: the procedural SDF is -2.3 .. -0.3 on these samples, which saturates the Laplace CDF at
+    # beta = 0.1 (d density / d sdf = 0: the position gradient would reach the deformation through the colour alone)
+    canon.scale.fill_(DVS_BETA)
+    return m, names, shapes
+
+
+def g22():
+    """g22_fourier_grad: the reference's FourierEncoder (src/neural_blocks.py:36-55, src/utils.py:14-17) under torch autograd, fp64 AND
+    fp32: gx = d(sum(enc(x) * g))/dx for F in {128, 4, 6} x D in {1, 2, 3} x extra_scale in {1, 1.5} x sigma in {16, 32}, |x| <= 6.  Inputs
+    are shared between the cases (x{D}, g{F}, basis_{sigma}_{D}_{F}); gx64.<case> / gx32.<case> per case.
+    g22_dnerf_volsdf_<case>: DynamicNeRF(VolSDF(sdf.MLP)) (`make dnerf_volsdf`, makefile:127-133) constructed directly, procedural weights
+    (delta_estim.out non-zero), eval mode, 2 views x 4 x 4 rays x 8 steps, fp64 AND fp32: out, alpha, weights, dp, rigidity, the l2 loss
+    against a procedural target and its gradient w.r.t. every parameter (at most DVS_GRAD_CAP entries per tensor, their flat indices,
+    the whole tensor's norm / largest entry and the fp32 run's own deviation from the fp64 run)."""
+    import copy
+    kw = dict(scales=np.array([1.0, 1.5]), sigmas=np.array([16, 32]), Fs=np.array([128, 4, 6]), Ds=np.array([1, 2, 3]))
+    for D in (1, 2, 3):
+        kw[f"x{D}"] = torch.from_numpy(proc_uniform((FG_N, D), 2200 + D, 6.0))
+    for F_ in (128, 4, 6):
+        kw[f"g{F_}"] = torch.from_numpy(proc_uniform((FG_N, 2 * F_), 2210 + F_, 1.0))
+    worst = 0.0
+    for F_ in (128, 4, 6):
+        for D in (1, 2, 3):
+            for sigma in (16, 32):
+                basis = torch.from_numpy(proc_param("basis", (D, F_))) * sigma
+                kw[f"basis_{sigma}_{D}_{F_}"] = basis
+                for scale in (1.0, 1.5):
+                    res = {}
+                    for dt in (torch.float64, torch.float32):
+                        enc = rnb.FourierEncoder(input_dims=D, freqs=F_, sigma=sigma)
+                        enc.basis.copy_(basis)
+                        enc = enc.to(dt)
+                        enc.extra_scale = scale
+                        with torch.enable_grad():
+                            x = kw[f"x{D}"].to(dt).clone().requires_grad_()
+                            (gx,) = torch.autograd.grad(enc(x), x, kw[f"g{F_}"].to(dt))
+                        res[dt] = gx
+                    tag = f"F{F_}_D{D}_s{scale}_sig{sigma}"
+                    kw[f"gx64.{tag}"], kw[f"gx32.{tag}"] = res[torch.float64], res[torch.float32]
+                    worst = max(worst, float((res[torch.float32].double() - res[torch.float64]).abs().max() / res[torch.float64].abs().max()))
+    print(f"g22 fourier_grad: the reference's fp32 gx is at most {worst:.2e} of the largest entry off its fp64 gx")
+    save("g22_fourier_grad", **kw)
+
+    size, T = 4, 8
+    for name, (kind, spline, rl) in DVS_CASES.items():
+        m, names, shapes = _dvs_build(kind, spline, rl, T)
+        c, focal = cam(POSES[:2], size)
+        rays = c.sample_positions(ref_pixel_grid(size, (0, 0, size, size)), size=size)
+        rays = torch.cat([rays[..., :3] * 0.2, torch.nn.functional.normalize(rays[..., 3:], dim=-1)], dim=-1)
+        target = torch.from_numpy(proc_uniform(tuple(rays.shape[:-1]) + (3,), 2201, 0.5)).double() + 0.5
+
+        def run(dt, times):
+            mm = copy.deepcopy(m).to(dt)
+            with torch.enable_grad():
+                for k, p_ in mm.named_parameters():
+                    p_.requires_grad_(p_.is_floating_point() and not k.endswith("basis"))
+                out = mm((rays.to(dt), times.to(dt)))
+                loss = torch.nn.functional.mse_loss(out, target.to(dt))
+                loss.backward()
+            return dict(out=out.detach(), loss=loss.detach(), alpha=mm.canonical.alpha.detach(), weights=mm.canonical.weights.detach(),
+                        dp=mm.dp.detach(), rigidity=mm.rigidity.detach(), grads={k: p_.grad for k, p_ in mm.named_parameters()})
+        # Frame times 0.25 / 0.8, the ones of the g9 D-NeRF fixtures, for every case: no draw is picked.  Where the warped samples land
+        # decides which LeakyReLU pre-activations of the SDF network sit within fp32 rounding of the kink (its later layers hold ~70 of
+        # 65 536 within 2e-5 each in the fp64 run) and which samples sit on a hash-cell face, and one flip moves a gradient summed over
+        # 256 samples by 1 / 256 and more, whatever computes it in fp32.  The reference's OWN fp32 autograd against its fp64 run, the
+        # worst tensor in units of its largest entry, goes into the fixture as `own_linf` (view_s4: 3.2e-5; plv_s6: 5.2e-2, it flips):
+        # the ruler tests/test_gpu_fourier_grad.py derives its fp32 bar from, on exactly the inputs it runs.
+        times = torch.tensor([0.25, 0.8])
+        r64, r32 = run(torch.float64, times), run(torch.float32, times)
+        opac = r64["weights"][:-1].sum(0)
+        frac = float(((opac > 0.05) & (opac < 0.95)).float().mean())
+        print(f"g22 {name}: opacity before the last sample {float(opac.min()):.2f}..{float(opac.max()):.2f} ({frac:.0%} of rays in 0.05..0.95), "
+              f"|dp| up to {float(r64['dp'].abs().max()):.3f}; fp32 vs fp64: out {float((r32['out'].double() - r64['out']).abs().max()):.2e} "
+              f"loss {abs(float(r32['loss']) - float(r64['loss'])):.2e}")
+        assert frac >= 0.5, f"{name}: degenerate case"
+        gnames = [k for k, g in r64["grads"].items() if g is not None]
+        missing = [k for k, g in r64["grads"].items() if g is None]
+        kw = dict(rays=rays, times=times, steps=T, near=0.3, far=1.8, spline=spline, n_rl=rl, refl_kind=kind, target_seed=2201,
+                  scale=DVS_BETA, grad_names=np.array(gnames), no_grad_names=np.array(missing), **spec(names, shapes))
+        for k in ("out", "alpha", "weights", "dp", "rigidity", "loss"):
+            kw[k], kw[k + "64"] = r32[k], r64[k]
+        own_linf = own_l2 = 0.0
+        for k in gnames:
+            g64, g32 = r64["grads"][k].reshape(-1), r32["grads"][k].reshape(-1)
+            pool = torch.nonzero(g64).reshape(-1).numpy() if "embs" in k else np.arange(g64.numel())
+            idx = pool[::max(1, -(-len(pool) // DVS_GRAD_CAP))].astype(np.int64)
+            kw[f"idx.{k}"] = idx.astype(np.int32)
+            kw[f"grad64.{k}"] = g64[idx]
+            kw[f"grad32.{k}"] = g32[idx]
+            kw[f"norm64.{k}"] = g64.norm()
+            kw[f"max64.{k}"] = g64.abs().max()
+            linf = float((g32.double() - g64).abs().max() / g64.abs().max().clamp_min(1e-300))
+            l2 = float((g32.double() - g64).norm() / g64.norm().clamp_min(1e-300))
+            kw[f"own_linf.{k}"], kw[f"own_l2.{k}"] = linf, l2
+            if float(g64.abs().max()) > 0:
+                own_linf, own_l2 = max(own_linf, linf), max(own_l2, l2)
+        kw["own_linf"], kw["own_l2"] = own_linf, own_l2
+        print(f"g22 {name}: loss {float(r64['loss']):.6f}, {len(gnames)} gradients (none: {missing}); the reference's fp32 gradients are at most "
+              f"{own_linf:.2e} (of the largest entry) / {own_l2:.2e} (relative L2) per tensor off its fp64 gradients")
+        save(f"g22_dnerf_volsdf_{name}", **kw)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22"]
     for g in which:
         globals()[g]()
     with open(os.path.join(OUT, "PROVENANCE.txt"), "w") as f:

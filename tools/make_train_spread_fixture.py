@@ -13,6 +13,11 @@ tests/test_gpu_train.py derives its end-point bars (a bar must come 
 tests/golden/train_spread_ae.json: the same for the `ae` recipe (reference runs only), a file of its own:
 
     python tools/make_train_spread_fixture.py --ae /tmp/ae_threads_*.json
+
+tests/golden/train_spread_dnerf_volsdf.json: the same for the short `dnerf_volsdf` recipe (its runs agree over the first ten iterations
+and decorrelate before the thirtieth):
+
+    python tools/make_train_spread_fixture.py --recipe dnerf_volsdf /tmp/dvs_threads_*.json
 """
 import json
 import os
@@ -38,16 +43,20 @@ def reference_runs(name, paths):
     return runs
 
 
-def main_ae(paths):
-    runs = reference_runs("ae", paths)
-    path = os.path.join(REPO, "tests", "golden", "train_spread_ae.json")
-    json.dump({"ae": {"reference_runs": runs}}, open(path, "w"), indent=1)
-    print("ae reference runs:", [(r["threads"], [round(x, 3) for x in r["test_psnr"]]) for r in runs], "wrote", path)
+def main_recipe(name, paths):
+    """a file of its own for one recipe: reference runs only"""
+    runs = reference_runs(name, paths)
+    path = os.path.join(REPO, "tests", "golden", f"train_spread_{name}.json")
+    json.dump({name: {"reference_runs": runs}}, open(path, "w"), indent=1)
+    print(name, "reference runs:", [(r["threads"], [round(x, 3) for x in r["test_psnr"]]) for r in runs], "wrote", path)
 
 
 def main():
     if "--ae" in sys.argv[1:]:
-        return main_ae([a for a in sys.argv[1:] if a != "--ae"])
+        return main_recipe("ae", [a for a in sys.argv[1:] if a != "--ae"])
+    if "--recipe" in sys.argv[1:]:
+        i = sys.argv.index("--recipe")
+        return main_recipe(sys.argv[i + 1], sys.argv[1:i] + sys.argv[i + 2:])
     out = {}
     build = json.load(open(os.path.join(REPO, "profiles", "r04", "train_spread_build.json")))
     for name in ("dnerf", "dnerf_div"):

@@ -73,6 +73,13 @@ RECIPES = {
     # raises at runner.py:807, `pts + dp` with dp the (dp, enc) tuple of DynamicNeRF.time_estim.)
     "volsdf_mlp": (False, ["--model", "volsdf", "--sdf-kind", "mlp", "--refl-kind", "view", "--near", "2", "--far", "6",
                            "--sdf-eikonal", "1e-5", "--sigmoid-kind", "upshifted", "-lr", "3e-4"]),
+    # `make dnerf_volsdf` (makefile:127-133) without its --sdf-eikonal (see above: that term raises in the reference): D-NeRF with a
+    # six-point spline over VolSDF's Fourier-encoded MLP SDF network and the PosLinearView head -- the deformation network learns
+    # through d(FourierEncoder)/d(position).  Recorded short, on the smallest scene, for a test of a few seconds:
+    # --epochs 30 --size 16 --crop-size 8 --steps 8
+    "dnerf_volsdf": (True, ["--model", "volsdf", "--sdf-kind", "mlp", "--data-kind", "dnerf", "--dyn-model", "plain", "--spline", "6",
+                            "--refl-kind", "pos-linear-view", "--sigmoid-kind", "upshifted", "--near", "2", "--far", "6", "-lr", "3e-4",
+                            "--loss-fns", "l2"]),
     # the SDF regularisers of the reference's VolSDF recipes (makefile:85-95): eikonal + normal smoothing by the unisurf
     # epsilon perturbation with a random radius (one random.random() and two randn draws per iteration in the RNG streams)
     "volsdf_smooth": (False, ["--model", "volsdf", "--sdf-kind", "siren", "--refl-kind", "view", "--near", "2", "--far", "6",
