@@ -599,7 +599,7 @@ __global__ void composite_backward_kernel(const float* __restrict__ density, con
         const int t = t0 + u;
         if (t < T) {
           const float d = dv[u];
-          const float sigma = density_kind == NA_DENSITY_SOFTPLUS_M1 ? softplusf_(d - 1.0f) : fmaxf(d, 0.f);
+          const float sigma = density_kind == NA_DENSITY_SOFTPLUS_M1 ? softplusf_(d - 1.0f) : (d < 0.f ? 0.f : d);
           float dist = t < T - 1 ? fmaxf(ts[t + 1] - ts[t], 1e-5f) : 1e10f;
           dist *= nrm;
           const float a = 1.0f - expf(-sigma * dist);
@@ -625,7 +625,7 @@ __global__ void composite_backward_kernel(const float* __restrict__ density, con
         const int t = t1 - u;
         if (t >= 0) {
           const float d = dv[u];
-          const float sigma = density_kind == NA_DENSITY_SOFTPLUS_M1 ? softplusf_(d - 1.0f) : fmaxf(d, 0.f);
+          const float sigma = density_kind == NA_DENSITY_SOFTPLUS_M1 ? softplusf_(d - 1.0f) : (d < 0.f ? 0.f : d);
           float dist = t < T - 1 ? fmaxf(ts[t + 1] - ts[t], 1e-5f) : 1e10f;
           dist *= nrm;
           const float e = expf(-sigma * dist);
@@ -692,7 +692,7 @@ __global__ __launch_bounds__(512) void composite_backward_seg_kernel(const float
   for (int u = 0; u < CB_SEG; ++u) {
     const int t = t_lo + u;
     const float d = dv[u];
-    const float sigma = density_kind == NA_DENSITY_SOFTPLUS_M1 ? softplusf_(d - 1.0f) : fmaxf(d, 0.f);
+    const float sigma = density_kind == NA_DENSITY_SOFTPLUS_M1 ? softplusf_(d - 1.0f) : (d < 0.f ? 0.f : d);
     float di = t < T - 1 ? fmaxf(ts[t + 1] - ts[t < T ? t : T - 1], 1e-5f) : 1e10f;
     di *= nrm;
     dist[u] = di;

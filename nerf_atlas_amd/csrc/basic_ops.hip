@@ -482,7 +482,7 @@ __global__ void composite_kernel(const float* __restrict__ density, const float*
           // hardware transcendentals (common.h): with libm's log1pf(expf()) / expf() this kernel was ALU-bound at ~300
           // instructions per sample.  One thread per (ray, 32-step segment) with the segments meeting in LDS -- 4x the
           // threads -- measured slower.
-          float sigma = density_kind == NA_DENSITY_SOFTPLUS_M1 ? fast_softplus(d - 1.0f) : fmaxf(d, 0.f);
+          float sigma = density_kind == NA_DENSITY_SOFTPLUS_M1 ? fast_softplus(d - 1.0f) : (d < 0.f ? 0.f : d);  // (a select: fmaxf(NaN, 0) = 0)
           float dist = t < T - 1 ? fmaxf(ts[t + 1] - ts[t], 1e-5f) : 1e10f;
           dist = dist * nrm;
           float a = 1.0f - fast_exp(-sigma * dist);
@@ -530,7 +530,7 @@ __device__ __forceinline__ float laplace_density_of(float sdf, float sc, float i
   const float scaled = (-sdf) / sc;
   // (fast_exp: v_exp_f32 with the product's rounding error recovered, 2e-7 relative -- libm's expf made this elementwise
   // kernel ALU-bound at 30 % of the HBM rate)
-  const float cdf = scaled <= 0.f ? fast_exp(fminf(scaled, 0.f)) / 2.f : 1.f - fast_exp(-fmaxf(scaled, 0.f)) / 2.f;
+  const float cdf = scaled <= 0.f ? fast_exp(scaled) / 2.f : 1.f - fast_exp(-scaled) / 2.f;  // (no fminf / fmaxf: they drop a NaN distance)
   return inv * cdf;
 }
 __global__ void laplace_density_kernel(const float* __restrict__ sdf, int64_t N, const float* __restrict__ beta,

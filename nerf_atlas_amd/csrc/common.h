@@ -74,12 +74,16 @@ __device__ __forceinline__ float softplusf_(float v) { return v > 20.f ? v : log
 // ---- compositing arithmetic on the hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32, 1 ulp each).  The
 // libm calls they replace made the compositing of a block the longest piece of the exposed EP phase (~5 k cycles).
 // exp(x): x log2(e) with the product's rounding error recovered by an fma (2e-7 relative for |x| <= 88)
+// Non-finite arguments behave like expf: NaN stays NaN (a clamp alone drops it -- fminf(NaN, 88) = 88 turned a NaN density into a
+// finite, nearly opaque sample and 1 - exp(NaN) into -1.6e38) and -inf gives 0 (unclamped, fma(-inf, c, +inf) = NaN).  Every finite
+// x keeps its bits: exp(-104) is below half the smallest denormal, the clamp only meets arguments whose result is 0 anyway.
 __device__ __forceinline__ float fast_exp(float x) {
-  x = fminf(x, 88.f);
-  const float t = x * 1.4426950408889634f;
-  const float r = fmaf(x, 1.4426950408889634f, -t) + x * 1.925963033500235e-8f;
+  const float xc = __builtin_amdgcn_fmed3f(x, -104.f, 88.f);
+  const float t = xc * 1.4426950408889634f;
+  const float r = fmaf(xc, 1.4426950408889634f, -t) + xc * 1.925963033500235e-8f;
   const float e = __builtin_amdgcn_exp2f(t);
-  return fmaf(e, r * 0.6931471805599453f, e);
+  const float y = fmaf(e, r * 0.6931471805599453f, e);
+  return x != x ? x : y;
 }
 __device__ __forceinline__ float fast_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + fast_exp(-v)); }
 // log1p(exp(v)) with the RELATIVE accuracy the 1e10-long last interval needs (src/nerf.py:60-68: sigma * 1e10): series

@@ -248,7 +248,9 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
     const float cg = fast_sigmoid_kind(oc[1], sgk);
     const float cb = fast_sigmoid_kind(oc[2], sgk);
     // (MODEL 2: `density` is VolSDF's Laplace density, used as it is: src/nerf.py:1004-1006, softplus = False)
-    const float sigma = (MODEL == 2 || MODEL == 3) ? fmaxf(density, 0.f) : fast_softplus(density - 1.0f);
+    // (relu as a select, not fmaxf: fmaxf(NaN, 0) = 0 made a NaN density -- fast_softplus(NaN) of a NaN logit in na_render_view_ls, the
+    // Laplace density of a NaN distance -- an empty sample)
+    const float sigma = (MODEL == 2 || MODEL == 3) ? (density < 0.f ? 0.f : density) : fast_softplus(density - 1.0f);
     const float alpha = q.t_ok ? 1.0f - fast_exp(-sigma * q.dist) : 0.f;
     const float f = (1.0f - alpha) + 1e-10f;
     // exclusive product scan over the 32 steps of the block: shift by one lane (lane 0 of each half: 1), then scan

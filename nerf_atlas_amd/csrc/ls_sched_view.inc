@@ -30,7 +30,7 @@
         } else {  // Laplace density of this pass's sample (src/utils.py:50-58, src/nerf.py:1000-1003), composited one pass later
           const float sc = a.beta[0];
           const float scaled = (-sdfv) / sc;
-          const float cdf = scaled <= 0.f ? fast_exp(fminf(scaled, 0.f)) * 0.5f : 1.f - fast_exp(-fmaxf(scaled, 0.f)) * 0.5f;
+          const float cdf = scaled <= 0.f ? fast_exp(scaled) * 0.5f : 1.f - fast_exp(-scaled) * 0.5f;  // (no fminf / fmaxf: they drop a NaN distance)
           density = (1.0f / sc) * cdf;
         }
         if constexpr (PREC == NA_PREC_F16X) {

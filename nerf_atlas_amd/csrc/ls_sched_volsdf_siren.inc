@@ -113,7 +113,7 @@
           const float sdfv = ((const float*)hb)[blk * 32 + ln];
           const float sc = a.beta[0];
           const float scaled = (-sdfv) / sc;
-          const float cdf = scaled <= 0.f ? fast_exp(fminf(scaled, 0.f)) * 0.5f : 1.f - fast_exp(-fmaxf(scaled, 0.f)) * 0.5f;
+          const float cdf = scaled <= 0.f ? fast_exp(scaled) * 0.5f : 1.f - fast_exp(-scaled) * 0.5f;  // (no fminf / fmaxf: they drop a NaN distance)
           density = (1.0f / sc) * cdf;
         }
         {
@@ -237,7 +237,7 @@
         const float sdfv = ((const float*)hb)[blk * 32 + ln];
         const float sc = a.beta[0];
         const float scaled = (-sdfv) / sc;
-        const float cdf = scaled <= 0.f ? fast_exp(fminf(scaled, 0.f)) * 0.5f : 1.f - fast_exp(-fmaxf(scaled, 0.f)) * 0.5f;
+        const float cdf = scaled <= 0.f ? fast_exp(scaled) * 0.5f : 1.f - fast_exp(-scaled) * 0.5f;  // (no fminf / fmaxf: they drop a NaN distance)
         density = (1.0f / sc) * cdf;
       }
       m_hidden<PREC, 0, 4, 1, 0, false, PPP>(acc, ring, cur, wrs, wvoff, hb, ib, lane, geo_load, geo_make);  // view.init

@@ -79,7 +79,14 @@ __device__ __forceinline__ float act_apply(float v) {
   // leaky_relu(v) = max(v, 0.01 v) = median(v, 0.01 v, +big): v_med3_f32 needs no canonicalising v_max
   // (f16 operands: the upper bound doubles as the clamp to the largest finite half, so a large pre-activation becomes 65504
   // instead of +inf -> NaN downstream; the negative side is safe down to v = -6.5e6)
-  if constexpr (ACT == NA_ACT_LEAKY_RELU) return __builtin_amdgcn_fmed3f(v, v * 0.01f, kHalfElem<PREC> ? 65504.0f : 3.0e38f);
+  // A NaN pre-activation stays NaN: the median alone returns its finite bound for it, which turned a NaN sample position into a
+  // finite, opaque sample.  (NA_PREC_F16X keeps the plain median: there the bound 65504 is what its range guard looks for, NaN
+  // included -- ls_engine.h -- and a NaN would slip past the block maximum.)
+  if constexpr (ACT == NA_ACT_LEAKY_RELU) {
+    const float m = __builtin_amdgcn_fmed3f(v, v * 0.01f, kHalfElem<PREC> ? 65504.0f : 3.0e38f);
+    if constexpr (PREC == NA_PREC_F16X) return m;
+    else return v != v ? v : m;
+  }
   // (sine: the exact reduction for bf16x3 only; f16x takes the three-instruction sine (v_mul, v_fract, v_sin) of the fast modes,
   // measured the same L-inf as the exact reduction (1.6e-5 golden / 9e-6 bench weights), 128 fewer VALU per sine epilogue)
   else if constexpr (ACT == NA_ACT_SIN) return PREC == NA_PREC_BF16X3 ? sin_hw2(v) : sin_hw(v);
@@ -95,7 +102,8 @@ __device__ __forceinline__ float act_apply(float v) {
 template <int PREC, bool CLAMP = true>
 __device__ __forceinline__ __bf16 to_elem(float v) {
   if constexpr (kHalfElem<PREC>) {
-    if constexpr (CLAMP) v = __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f);
+    // (NA_PREC_F16: only FINITE values saturate -- the median maps NaN to -65504 and would hide an Inf; NA_PREC_F16X leaves both to its guard)
+    if constexpr (CLAMP) v = (PREC == NA_PREC_F16X || __builtin_fabsf(v) < __builtin_inff()) ? __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f) : v;
     return __builtin_bit_cast(__bf16, (_Float16)v);
   } else return (__bf16)v;
 }
