@@ -113,8 +113,9 @@ __device__ __forceinline__ float apply_sigmoid_kind(float v, int kind) {
   }
 }
 
-// sin with a 2-term Cody-Waite reduction by pi and a degree-9 odd polynomial (least-squares on
-// Chebyshev nodes of [-pi/2,pi/2]): max |err| 1.6e-7 for |x| <= 3e3 (checked against fp64).
+// sin with a three-constant Cody-Waite reduction by pi and a degree-9 odd polynomial (least-squares on
+// Chebyshev nodes of [-pi/2,pi/2]): max |err| 1.6e-7 for |x| <= 3e3 (tests/encoder_ref.py restates it in fp32 and measures it
+// against fp64; tests/test_gpu_encoders.py holds the kernels to 1.25 x that).  Without the third constant: 1.4e-4 at 3e3.
 __device__ __forceinline__ float sin_cw(float x) {
   float q = rintf(x * 0.318309886183790672f);
   float r = fmaf(q, -3.140625f, x);
@@ -183,7 +184,7 @@ __device__ __forceinline__ float mip_radius(const float* rays, int H, int W, int
 // drops out exactly and the sine sees an angle in [-pi, pi] for every degree (the reference's fp32 sin(y) reduces
 // y = 2^15 mean the same way inside libm).  The cosine half is sin(fl(y + pi/2)) like the reference: the rounded sum
 // differs from y by an exactly representable delta, which is added to the reduced angle.  damp = exp(-cov 4^k / 2)
-// through v_exp_f32.  Max deviation from libm's sinf / expf: 6e-7 (angle) and 2 ulp (damp).  FAST (bf16 operands
+// through v_exp_f32.  Max deviation from fp64: 6e-7 (angle; 3.8e-7 measured) and 2 ulp (damp).  FAST (bf16 operands
 // downstream): hardware v_sin_f32 on the revolution count instead of the polynomial.
 template <bool FAST = false>
 __device__ __forceinline__ float mip_feature(float m0, float m1, float m2, float c0, float c1, float c2, int f, int nd,
@@ -237,8 +238,9 @@ __device__ __forceinline__ uint32_t hash_index(int lx, int ly, int lz) {
   return (((uint32_t)lx) ^ ((uint32_t)ly * 2654435761u) ^ ((uint32_t)lz * 805459861u)) & 0xFFFFu;
 }
 
-// sin / cos of one Fourier feature (src/utils.py:14-17; arguments reach 1e3): Cody-Waite reduction + polynomials (1.6e-7 / 5e-7 for
-// |m| <= 3e3, the same pair the fused prologues use in the parity mode); larger arguments (a basis far beyond the reference's
+// sin / cos of one Fourier feature (src/utils.py:14-17; arguments reach 1e3): Cody-Waite reduction + polynomials (1.6e-7 / 5.9e-7 for
+// |m| <= 3e3 -- the cosine's degree-10 Taylor polynomial truncates at (pi/2)^12 / 12! = 4.7e-7; measured on the MI355X on
+// argument-exact inputs: 1.5e-7 / 5.8e-7 --, the same pair the fused prologues use in the parity mode); larger arguments (a basis far beyond the reference's
 // sigma 16 / 32) take libm's large-argument path.  Shared by na_fourier_encode and na_sh_view_terms: bit-identical features.
 __device__ __forceinline__ void fourier_sincos(float m, float& sn, float& cs) {
   if (fabsf(m) <= 3.0e3f) sincos_cw(m, sn, cs);
@@ -264,14 +266,18 @@ __device__ __forceinline__ float sigmoid_kind_grad(float v, int kind) {
   }
 }
 
-// dir_to_elev_azim (src/utils.py:247-254)
+// dir_to_elev_azim (src/utils.py:247-254).  The clamps are comparisons, not fmaxf / fminf: those return their other operand for a
+// NaN, which turned a NaN norm into 1e-12, the NaN component into -lim and the finite ones into +-lim -- (NaN, y, z) came out as the
+// finite elevation 1.4e-3 and azimuth 3 pi / 4, an Inf component as azimuth pi.  torch's clamp keeps NaN, so a non-finite direction
+// stays loud here too (every finite input keeps its bits).
+__device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ void elev_azim(float dx, float dy, float dz, float& elev, float& azim) {
   const float lim = 1.f - 1e-6f;
   float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
-  nrm = fmaxf(nrm, 1e-12f);
-  float x = fminf(fmaxf(dx / nrm, -lim), lim);
-  float y = fminf(fmaxf(dy / nrm, -lim), lim);
-  float z = fminf(fmaxf(dz / nrm, -lim), lim);
+  nrm = nrm < 1e-12f ? 1e-12f : nrm;
+  float x = clamp_keep_nan(dx / nrm, -lim, lim);
+  float y = clamp_keep_nan(dy / nrm, -lim, lim);
+  float z = clamp_keep_nan(dz / nrm, -lim, lim);
   elev = acosf(z);
   azim = atan2f(y, x);
 }
