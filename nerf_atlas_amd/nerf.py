@@ -198,12 +198,7 @@ class TinyNeRF(CommonNeRF):
     def packed_ls(self, precision: str):
         """Weight stream of the layer-synchronous renderer (cached, re-packed when any parameter changed)."""
         lin = self.estim._linears()
-        stamp = utils.pack_stamp(lin)
-        cache = self.__dict__.setdefault("_packed_ls", {})
-        hit = cache.get(precision)
-        if hit is None or stamp is None or hit[0] != stamp:
-            cache[precision] = (stamp, ops.render_tiny_ls_pack(precision, [l.weight.data for l in lin], [l.bias.data for l in lin]))
-        return cache[precision][1]
+        return utils.packed_stream(self, "_packed_ls", precision, lin, lambda: ops.render_tiny_ls_pack(precision, *utils.linears_wb(lin)))
 
     @_f16x_policy
     def forward(self, rays, want_weights: bool = True):
@@ -265,19 +260,13 @@ class PlainNeRF(CommonNeRF):
     def packed_head_ls(self, kind: str, precision: str, n_rl: int = 0):
         r = self.refl
         heads = r.mlp._linears() if kind == "pos" else r.pos._linears() + r.view._linears()
-        lin = self.first._linears() + heads
-        stamp = utils.pack_stamp(lin)
-        cache = self.__dict__.setdefault("_packed_head_ls", {})
-        key = (kind, precision, n_rl)
-        hit = cache.get(key)
-        if hit is None or stamp is None or hit[0] != stamp:
-            wb = lambda ls: ([l.weight.data for l in ls], [l.bias.data for l in ls])
+        first = self.first._linears()
+
+        def pack():
             if kind == "pos":
-                packed = ops.render_plain_pos_ls_pack(precision, wb(self.first._linears()), wb(heads))
-            else:
-                packed = ops.render_plain_plv_ls_pack(precision, wb(self.first._linears()), wb(heads), n_rl)
-            cache[key] = (stamp, packed)
-        return cache[key][1]
+                return ops.render_plain_pos_ls_pack(precision, utils.linears_wb(first), utils.linears_wb(heads))
+            return ops.render_plain_plv_ls_pack(precision, utils.linears_wb(first), utils.linears_wb(heads), n_rl)
+        return utils.packed_stream(self, "_packed_head_ls", (kind, precision, n_rl), first + heads, pack)
 
     def _render_head(self, kind, rays, ts, want_weights, pts=None, refl_latent=None):
         want_weights = want_weights or self.bg == "random"
@@ -298,26 +287,16 @@ class PlainNeRF(CommonNeRF):
                 and self.total_latent_size() == 96 and not self.training and not wants_grad)
 
     def packed_mip_ls(self, precision: str):
-        lin = self.first._linears() + self.refl.mlp._linears()
-        stamp = utils.pack_stamp(lin)
-        cache = self.__dict__.setdefault("_packed_mip_ls", {})
-        hit = cache.get(precision)
-        if hit is None or stamp is None or hit[0] != stamp:
-            wb = lambda m: ([l.weight.data for l in m._linears()], [l.bias.data for l in m._linears()])
-            cache[precision] = (stamp, ops.render_plain_mip_ls_pack(precision, wb(self.first), wb(self.refl.mlp)))
-        return cache[precision][1]
+        first, view = self.first._linears(), self.refl.mlp._linears()
+        return utils.packed_stream(self, "_packed_mip_ls", precision, first + view,
+                                   lambda: ops.render_plain_mip_ls_pack(precision, utils.linears_wb(first), utils.linears_wb(view)))
 
     def packed_ls(self, precision: str):
         """Weight stream of the layer-synchronous renderer (both MLPs in one buffer; cached, re-packed when any
         parameter changed)."""
-        lin = self.first._linears() + self.refl.mlp._linears()
-        stamp = utils.pack_stamp(lin)
-        cache = self.__dict__.setdefault("_packed_ls", {})
-        hit = cache.get(precision)
-        if hit is None or stamp is None or hit[0] != stamp:
-            wb = lambda m: ([l.weight.data for l in m._linears()], [l.bias.data for l in m._linears()])
-            cache[precision] = (stamp, ops.render_ls_pack(precision, wb(self.first), wb(self.refl.mlp)))
-        return cache[precision][1]
+        first, view = self.first._linears(), self.refl.mlp._linears()
+        return utils.packed_stream(self, "_packed_ls", precision, first + view,
+                                   lambda: ops.render_ls_pack(precision, utils.linears_wb(first), utils.linears_wb(view)))
 
     def _render_fused(self, rays, ts, want_weights, pts=None):
         """sample -> hash -> first -> elaz -> View -> sigmoid -> composite in ONE kernel (config.engine picks the
@@ -498,24 +477,14 @@ class NeRFAE(CommonNeRF):
                 and r.latent_size == 64 and r.out_features == 3 and getattr(r, "act_kind", None) in ops.SIGMOID)
 
     def packed_front(self, precision: str):
-        lin = self.encode._linears() + self.density_tform._linears()
-        stamp = utils.pack_stamp(lin)
-        cache = self.__dict__.setdefault("_packed_front", {})
-        hit = cache.get(precision)
-        if hit is None or stamp is None or hit[0] != stamp:
-            wb = lambda m: ([l.weight.data for l in m._linears()], [l.bias.data for l in m._linears()])
-            cache[precision] = (stamp, ops.ae_front_pack(precision, self.encoding_size, self.intermediate_size, wb(self.encode),
-                                                         wb(self.density_tform)))
-        return cache[precision][1]
+        enc, den = self.encode._linears(), self.density_tform._linears()
+        return utils.packed_stream(self, "_packed_front", precision, enc + den,
+                                   lambda: ops.ae_front_pack(precision, self.encoding_size, self.intermediate_size, utils.linears_wb(enc),
+                                                             utils.linears_wb(den)))
 
     def packed_view_ls(self, precision: str):
         lin = self.refl.mlp._linears()
-        stamp = utils.pack_stamp(lin)
-        cache = self.__dict__.setdefault("_packed_view_ls", {})
-        hit = cache.get(precision)
-        if hit is None or stamp is None or hit[0] != stamp:
-            cache[precision] = (stamp, ops.render_view_ls_pack(precision, [l.weight.data for l in lin], [l.bias.data for l in lin]))
-        return cache[precision][1]
+        return utils.packed_stream(self, "_packed_view_ls", precision, lin, lambda: ops.render_view_ls_pack(precision, *utils.linears_wb(lin)))
 
     def _basis(self):
         enc = self.encode.enc
@@ -623,31 +592,16 @@ class VolSDF(CommonNeRF):
 
     def packed_fourier_sdf_ls(self, precision: str):
         lin = self.sdf.underlying.mlp._linears()
-        stamp = utils.pack_stamp(lin)
-        cache = self.__dict__.setdefault("_packed_fourier_ls", {})
-        hit = cache.get(precision)
-        if hit is None or stamp is None or hit[0] != stamp:
-            cache[precision] = (stamp, ops.mlp_fourier_ls_pack(precision, [l.weight.data for l in lin], [l.bias.data for l in lin]))
-        return cache[precision][1]
+        return utils.packed_stream(self, "_packed_fourier_ls", precision, lin, lambda: ops.mlp_fourier_ls_pack(precision, *utils.linears_wb(lin)))
 
     def packed_view_ls(self, precision: str):
         lin = self.sdf.refl.mlp._linears()
-        stamp = utils.pack_stamp(lin)
-        cache = self.__dict__.setdefault("_packed_view_ls", {})
-        hit = cache.get(precision)
-        if hit is None or stamp is None or hit[0] != stamp:
-            cache[precision] = (stamp, ops.render_view_ls_pack(precision, [l.weight.data for l in lin], [l.bias.data for l in lin]))
-        return cache[precision][1]
+        return utils.packed_stream(self, "_packed_view_ls", precision, lin, lambda: ops.render_view_ls_pack(precision, *utils.linears_wb(lin)))
 
     def packed_siren_ls(self, precision: str):
-        lin = self.sdf.underlying.siren._linears() + self.sdf.refl.mlp._linears()
-        stamp = utils.pack_stamp(lin)
-        cache = self.__dict__.setdefault("_packed_siren_ls", {})
-        hit = cache.get(precision)
-        if hit is None or stamp is None or hit[0] != stamp:
-            wb = lambda m: ([l.weight.data for l in m._linears()], [l.bias.data for l in m._linears()])
-            cache[precision] = (stamp, ops.render_volsdf_siren_ls_pack(precision, wb(self.sdf.underlying.siren), wb(self.sdf.refl.mlp)))
-        return cache[precision][1]
+        siren, view = self.sdf.underlying.siren._linears(), self.sdf.refl.mlp._linears()
+        return utils.packed_stream(self, "_packed_siren_ls", precision, siren + view,
+                                   lambda: ops.render_volsdf_siren_ls_pack(precision, utils.linears_wb(siren), utils.linears_wb(view)))
 
     def from_pts(self, pts, ts, r_o, r_d, refl_latent=None, rays=None):
         if rays is None: rays = torch.cat([r_o, r_d], dim=-1).contiguous()
@@ -792,12 +746,7 @@ class DynamicNeRF(utils.PackedCacheMixin, nn.Module):
 
     def packed_deformation_ls(self, precision: str):
         lin = self.delta_estim._linears()
-        stamp = utils.pack_stamp(lin)
-        cache = self.__dict__.setdefault("_packed_ls", {})
-        hit = cache.get(precision)
-        if hit is None or stamp is None or hit[0] != stamp:
-            cache[precision] = (stamp, ops.mlp_hash_ls_pack(precision, [l.weight.data for l in lin], [l.bias.data for l in lin]))
-        return cache[precision][1]
+        return utils.packed_stream(self, "_packed_ls", precision, lin, lambda: ops.mlp_hash_ls_pack(precision, *utils.linears_wb(lin)))
 
     @_f16x_policy
     def forward(self, rays_t):

@@ -225,13 +225,7 @@ class SkipConnMLP(utils.PackedCacheMixin, nn.Module):
         if desc is None or ops.mlp_packed_bytes(desc, precision) == 0:
             return None, None
         lin = self._linears()
-        stamp = utils.pack_stamp(lin)
-        key = (precision, layout)
-        hit = self._packed.get(key)
-        if hit is None or stamp is None or hit[0] != stamp:
-            buf = ops.mlp_pack(desc, precision, [l.weight.data for l in lin], [l.bias.data for l in lin])
-            self._packed[key] = (stamp, buf)
-        return desc, self._packed[key][1]
+        return desc, utils.packed_stream(self, "_packed", (precision, layout), lin, lambda: ops.mlp_pack(desc, precision, *utils.linears_wb(lin)))
 
     def _mip_prologue_shape(self):
         """the shapes csrc/mlp_fwd_inst.hip instantiates with the IPE prologue: PlainNeRF.first (hash, 38 + 96 inputs)

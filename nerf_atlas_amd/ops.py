@@ -1062,24 +1062,73 @@ def render_plain_view(rays: torch.Tensor, ts: torch.Tensor, hash_tables: torch.T
     return out, alpha, weights
 
 
+# ---- the layer-synchronous engine (csrc/render_ls.hip): what its pack and render wrappers share
+# Linear shapes [out, in] ({init, layers.*, out}) of the MLPs the schedules are built for
+_H = [(256, 256)]
+_LS_SHAPES = {
+    "first": [(256, 38), (256, 294)] + 3 * _H + [(65, 256)],
+    "view": [(256, 69), (256, 325)] + 3 * _H + [(3, 256)],
+    "mip_first": [(256, 134), (256, 390)] + 3 * _H + [(65, 256)],
+    "mip_view": [(256, 165), (256, 421)] + 3 * _H + [(3, 256)],
+    "pos": [(256, 102), (256, 358)] + 2 * _H + [(256, 358)] + _H + [(3, 256)],
+    "tiny": [(256, 3), (256, 259)] + 2 * _H + [(256, 259)] + 2 * _H + [(4, 256)],
+    "siren": [(256, 3), (256, 259)] + 2 * _H + [(256, 259)] + _H + [(65, 256)],
+    "fourier": [(256, 259), (256, 515)] + 2 * _H + [(256, 515)] + 2 * _H + [(65, 256)],
+}
+
+
+def _ls_pack(what: str, symbol: str, precision: str, groups, shapes, *extra, bias_required: bool = False) -> torch.Tensor:
+    """One weight stream of the layer-synchronous engine: groups = [(weights, biases)] per MLP, shapes = the Linear shapes each
+    must have, extra = the entry's own integers; calls `symbol`(precision, w0, b0[, w1, b1], *extra, packed, stream)."""
+    lib = _lib.load()
+    keep = []
+    for (ws, bs), shp in zip(groups, shapes):
+        assert len(ws) == len(shp) and len(bs) == len(shp), f"{what}: {len(shp)} Linears, got {len(ws)} weights / {len(bs)} biases"
+        keep += [[_f32(w.detach(), "weight") for w in ws],
+                 [None if b is None and not bias_required else _f32(b.detach(), "bias") for b in bs]]
+    for w, shp in zip(sum(keep[0::2], []), sum(shapes, [])):
+        if tuple(w.shape) != tuple(shp):
+            raise ValueError(f"{what}: weight shape {tuple(w.shape)} != {tuple(shp)}")
+    nbytes = int(getattr(lib, symbol.replace("_pack", "_packed_bytes"))(PREC[precision]))
+    if nbytes == 0:
+        raise _lib.NaError(f"{what}: precision {precision} not supported")
+    arrs = [(C.c_void_p * len(lst))(*[0 if t is None else t.data_ptr() for t in lst]) for lst in keep]
+    packed = torch.empty(nbytes, device=keep[0][0].device, dtype=torch.uint8)
+    check(getattr(lib, symbol)(PREC[precision], *arrs, *extra, _ptr(packed), _stream()))
+    return packed
+
+
+def _ls_batch(rays: torch.Tensor, T: int, pts: Optional[torch.Tensor]):
+    """R, and `pts` [T, *batch, 3] checked against it"""
+    R = rays.numel() // 6
+    if pts is not None:
+        pts = _f32(pts, "pts")
+        assert pts.numel() == T * R * 3, (pts.shape, T, R)
+    return R, pts
+
+
+def _ls_outputs(batch, T: int, device, bg: str, want_weights: bool):
+    """(out [*batch, 3], alpha, weights [T, *batch] or None) of a render entry"""
+    if bg not in BG:
+        raise NotImplementedError(bg)
+    out = torch.empty(tuple(batch) + (3,), device=device, dtype=torch.float32)
+    alpha = torch.empty((T,) + tuple(batch), device=device, dtype=torch.float32) if want_weights else None
+    weights = torch.empty((T,) + tuple(batch), device=device, dtype=torch.float32) if want_weights else None
+    return out, alpha, weights
+
+
+def _ls_workspace(workspace: Optional[torch.Tensor], T: int, R: int, device, head: bool = False) -> torch.Tensor:
+    if workspace is not None:
+        return workspace
+    lib = _lib.load()
+    nbytes = lib.na_render_head_ls_workspace_bytes(T, R) if head else lib.na_render_ls_workspace_bytes(T, R)
+    return torch.empty(int(nbytes), device=device, dtype=torch.uint8)
+
+
 def render_ls_pack(precision: str, first_wb, view_wb) -> torch.Tensor:
     """Pack PlainNeRF.first and View.mlp ({init, layers.0..3, out} weights and biases each) into the weight stream of
     the layer-synchronous renderer (na_render_ls_pack)."""
-    lib = _lib.load()
-    (w1, b1), (w2, b2) = first_wb, view_wb
-    assert len(w1) == 6 and len(w2) == 6, "the LS renderer is specialised for 4 hidden layers per MLP"
-    dev = w1[0].device
-    keep = [[_f32(w.detach(), "weight") for w in w1], [None if b is None else _f32(b.detach(), "bias") for b in b1],
-            [_f32(w.detach(), "weight") for w in w2], [None if b is None else _f32(b.detach(), "bias") for b in b2]]
-    shapes1 = [(256, 38), (256, 294), (256, 256), (256, 256), (256, 256), (65, 256)]
-    shapes2 = [(256, 69), (256, 325), (256, 256), (256, 256), (256, 256), (3, 256)]
-    for w, shp in zip(keep[0] + keep[2], shapes1 + shapes2):
-        if tuple(w.shape) != shp:
-            raise ValueError(f"LS renderer: weight shape {tuple(w.shape)} != {shp}")
-    arrs = [(C.c_void_p * 6)(*[0 if t is None else t.data_ptr() for t in lst]) for lst in keep]
-    packed = torch.empty(int(lib.na_render_ls_packed_bytes(PREC[precision])), device=dev, dtype=torch.uint8)
-    check(lib.na_render_ls_pack(PREC[precision], arrs[0], arrs[1], arrs[2], arrs[3], _ptr(packed), _stream()))
-    return packed
+    return _ls_pack("LS renderer", "na_render_ls_pack", precision, [first_wb, view_wb], [_LS_SHAPES["first"], _LS_SHAPES["view"]])
 
 
 def render_plain_view_ls(rays: torch.Tensor, ts: torch.Tensor, hash_tables: torch.Tensor, packed: torch.Tensor,
@@ -1088,20 +1137,10 @@ def render_plain_view_ls(rays: torch.Tensor, ts: torch.Tensor, hash_tables: torc
     """PlainNeRF(view) forward on the layer-synchronous engine (same contract as render_plain_view)."""
     lib = _lib.load()
     rays, ts, hash_tables = _f32(rays, "rays"), _f32(ts, "ts"), _f32(hash_tables, "hash_tables")
-    R = rays.numel() // 6
     T = ts.shape[0]
-    if bg not in BG:
-        raise NotImplementedError(bg)
-    nbytes = int(lib.na_render_ls_workspace_bytes(T, R))
-    if workspace is None:
-        workspace = torch.empty(nbytes, device=rays.device, dtype=torch.uint8)
-    out = torch.empty(tuple(rays.shape[:-1]) + (3,), device=rays.device, dtype=torch.float32)
-    shape_t = (T,) + tuple(rays.shape[:-1])
-    alpha = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
-    weights = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
-    if pts is not None:
-        pts = _f32(pts, "pts")
-        assert pts.numel() == T * R * 3, (pts.shape, T, R)
+    R, pts = _ls_batch(rays, T, pts)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
+    workspace = _ls_workspace(workspace, T, R, rays.device)
     check(lib.na_render_plain_view_ls(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(hash_tables), _ptr(packed),
                                       PREC[precision], SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights),
                                       _ptr(out), _ptr(workspace), workspace.numel(), _stream()))
@@ -1128,7 +1167,7 @@ def train_plain_view_ls(rays: torch.Tensor, ts: torch.Tensor, pts: torch.Tensor,
     density = torch.empty((N,), device=dev, dtype=torch.float32)
     rgb_pre = torch.empty((N, 3), device=dev, dtype=torch.float32)
     out = torch.empty(tuple(rays.shape[:-1]) + (3,), device=dev, dtype=torch.float32)
-    workspace = torch.empty(int(lib.na_render_ls_workspace_bytes(T, R)), device=dev, dtype=torch.uint8)
+    workspace = _ls_workspace(None, T, R, dev)
     check(lib.na_train_plain_view_ls(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(hash_tables), _ptr(packed), SIGMOID[sigmoid_kind],
                                      _ptr(planes), _ptr(view_rows), _ptr(density), _ptr(rgb_pre), _ptr(out), _ptr(workspace),
                                      workspace.numel(), _stream()))
@@ -1163,15 +1202,8 @@ def render_plain_view_ls_rayts(rays: torch.Tensor, ts_ray: torch.Tensor, hash_ta
     R = rays.numel() // 6
     T = ts_ray.shape[-1]
     assert ts_ray.numel() == R * T, (ts_ray.shape, R)
-    if bg not in BG:
-        raise NotImplementedError(bg)
-    nbytes = int(lib.na_render_ls_workspace_bytes(T, R))
-    if workspace is None:
-        workspace = torch.empty(nbytes, device=rays.device, dtype=torch.uint8)
-    out = torch.empty(tuple(rays.shape[:-1]) + (3,), device=rays.device, dtype=torch.float32)
-    shape_t = (T,) + tuple(rays.shape[:-1])
-    alpha = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
-    weights = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
+    workspace = _ls_workspace(workspace, T, R, rays.device)
     check(lib.na_render_plain_view_ls_rayts(_ptr(rays), R, _ptr(ts_ray), T, _ptr(hash_tables), _ptr(packed), PREC[precision],
                                             SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _ptr(workspace),
                                             workspace.numel(), _stream()))
@@ -1182,21 +1214,8 @@ def render_plain_view_ls_rayts(rays: torch.Tensor, ts_ray: torch.Tensor, hash_ta
 def render_plain_mip_ls_pack(precision: str, first_wb, view_wb) -> torch.Tensor:
     """PlainNeRF.first and View.mlp of a mip model (96 IPE latent columns in both) as one weight stream of the
     layer-synchronous renderer (na_render_plain_mip_ls_pack; f16x only)."""
-    lib = _lib.load()
-    (w1, b1), (w2, b2) = first_wb, view_wb
-    assert len(w1) == 6 and len(w2) == 6, "the LS renderer is specialised for 4 hidden layers per MLP"
-    dev = w1[0].device
-    keep = [[_f32(w.detach(), "weight") for w in w1], [_f32(b.detach(), "bias") for b in b1],
-            [_f32(w.detach(), "weight") for w in w2], [_f32(b.detach(), "bias") for b in b2]]
-    shapes1 = [(256, 134), (256, 390), (256, 256), (256, 256), (256, 256), (65, 256)]
-    shapes2 = [(256, 165), (256, 421), (256, 256), (256, 256), (256, 256), (3, 256)]
-    for w, shp in zip(keep[0] + keep[2], shapes1 + shapes2):
-        if tuple(w.shape) != shp:
-            raise ValueError(f"LS mip renderer: weight shape {tuple(w.shape)} != {shp}")
-    arrs = [(C.c_void_p * 6)(*[t.data_ptr() for t in lst]) for lst in keep]
-    packed = torch.empty(int(lib.na_render_plain_mip_ls_packed_bytes(PREC[precision])), device=dev, dtype=torch.uint8)
-    check(lib.na_render_plain_mip_ls_pack(PREC[precision], arrs[0], arrs[1], arrs[2], arrs[3], _ptr(packed), _stream()))
-    return packed
+    return _ls_pack("LS mip renderer", "na_render_plain_mip_ls_pack", precision, [first_wb, view_wb],
+                    [_LS_SHAPES["mip_first"], _LS_SHAPES["mip_view"]], bias_required=True)
 
 
 def render_plain_mip_ls(rays: torch.Tensor, ts: torch.Tensor, hash_tables: torch.Tensor, packed: torch.Tensor, precision: str,
@@ -1208,14 +1227,8 @@ def render_plain_mip_ls(rays: torch.Tensor, ts: torch.Tensor, hash_tables: torch
     assert rays.dim() == 4 and rays.shape[-1] == 6, rays.shape
     B, H, W = rays.shape[:3]
     R, T = B * H * W, ts.shape[0]
-    if bg not in BG:
-        raise NotImplementedError(bg)
-    nbytes = int(lib.na_render_ls_workspace_bytes(T, R))
-    if workspace is None:
-        workspace = torch.empty(nbytes, device=rays.device, dtype=torch.uint8)
-    out = torch.empty((B, H, W, 3), device=rays.device, dtype=torch.float32)
-    alpha = torch.empty((T, B, H, W), device=rays.device, dtype=torch.float32) if want_weights else None
-    weights = torch.empty((T, B, H, W), device=rays.device, dtype=torch.float32) if want_weights else None
+    out, alpha, weights = _ls_outputs((B, H, W), T, rays.device, bg, want_weights)
+    workspace = _ls_workspace(workspace, T, R, rays.device)
     check(lib.na_render_plain_mip_ls(_ptr(rays), B, H, W, _ptr(ts), T, _ptr(hash_tables), _ptr(packed), PREC[precision],
                                      MIP_KIND[kind], min_deg, max_deg, float(t_end), SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha),
                                      _ptr(weights), _ptr(out), _ptr(workspace), workspace.numel(), _stream()))
@@ -1223,54 +1236,20 @@ def render_plain_mip_ls(rays: torch.Tensor, ts: torch.Tensor, hash_tables: torch
     return out, alpha, weights
 
 
-def _wb_arrays(lists):
-    return [(C.c_void_p * len(lst))(*[0 if t is None else t.data_ptr() for t in lst]) for lst in lists]
-
-
-_FIRST_SHAPES = [(256, 38), (256, 294), (256, 256), (256, 256), (256, 256), (65, 256)]
-
-
 def render_plain_pos_ls_pack(precision: str, first_wb, pos_wb) -> torch.Tensor:
     """PlainNeRF.first and refl.Positional.mlp ({init, layers.0..4, out}) as one weight stream of the layer-synchronous renderer
     (na_render_plain_pos_ls_pack; f16x only)."""
-    lib = _lib.load()
-    (w1, b1), (w2, b2) = first_wb, pos_wb
-    assert len(w1) == 6 and len(w2) == 7
-    keep = [[_f32(w.detach(), "weight") for w in w1], [_f32(b.detach(), "bias") for b in b1],
-            [_f32(w.detach(), "weight") for w in w2], [_f32(b.detach(), "bias") for b in b2]]
-    shapes2 = [(256, 102), (256, 358), (256, 256), (256, 256), (256, 358), (256, 256), (3, 256)]
-    for w, shp in zip(keep[0] + keep[2], _FIRST_SHAPES + shapes2):
-        if tuple(w.shape) != shp:
-            raise ValueError(f"LS pos renderer: weight shape {tuple(w.shape)} != {shp}")
-    nbytes = int(lib.na_render_plain_pos_ls_packed_bytes(PREC[precision]))
-    if nbytes == 0:
-        raise _lib.NaError(f"LS pos renderer: precision {precision} not supported (f16x)")
-    arrs = _wb_arrays(keep)
-    packed = torch.empty(nbytes, device=keep[0][0].device, dtype=torch.uint8)
-    check(lib.na_render_plain_pos_ls_pack(PREC[precision], arrs[0], arrs[1], arrs[2], arrs[3], _ptr(packed), _stream()))
-    return packed
+    return _ls_pack("LS pos renderer", "na_render_plain_pos_ls_pack", precision, [first_wb, pos_wb],
+                    [_LS_SHAPES["first"], _LS_SHAPES["pos"]], bias_required=True)
 
 
 def render_plain_plv_ls_pack(precision: str, first_wb, head_wb, n_rl: int = 0) -> torch.Tensor:
     """PlainNeRF.first and refl.PosLinearView ({pos.init, pos.layers.0..1, pos.out, view.init, view.layers.0..1, view.out}) as one
     weight stream (na_render_plain_plv_ls_pack; f16x only); n_rl = DynamicNeRF's refl_latent columns (0..3)."""
-    lib = _lib.load()
-    (w1, b1), (w2, b2) = first_wb, head_wb
-    assert len(w1) == 6 and len(w2) == 8
-    keep = [[_f32(w.detach(), "weight") for w in w1], [_f32(b.detach(), "bias") for b in b1],
-            [_f32(w.detach(), "weight") for w in w2], [_f32(b.detach(), "bias") for b in b2]]
-    n = int(n_rl)
-    shapes2 = [(256, 102 + n), (256, 358 + n), (256, 256), (67, 256), (128, 134 + n), (128, 262 + n), (128, 128), (1, 128)]
-    for w, shp in zip(keep[0] + keep[2], _FIRST_SHAPES + shapes2):
-        if tuple(w.shape) != shp:
-            raise ValueError(f"LS pos-linear-view renderer: weight shape {tuple(w.shape)} != {shp}")
-    nbytes = int(lib.na_render_plain_plv_ls_packed_bytes(PREC[precision]))
-    if nbytes == 0 or not 0 <= n <= 3:
-        raise _lib.NaError(f"LS pos-linear-view renderer: precision {precision} / {n} refl_latent columns not supported (f16x, 0..3)")
-    arrs = _wb_arrays(keep)
-    packed = torch.empty(nbytes, device=keep[0][0].device, dtype=torch.uint8)
-    check(lib.na_render_plain_plv_ls_pack(PREC[precision], arrs[0], arrs[1], arrs[2], arrs[3], n, _ptr(packed), _stream()))
-    return packed
+    n = int(n_rl)  # (0..3: the C entry refuses anything else)
+    head =[(256, 102 + n), (256, 358 + n), (256, 256), (67, 256), (128, 134 + n), (128, 262 + n), (128, 128), (1, 128)]
+    return _ls_pack("LS pos-linear-view renderer", "na_render_plain_plv_ls_pack", precision, [first_wb, head_wb],
+                    [_LS_SHAPES["first"], head], n, bias_required=True)
 
 
 def _render_head_ls(which: str, rays, ts, hash_tables, hash_tables_refl, packed, precision, sigmoid_kind, bg, want_weights, workspace,
@@ -1278,20 +1257,10 @@ def _render_head_ls(which: str, rays, ts, hash_tables, hash_tables_refl, packed,
     lib = _lib.load()
     rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
     hash_tables, hash_tables_refl = _f32(hash_tables, "hash_tables"), _f32(hash_tables_refl, "hash_tables_refl")
-    R = rays.numel() // 6
     T = ts.shape[0]
-    if bg not in BG:
-        raise NotImplementedError(bg)
-    nbytes = int(lib.na_render_head_ls_workspace_bytes(T, R))
-    if workspace is None:
-        workspace = torch.empty(nbytes, device=rays.device, dtype=torch.uint8)
-    out = torch.empty(tuple(rays.shape[:-1]) + (3,), device=rays.device, dtype=torch.float32)
-    shape_t = (T,) + tuple(rays.shape[:-1])
-    alpha = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
-    weights = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
-    if pts is not None:
-        pts = _f32(pts, "pts")
-        assert pts.numel() == T * R * 3, (pts.shape, T, R)
+    R, pts = _ls_batch(rays, T, pts)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
+    workspace = _ls_workspace(workspace, T, R, rays.device, head=True)
     if which == "pos":
         assert refl_latent is None
         check(lib.na_render_plain_pos_ls(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(hash_tables), _ptr(hash_tables_refl), _ptr(packed),
@@ -1328,23 +1297,9 @@ def render_plain_plv_ls(rays, ts, hash_tables, hash_tables_refl, packed, precisi
 def mlp_hash_ls_pack(precision: str, weights, biases) -> torch.Tensor:
     """Pack a hash-encoded SkipConnMLP (in 3, HashEncoder, 5 x 256, skip 3: {init, layers.0..4, out}) into the weight stream of the
     layer-synchronous engine (D-NeRF's deformation network): "f16x" (out <= 32) or, round 6, "bf16x3" (the three-product split, out <= 64)."""
-    lib = _lib.load()
-    assert len(weights) == 7 and len(biases) == 7
-    ws = [_f32(w.detach(), "weight") for w in weights]
-    bs = [None if b is None else _f32(b.detach(), "bias") for b in biases]
-    n_out = ws[-1].shape[0]
-    shapes = [(256, 38), (256, 294), (256, 256), (256, 256), (256, 294), (256, 256), (n_out, 256)]
-    for w, shp in zip(ws, shapes):
-        if tuple(w.shape) != shp:
-            raise ValueError(f"LS hash MLP: weight shape {tuple(w.shape)} != {shp}")
-    nbytes = int(lib.na_mlp_hash_ls_packed_bytes(PREC[precision]))
-    if nbytes == 0 or not 1 <= n_out <= (64 if precision == "bf16x3" else 32):
-        raise _lib.NaError(f"LS hash MLP: precision {precision} / {n_out} output rows not supported (f16x: <= 32 rows, bf16x3: <= 64)")
-    wp = (C.c_void_p * 7)(*[w.data_ptr() for w in ws])
-    bp = (C.c_void_p * 7)(*[0 if b is None else b.data_ptr() for b in bs])
-    packed = torch.empty(nbytes, device=ws[0].device, dtype=torch.uint8)
-    check(lib.na_mlp_hash_ls_pack(PREC[precision], wp, bp, n_out, _ptr(packed), _stream()))
-    return packed
+    n_out = int(weights[-1].shape[0])  # (f16x: <= 32 rows, bf16x3: <= 64: the C entry refuses anything else)
+    shapes = [(256, 38), (256, 294)] + 2 * _H + [(256, 294)] + _H + [(n_out, 256)]
+    return _ls_pack("LS hash MLP", "na_mlp_hash_ls_pack", precision, [(weights, biases)], [shapes], n_out)
 
 
 def mlp_hash_ls(rays: torch.Tensor, ts: torch.Tensor, tables: torch.Tensor, packed: torch.Tensor, precision: str, n_out: int,
@@ -1353,10 +1308,7 @@ def mlp_hash_ls(rays: torch.Tensor, ts: torch.Tensor, tables: torch.Tensor, pack
     lib = _lib.load()
     rays, ts, tables = _f32(rays, "rays"), _f32(ts, "ts"), _f32(tables, "tables")
     T = ts.shape[0]
-    R = rays.numel() // 6
-    if pts is not None:
-        pts = _f32(pts, "pts")
-        assert pts.numel() == T * R * 3
+    R, pts = _ls_batch(rays, T, pts)
     y = torch.empty((T,) + tuple(rays.shape[:-1]) + (n_out,), device=rays.device, dtype=torch.float32)
     check(lib.na_mlp_hash_ls(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(tables), _ptr(packed), PREC[precision], n_out, _ptr(y),
                              n_out, _stream()))
@@ -1367,22 +1319,7 @@ def mlp_hash_ls(rays: torch.Tensor, ts: torch.Tensor, tables: torch.Tensor, pack
 def mlp_fourier_ls_pack(precision: str, weights, biases) -> torch.Tensor:
     """Pack a Fourier-encoded SkipConnMLP (in 3, 128 frequencies, 6 x 256, skip 3, out 65: {init, layers.0..5, out}) into the weight
     stream of the layer-synchronous engine (f16x only; VolSDF's MLP SDF network)."""
-    lib = _lib.load()
-    assert len(weights) == 8 and len(biases) == 8
-    ws = [_f32(w.detach(), "weight") for w in weights]
-    bs = [None if b is None else _f32(b.detach(), "bias") for b in biases]
-    shapes = [(256, 259), (256, 515), (256, 256), (256, 256), (256, 515), (256, 256), (256, 256), (65, 256)]
-    for w, shp in zip(ws, shapes):
-        if tuple(w.shape) != shp:
-            raise ValueError(f"LS Fourier MLP: weight shape {tuple(w.shape)} != {shp}")
-    nbytes = int(lib.na_mlp_fourier_ls_packed_bytes(PREC[precision]))
-    if nbytes == 0:
-        raise _lib.NaError(f"LS Fourier MLP: precision {precision} not supported (f16x only)")
-    wp = (C.c_void_p * 8)(*[w.data_ptr() for w in ws])
-    bp = (C.c_void_p * 8)(*[0 if b is None else b.data_ptr() for b in bs])
-    packed = torch.empty(nbytes, device=ws[0].device, dtype=torch.uint8)
-    check(lib.na_mlp_fourier_ls_pack(PREC[precision], wp, bp, _ptr(packed), _stream()))
-    return packed
+    return _ls_pack("LS Fourier MLP", "na_mlp_fourier_ls_pack", precision, [(weights, biases)], [_LS_SHAPES["fourier"]])
 
 
 def mlp_fourier_ls(rays: torch.Tensor, ts: torch.Tensor, basis: torch.Tensor, packed: torch.Tensor, precision: str,
@@ -1393,10 +1330,7 @@ def mlp_fourier_ls(rays: torch.Tensor, ts: torch.Tensor, basis: torch.Tensor, pa
     rays, ts, basis = _f32(rays, "rays"), _f32(ts, "ts"), _f32(basis, "basis")
     assert tuple(basis.shape) == (3, 128), basis.shape
     T = ts.shape[0]
-    R = rays.numel() // 6
-    if pts is not None:
-        pts = _f32(pts, "pts")
-        assert pts.numel() == T * R * 3
+    R, pts = _ls_batch(rays, T, pts)
     y = torch.empty((T,) + tuple(rays.shape[:-1]) + (65,), device=rays.device, dtype=torch.float32)
     check(lib.na_mlp_fourier_ls(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(basis), _ptr(packed), PREC[precision], _ptr(y), 65,
                                 _stream()))
@@ -1497,19 +1431,7 @@ def row_sqnorm_mean_backward(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
 
 def render_tiny_ls_pack(precision: str, weights, biases) -> torch.Tensor:
     """Pack TinyNeRF.estim ({init, layers.0..5, out}) into the weight stream of the layer-synchronous renderer."""
-    lib = _lib.load()
-    assert len(weights) == 8 and len(biases) == 8, "TinyNeRF.estim has 6 hidden layers"
-    ws = [_f32(w.detach(), "weight") for w in weights]
-    bs = [None if b is None else _f32(b.detach(), "bias") for b in biases]
-    shapes = [(256, 3), (256, 259), (256, 256), (256, 256), (256, 259), (256, 256), (256, 256), (4, 256)]
-    for w, shp in zip(ws, shapes):
-        if tuple(w.shape) != shp:
-            raise ValueError(f"LS TinyNeRF renderer: weight shape {tuple(w.shape)} != {shp}")
-    wp = (C.c_void_p * 8)(*[w.data_ptr() for w in ws])
-    bp = (C.c_void_p * 8)(*[0 if b is None else b.data_ptr() for b in bs])
-    packed = torch.empty(int(lib.na_render_tiny_ls_packed_bytes(PREC[precision])), device=ws[0].device, dtype=torch.uint8)
-    check(lib.na_render_tiny_ls_pack(PREC[precision], wp, bp, _ptr(packed), _stream()))
-    return packed
+    return _ls_pack("LS TinyNeRF renderer", "na_render_tiny_ls_pack", precision, [(weights, biases)], [_LS_SHAPES["tiny"]])
 
 
 def render_tiny_ls(rays: torch.Tensor, ts: torch.Tensor, packed: torch.Tensor, precision: str, sigmoid_kind: str = "thin",
@@ -1517,17 +1439,9 @@ def render_tiny_ls(rays: torch.Tensor, ts: torch.Tensor, packed: torch.Tensor, p
     """TinyNeRF forward in one kernel (layer-synchronous engine): rays [..., 6], ts [T] -> (rgb [..., 3], alpha, weights)."""
     lib = _lib.load()
     rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
-    R = rays.numel() // 6
     T = ts.shape[0]
-    if bg not in BG:
-        raise NotImplementedError(bg)
-    out = torch.empty(tuple(rays.shape[:-1]) + (3,), device=rays.device, dtype=torch.float32)
-    shape_t = (T,) + tuple(rays.shape[:-1])
-    alpha = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
-    weights = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
-    if pts is not None:
-        pts = _f32(pts, "pts")
-        assert pts.numel() == T * R * 3, (pts.shape, T, R)
+    R, pts = _ls_batch(rays, T, pts)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
     check(lib.na_render_tiny_ls(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(packed), PREC[precision], SIGMOID[sigmoid_kind],
                                 BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
     _f16x_guard(precision, out, "na_render_tiny_ls")
@@ -1536,19 +1450,7 @@ def render_tiny_ls(rays: torch.Tensor, ts: torch.Tensor, packed: torch.Tensor, p
 
 def render_view_ls_pack(precision: str, weights, biases) -> torch.Tensor:
     """Pack refl.View's MLP ({init, layers.0..3, out}; 5 + 64 inputs) into the weight stream of na_render_view_ls."""
-    lib = _lib.load()
-    assert len(weights) == 6 and len(biases) == 6
-    ws = [_f32(w.detach(), "weight") for w in weights]
-    bs = [None if b is None else _f32(b.detach(), "bias") for b in biases]
-    shapes = [(256, 69), (256, 325), (256, 256), (256, 256), (256, 256), (3, 256)]
-    for w, shp in zip(ws, shapes):
-        if tuple(w.shape) != shp:
-            raise ValueError(f"LS View renderer: weight shape {tuple(w.shape)} != {shp}")
-    wp = (C.c_void_p * 6)(*[w.data_ptr() for w in ws])
-    bp = (C.c_void_p * 6)(*[0 if b is None else b.data_ptr() for b in bs])
-    packed = torch.empty(int(lib.na_render_view_ls_packed_bytes(PREC[precision])), device=ws[0].device, dtype=torch.uint8)
-    check(lib.na_render_view_ls_pack(PREC[precision], wp, bp, _ptr(packed), _stream()))
-    return packed
+    return _ls_pack("LS View renderer", "na_render_view_ls_pack", precision, [(weights, biases)], [_LS_SHAPES["view"]])
 
 
 def render_view_ls(rays: torch.Tensor, ts: torch.Tensor, feat: torch.Tensor, beta: torch.Tensor, packed: torch.Tensor,
@@ -1559,21 +1461,13 @@ def render_view_ls(rays: torch.Tensor, ts: torch.Tensor, feat: torch.Tensor, bet
     is a density logit, sigma = softplus(column 0 - 1) (NeRFAE's rows from `ae_front`)."""
     lib = _lib.load()
     rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
-    R = rays.numel() // 6
     T = ts.shape[0]
+    R, pts = _ls_batch(rays, T, pts)
     feat, ld = _rows(feat, feat.shape[-1], "feat")
     assert feat.shape[0] == T * R and ld >= 65, (feat.shape, T, R, ld)
     beta = None if beta is None else _f32(beta.reshape(1), "beta")
-    if bg not in BG:
-        raise NotImplementedError(bg)
-    workspace = torch.empty(int(lib.na_render_ls_workspace_bytes(T, R)), device=rays.device, dtype=torch.uint8)
-    out = torch.empty(tuple(rays.shape[:-1]) + (3,), device=rays.device, dtype=torch.float32)
-    shape_t = (T,) + tuple(rays.shape[:-1])
-    alpha = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
-    weights = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
-    if pts is not None:
-        pts = _f32(pts, "pts")
-        assert pts.numel() == T * R * 3, (pts.shape, T, R)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
+    workspace = _ls_workspace(None, T, R, rays.device)
     check(lib.na_render_view_ls(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(feat), ld, _ptr(beta), _ptr(packed), PREC[precision],
                                 SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _ptr(workspace),
                                 workspace.numel(), _stream()))
@@ -1583,20 +1477,8 @@ def render_view_ls(rays: torch.Tensor, ts: torch.Tensor, feat: torch.Tensor, bet
 
 def render_volsdf_siren_ls_pack(precision: str, sdf_wb, view_wb) -> torch.Tensor:
     """Pack the SIREN SDF network (7 Linears) and refl.View's MLP (6) into the stream of na_render_volsdf_siren_ls."""
-    lib = _lib.load()
-    (w1, b1), (w2, b2) = sdf_wb, view_wb
-    assert len(w1) == 7 and len(w2) == 6
-    keep = [[_f32(w.detach(), "weight") for w in w1], [None if b is None else _f32(b.detach(), "bias") for b in b1],
-            [_f32(w.detach(), "weight") for w in w2], [None if b is None else _f32(b.detach(), "bias") for b in b2]]
-    shapes = [(256, 3), (256, 259), (256, 256), (256, 256), (256, 259), (256, 256), (65, 256),
-              (256, 69), (256, 325), (256, 256), (256, 256), (256, 256), (3, 256)]
-    for w, shp in zip(keep[0] + keep[2], shapes):
-        if tuple(w.shape) != shp:
-            raise ValueError(f"LS SIREN-VolSDF renderer: weight shape {tuple(w.shape)} != {shp}")
-    arrs = [(C.c_void_p * len(lst))(*[0 if t is None else t.data_ptr() for t in lst]) for lst in keep]
-    packed = torch.empty(int(lib.na_render_volsdf_siren_ls_packed_bytes(PREC[precision])), device=keep[0][0].device, dtype=torch.uint8)
-    check(lib.na_render_volsdf_siren_ls_pack(PREC[precision], arrs[0], arrs[1], arrs[2], arrs[3], _ptr(packed), _stream()))
-    return packed
+    return _ls_pack("LS SIREN-VolSDF renderer", "na_render_volsdf_siren_ls_pack", precision, [sdf_wb, view_wb],
+                    [_LS_SHAPES["siren"], _LS_SHAPES["view"]])
 
 
 def render_volsdf_siren_ls(rays: torch.Tensor, ts: torch.Tensor, beta: torch.Tensor, packed: torch.Tensor, precision: str,
@@ -1605,19 +1487,11 @@ def render_volsdf_siren_ls(rays: torch.Tensor, ts: torch.Tensor, beta: torch.Ten
     """VolSDF (SIREN SDF network + View head) forward in one kernel: rays [..., 6], ts [T] -> (rgb, alpha, weights)."""
     lib = _lib.load()
     rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
-    R = rays.numel() // 6
     T = ts.shape[0]
+    R, pts = _ls_batch(rays, T, pts)
     beta = _f32(beta.reshape(1), "beta")
-    if bg not in BG:
-        raise NotImplementedError(bg)
-    workspace = torch.empty(int(lib.na_render_ls_workspace_bytes(T, R)), device=rays.device, dtype=torch.uint8)
-    out = torch.empty(tuple(rays.shape[:-1]) + (3,), device=rays.device, dtype=torch.float32)
-    shape_t = (T,) + tuple(rays.shape[:-1])
-    alpha = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
-    weights = torch.empty(shape_t, device=rays.device, dtype=torch.float32) if want_weights else None
-    if pts is not None:
-        pts = _f32(pts, "pts")
-        assert pts.numel() == T * R * 3, (pts.shape, T, R)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
+    workspace = _ls_workspace(None, T, R, rays.device)
     check(lib.na_render_volsdf_siren_ls(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(beta), _ptr(packed), PREC[precision],
                                         SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _ptr(workspace),
                                         workspace.numel(), _stream()))

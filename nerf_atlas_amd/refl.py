@@ -146,14 +146,12 @@ class SphericalHarmonic(Reflectance):
         the three wide Linears once their view columns are per-ray terms (cached; rebuilt when a parameter changed)."""
         m = self.mlp
         lins = [m.init, m.layers[0], m.layers[3]]
-        stamp = utils.pack_stamp(lins)
-        hit = self.__dict__.get("_lat_w")
-        if hit is None or stamp is None or hit[0] != stamp:
+
+        def pack():
             H, vc = m.init.out_features, m.in_size + m.enc.output_dims()
             ws = [m.init.weight.data[:, vc:].contiguous()]
-            ws += [torch.cat([l.weight.data[:, :H], l.weight.data[:, H + vc:]], dim=1).contiguous() for l in lins[1:]]
-            hit = self.__dict__["_lat_w"] = (stamp, ws)
-        return hit[1]
+            return ws + [torch.cat([l.weight.data[:, :H], l.weight.data[:, H + vc:]], dim=1).contiguous() for l in lins[1:]]
+        return utils.packed_stream(self, "_lat_w", None, lins, pack)
 
     def _forward_hoisted(self, dirs, latent, kind):
         m = self.mlp

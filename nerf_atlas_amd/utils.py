@@ -145,7 +145,8 @@ def rand(shape, device): return random_source.rand(tuple(shape), device)
 def randn(shape, device): return random_source.randn(tuple(shape), device)
 
 
-PACK_CACHE_ATTRS = ("_packed", "_packed_ls", "_packed_mip_ls", "_packed_view_ls", "_packed_siren_ls", "_packed_fourier_ls", "_packed_front")
+PACK_CACHE_ATTRS = ("_packed", "_packed_ls", "_packed_mip_ls", "_packed_view_ls", "_packed_siren_ls", "_packed_fourier_ls", "_packed_front",
+                    "_packed_head_ls", "_lat_w")
 
 
 def invalidate_packed(module) -> int:
@@ -196,6 +197,25 @@ def pack_stamp(linears):
     if config.repack_always:
         return None
     return tuple((l.weight._version, l.weight.data_ptr(), l.bias._version, l.bias.data_ptr()) for l in linears)
+
+
+def linears_wb(linears):
+    """([weight.data ...], [bias.data ...]) of a list of Linears: what the pack functions of ops take"""
+    return [l.weight.data for l in linears], [l.bias.data for l in linears]
+
+
+def packed_stream(module, attr: str, key, linears, pack):
+    """The one cache of packed weight streams: `module.<attr>[key]` holds (stamp of `linears`, pack()), and pack() runs again when
+    the stamp moved (pack_stamp), under config.repack_always, or after invalidate_packed() -- which only knows the attributes
+    of PACK_CACHE_ATTRS, so any other `attr` is refused here instead of being missed there."""
+    if attr not in PACK_CACHE_ATTRS:
+        raise KeyError(f"{attr!r} is not in utils.PACK_CACHE_ATTRS: invalidate_packed() would never clear it")
+    stamp = pack_stamp(linears)
+    cache = module.__dict__.setdefault(attr, {})
+    hit = cache.get(key)
+    if hit is None or stamp is None or hit[0] != stamp:
+        hit = cache[key] = (stamp, pack())
+    return hit[1]
 
 
 # ------------------------------------------------------------------------------------------------- fallback notices

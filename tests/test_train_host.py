@@ -103,6 +103,82 @@ def test_packed_caches_drop_on_load_state_dict_and_apply():
         config.set_repack_always(False)
 
 
+def _counting_pack():
+    calls = []
+
+    def pack():
+        calls.append(object())
+        return calls[-1]
+    return pack, calls
+
+
+def test_packed_stream_hits_repacks_and_refuses_unknown_attrs():
+    """utils.packed_stream, the one cache in front of every pack function (with a stub `pack`: no GPU)"""
+    import torch
+    from nerf_atlas_amd import config, utils
+    mod = torch.nn.Sequential(torch.nn.Linear(3, 2), torch.nn.Linear(2, 1))
+    lin = list(mod)
+    pack, calls = _counting_pack()
+    a = utils.packed_stream(mod, "_packed_ls", "f16x", lin, pack)
+    assert utils.packed_stream(mod, "_packed_ls", "f16x", lin, pack) is a and len(calls) == 1  # a hit: the same object, no pack
+    assert utils.packed_stream(mod, "_packed_ls", "bf16", lin, pack) is not a and len(calls) == 2  # another key: its own stream
+    with torch.no_grad():
+        lin[1].bias.add_(1.0)  # bumps the version counter: the stamp moves
+    b = utils.packed_stream(mod, "_packed_ls", "f16x", lin, pack)
+    assert b is not a and len(calls) == 3
+    assert utils.packed_stream(mod, "_packed_ls", "f16x", lin, pack) is b and len(calls) == 3
+    config.set_repack_always(True)
+    try:
+        c = utils.packed_stream(mod, "_packed_ls", "f16x", lin, pack)
+        d = utils.packed_stream(mod, "_packed_ls", "f16x", lin, pack)
+        assert c is not b and d is not c and len(calls) == 5  # every call packs
+    finally:
+        config.set_repack_always(False)
+    with pytest.raises(KeyError, match="PACK_CACHE_ATTRS"):
+        utils.packed_stream(mod, "_packed_somewhere_else", "f16x", lin, pack)
+    assert len(calls) == 5 and "_packed_somewhere_else" not in mod.__dict__
+
+
+def test_invalidate_packed_forces_a_repack_for_every_cache_attr():
+    """a write through `.data` moves no stamp: invalidate_packed() is the documented way to re-pack, and it has to reach EVERY
+    cache packed_stream can fill, `_packed_head_ls` (MODEL 7 / 8) and `_lat_w` (the hoisted SH head) included"""
+    import torch
+    from nerf_atlas_amd import utils
+    for attr in utils.PACK_CACHE_ATTRS:
+        mod = torch.nn.Sequential(torch.nn.Linear(3, 2))
+        root = torch.nn.Sequential(mod)
+        pack, calls = _counting_pack()
+        a = utils.packed_stream(mod, attr, None, list(mod), pack)
+        mod[0].weight.data.copy_(torch.ones(2, 3))
+        assert utils.packed_stream(mod, attr, None, list(mod), pack) is a, attr  # (invisible to the stamp)
+        assert utils.invalidate_packed(root) == 1, attr
+        assert utils.packed_stream(mod, attr, None, list(mod), pack) is not a and len(calls) == 2, attr
+
+
+def test_head_and_sh_caches_repack_after_invalidate_packed(monkeypatch):
+    """PlainNeRF.packed_head_ls (`_packed_head_ls`) and SphericalHarmonic._latent_weights (`_lat_w`) after a write through `.data`"""
+    import torch
+    from nerf_atlas_amd import nerf, ops, refl
+    m = nerf.PlainNeRF(steps=8, intermediate_size=64)
+    m.refl = refl.Positional(latent_size=64)
+    seen = []
+    monkeypatch.setattr(ops, "render_plain_pos_ls_pack", lambda precision, first_wb, pos_wb: seen.append((len(first_wb[0]), len(pos_wb[0]))) or object())
+    a = m.packed_head_ls("pos", "f16x")
+    assert m.packed_head_ls("pos", "f16x") is a and seen == [(6, 7)]
+    m.first.init.weight.data.mul_(2.0)
+    assert m.packed_head_ls("pos", "f16x") is a  # (invisible to the stamp: the documented reason to call invalidate_packed)
+    assert m.invalidate_packed() >= 1
+    assert m.packed_head_ls("pos", "f16x") is not a and len(seen) == 2
+    sh = refl.SphericalHarmonic(latent_size=64)
+    w = sh._latent_weights()
+    assert sh._latent_weights() is w and isinstance(sh.__dict__["_lat_w"], dict)
+    sh.mlp.init.weight.data.mul_(2.0)
+    assert sh._latent_weights() is w
+    assert nerf.utils.invalidate_packed(sh) >= 1
+    w2 = sh._latent_weights()
+    assert w2 is not w and torch.equal(w2[0], 2.0 * w[0])
+
+
 def test_train_forward_switch_and_the_step_byte_model():
     """config.train_forward ("ls" = the one-launch training forward, "layers" = one Linear per launch) and bench.py's model of the bytes a
     training step has to move with either: the one-launch forward saves exactly the forward's input reads, 4 B per input column."""
