@@ -627,6 +627,30 @@ int na_render_plain_view_ls_rayts(const float* rays, int64_t R, const float* ts_
                                   const void* packed, int precision, int sigmoid_kind, int bg_kind, float* alpha,
                                   float* weights, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Compositing over PER-RAY steps with a backward: the fine pass of coarse -> fine TRAINING (csrc/composite_rayts.hip).
+ * ts_ray [R,T]: one increasing row per ray (`merged` of na_resample_ts); density / alpha / weights [T,R], feat [T,R,C] step-major.
+ * na_compute_pts_rayts          pts[t, r, :] = r_o[r] + ts_ray[r, t] * r_d[r], na_compute_pts's operation order; pts [T,R,3].
+ * na_composite_rayts            na_composite with interval lengths max(ts_ray[r,t+1] - ts_ray[r,t], 1e-5) |d| (the closing one
+ *                      1e10 |d|); C = 1..8; bg_kind black / white / random, `rand` [R] the per-ray draw of NA_BG_RANDOM (NULL
+ *                      otherwise); alpha / weights NULL or [T,R].  Rows equal to shared steps give na_composite's bits.
+ * na_composite_rayts_backward   g_density [T,R], g_feat [T,R,C] (C = 1 or 3) given g_out [R,C]; `rand` as above, it carries no
+ *                      gradient, nor do the steps.  No atomics: bitwise reproducible.  The decomposition follows T like
+ *                      na_composite_backward's up to 128 steps (rows equal to shared steps: the same bits), 16-step segments go on
+ *                      to 256 steps, any longer row takes the one-thread-per-ray chain.
+ * na_composite_rayts_backward_form  the same with the decomposition named (measurements, tests): NA_RAYTS_BWD_SEG outside
+ *                      17 .. 256 steps is NA_EUNSUPPORTED.
+ * A non-finite step or density poisons its own ray only, as far as the reference's arithmetic makes it non-finite.               */
+enum { NA_RAYTS_BWD_AUTO = 0, NA_RAYTS_BWD_SEQ = 1, NA_RAYTS_BWD_SEG = 2 };
+int na_compute_pts_rayts(const float* rays, int64_t R, const float* ts_ray, int T, float* pts, void* stream);
+int na_composite_rayts(const float* density, const float* feat, const float* ts_ray, const float* rays, int T, int64_t R, int C,
+                       int density_kind, int bg_kind, const float* rand, float* out, float* alpha, float* weights, void* stream);
+int na_composite_rayts_backward(const float* density, const float* feat, const float* ts_ray, const float* rays, int T, int64_t R,
+                                int C, int density_kind, int bg_kind, const float* rand, const float* g_out, float* g_density,
+                                float* g_feat, void* stream);
+int na_composite_rayts_backward_form(const float* density, const float* feat, const float* ts_ray, const float* rays, int T,
+                                     int64_t R, int C, int density_kind, int bg_kind, const float* rand, const float* g_out,
+                                     float* g_density, float* g_feat, int form, void* stream);
+
 /* The training iteration's FORWARD of PlainNeRF(view) as ONE launch (round 6; runner.py:647-825 drives src/nerf.py:326-361, whose two
  * SkipConnMLPs are src/neural_blocks.py:279-296): na_render_plain_view_ls's kernel in NA_PREC_BF16X3 -- the three-product bf16 split
  * of the training GEMMs -- with explicit sample positions pts [T,R,3], which also leaves in HBM what the backward pass reads: the output

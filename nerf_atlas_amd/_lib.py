@@ -179,6 +179,13 @@ SIGNATURES = {
     "na_resample_ts": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, C.c_void_p]),
     "na_render_plain_view_ls_rayts": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                 c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "na_compute_pts_rayts": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_void_p]),
+    "na_composite_rayts": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p,
+                                     c_f32p, c_f32p, C.c_void_p]),
+    "na_composite_rayts_backward": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, c_i64, C.c_int, C.c_int, C.c_int, c_f32p,
+                                              c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "na_composite_rayts_backward_form": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, c_i64, C.c_int, C.c_int, C.c_int, c_f32p,
+                                                   c_f32p, c_f32p, c_f32p, C.c_int, C.c_void_p]),
     "na_train_plain_view_ls": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_int, c_f32p, c_f32p,
                                          c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "na_render_plain_mip_ls_packed_bytes": (C.c_size_t, [C.c_int]),

@@ -380,6 +380,27 @@ class CompositeFn(Function):
         return gd, gf, None, None, None, None, None
 
 
+class CompositeRayTsFn(Function):
+    """CompositeFn over per-ray steps ts_ray [..., T] (the fine pass of coarse -> fine training; csrc/composite_rayts.hip).  Returns
+    (out, alpha, weights); alpha / weights are auxiliary outputs, ts_ray and rays constants: no gradient flows through the sample
+    positions."""
+
+    @staticmethod
+    def forward(ctx, density, feat, ts_ray, rays, softplus, bg, rand=None):
+        out, alpha, weights = ops.composite_rayts(density, feat, ts_ray, rays, softplus=softplus, bg=bg, rand=rand)
+        ctx.save_for_backward(density, feat, ts_ray, rays)
+        ctx.softplus, ctx.bg, ctx.rand = softplus, bg, rand
+        ctx.mark_non_differentiable(alpha, weights)
+        ctx.set_materialize_grads(False)
+        return out, alpha, weights
+
+    @staticmethod
+    def backward(ctx, g_out, _ga, _gw):
+        density, feat, ts_ray, rays = ctx.saved_tensors
+        gd, gf = ops.composite_rayts_backward(density, feat, ts_ray, rays, g_out.contiguous(), ctx.softplus, ctx.bg, rand=ctx.rand)
+        return gd, gf, None, None, None, None, None
+
+
 class SplitHeadFn(Function):
     """(y[..., 0] contiguous, y[..., 1:] as a view) of a network output [.., 1 + C] -- PlainNeRF's density | intermediate
     (src/nerf.py:338-342).  The same values as the two slices; the point is the BACKWARD: autograd's own slice gradients are a

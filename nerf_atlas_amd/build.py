@@ -36,6 +36,7 @@ UNITS = [
     ("sh_head.hip", [], ""),
     ("ae_front.hip", [], ""),
     ("fourier_grad.hip", [], ""),
+    ("composite_rayts.hip", [], ""),
     ("backward.hip", [], ""),
     ("train_gemm.hip", [], ""),
     ("train_bwd.hip", [], ""),

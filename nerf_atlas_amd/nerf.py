@@ -171,11 +171,14 @@ class CommonNeRF(utils.PackedCacheMixin, nn.Module):
         rand = None
         if bg == "random":
             rand = self.bg_rand = utils.rand(tuple(rays.shape[:-1]) + (1,), rays.device)
+        per_ray = ts.dim() > 1  # ts [*batch, T]: the fine pass of coarse -> fine training integrates over per-ray steps
         if torch.is_grad_enabled() and (density.requires_grad or feat.requires_grad):
-            from .autograd import CompositeFn
-            out, self.alpha, self.weights = CompositeFn.apply(density.contiguous(), feat.contiguous(), ts, rays, softplus, bg, rand)
+            from .autograd import CompositeFn, CompositeRayTsFn
+            fn = CompositeRayTsFn if per_ray else CompositeFn
+            out, self.alpha, self.weights = fn.apply(density.contiguous(), feat.contiguous(), ts, rays, softplus, bg, rand)
             return out
-        out, self.alpha, self.weights = ops.composite(density, feat, ts, rays, softplus=softplus, bg=bg, rand=rand)
+        comp = ops.composite_rayts if per_ray else ops.composite
+        out, self.alpha, self.weights = comp(density, feat, ts, rays, softplus=softplus, bg=bg, rand=rand)
         return out
 
 
@@ -227,7 +230,9 @@ class TinyNeRF(CommonNeRF):
 
 # ------------------------------------------------------------------------------------------------- PlainNeRF
 class PlainNeRF(CommonNeRF):
-    """src/nerf.py:310-361."""
+    """src/nerf.py:310-361.  steps_fine > 0 (train.py --steps-fine): every forward is coarse -> fine (forward_coarse_fine)."""
+
+    steps_fine: int = 0  # (a plain attribute, neither parameter nor buffer: the state_dict does not know it)
 
     def __init__(self, out_features: int = 3, **kwargs):
         super().__init__(r=lambda ls: refl.View(out_features=out_features, latent_size=ls + self.intermediate_size),
@@ -336,6 +341,7 @@ class PlainNeRF(CommonNeRF):
 
     @_f16x_policy
     def forward(self, rays, want_weights: bool = True):
+        if self.steps_fine > 0: return self.forward_coarse_fine(rays, self.steps_fine)
         self.ts_ray = None  # (only forward_coarse_fine integrates over per-ray steps)
         if self._fusable():
             _, _, self.ts, _ = compute_ts(rays, self.t_near, self.t_far, self.steps)
@@ -364,8 +370,12 @@ class PlainNeRF(CommonNeRF):
         CoarseFineNeRF, src/nerf.py:548-580, 1745-1779 -- see csrc/basic_ops.hip resample_ts_kernel): a coarse pass over
         `self.steps` shared steps, inverse-cdf resampling of `steps_fine` new positions per ray from its weights (u: None =
         linspace, or [steps_fine, *rays.shape[:-1]] draws), and a fine pass over the union in order -- three launches of the
-        layer-synchronous engine's kernels, one network for both passes like the reference's class.  Inference only."""
+        layer-synchronous engine's kernels, one network for both passes like the reference's class.
+        In training mode, or with gradients wanted: the differentiable route on the operator path (`_coarse_fine_operators`)."""
         if not (self._fusable() and config.engine == "ls"):
+            wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+            if isinstance(self.refl, refl.View) and self.mip is None and (self.training or wants_grad):
+                return self._coarse_fine_operators(rays.contiguous(), steps_fine, u)
             raise NotImplementedError("coarse -> fine rendering runs on the fused layer-synchronous renderer (eval mode, View head)")
         rays = rays.contiguous()
         _, _, ts, _ = compute_ts(rays, self.t_near, self.t_far, self.steps)
@@ -380,6 +390,24 @@ class PlainNeRF(CommonNeRF):
         out, self.alpha, self.weights = ops.render_plain_view_ls_rayts(rays, self.ts_ray, tables, packed, prec, self.sigmoid_kind,
                                                                        self._kernel_bg(), want_weights or self.bg == "random")
         return self._finish_sky(out)
+
+    def _coarse_fine_operators(self, rays, steps_fine: int, u=None):
+        """Coarse -> fine with both passes on the operator path and in the graph: what training minimises is NeRF's joint loss over
+        `self.coarse` and the returned fine image, one network for both (train.py).  The coarse pass is an ordinary forward over the
+        shared steps (stratified in training mode); its weights -- constants -- place `steps_fine` new samples per ray
+        (na_resample_ts; u: the caller's draws, else one utils.rand draw per new sample in training mode, linspace in eval mode),
+        and the fine pass evaluates the same network at o + t d over every ray's own merged row and composites over it
+        (autograd.CompositeRayTsFn).  No gradient flows through the sample positions, as in NeRF.  Density noise and the draw of
+        bg "random" are drawn per pass, coarse first."""
+        pts, ts, r_o, r_d, _ = compute_pts_ts(rays, self.t_near, self.t_far, self.steps, perturb=self._perturb())
+        self.coarse = self._from_pts_operators(pts, ts, r_o, r_d, None, rays)
+        if u is None and self.training:
+            u = utils.rand((steps_fine,) + tuple(rays.shape[:-1]), rays.device)
+        ts_ray = ops.resample_ts(ts, self.weights.detach(), steps_fine, u)
+        out = self._from_pts_operators(ops.compute_pts_rayts(rays, ts_ray), ts_ray, r_o, r_d, None, rays)
+        # the protocol of the fused route: `ts` the [T] shared steps, `ts_ray` [*batch, T + N] what alpha / weights [T + N, ...] follow
+        self.ts, self.ts_ray = ts, ts_ray
+        return out
 
     def from_pts(self, pts, ts, r_o, r_d, refl_latent=None, rays=None):
         if rays is None: rays = torch.cat([r_o, r_d], dim=-1).contiguous()
@@ -400,6 +428,10 @@ class PlainNeRF(CommonNeRF):
                                 f"PlainNeRF with {type(self.refl).__name__} reflectance / intermediate size {self.intermediate_size} is not one of the "
                                 "fused renderer's schedules (View head, intermediate 64, 3 channels): inference runs the generic MLP kernels "
                                 "+ separate compositing")
+        return self._from_pts_operators(pts, ts, r_o, r_d, refl_latent, rays)
+
+    def _from_pts_operators(self, pts, ts, r_o, r_d, refl_latent, rays):
+        """the operator path of `from_pts` (one kernel per operator, with its graph); ts [T] shared steps or [*batch, T] per-ray rows"""
         latent = self.mip_latent(rays, ts)  # lazy: generated in the prologues of `first` and of the View MLP
         pre = self._train_forward_ls(rays, ts, pts, r_d) if latent is None and refl_latent is None else None
         first_out = self.first(pts, latent, pre=None if pre is None else (list(pre[0][:5]), None, pre[3]))

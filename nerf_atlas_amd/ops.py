@@ -1193,6 +1193,67 @@ def resample_ts(ts: torch.Tensor, weights: torch.Tensor, n_fine: int, u: Optiona
     return (merged, fine) if want_fine else merged
 
 
+BG_RAYTS = {"black": 0, "white": 1, "random": 2}
+RAYTS_BWD_FORM = {"auto": 0, "seq": 1, "seg": 2}
+
+
+def compute_pts_rayts(rays: torch.Tensor, ts_ray: torch.Tensor) -> torch.Tensor:
+    """pts[T, *batch, 3] = r_o + ts_ray[*batch, t] r_d over per-ray steps ts_ray [*batch, T] (na_compute_pts_rayts)."""
+    lib = _lib.load()
+    rays, ts_ray = _f32(rays, "rays"), _f32(ts_ray, "ts_ray")
+    R = rays.numel() // 6
+    T = ts_ray.shape[-1]
+    assert tuple(ts_ray.shape[:-1]) == tuple(rays.shape[:-1]), (ts_ray.shape, rays.shape)
+    pts = torch.empty((T,) + tuple(rays.shape[:-1]) + (3,), device=rays.device, dtype=torch.float32)
+    check(lib.na_compute_pts_rayts(_ptr(rays), R, _ptr(ts_ray), T, _ptr(pts), _stream()))
+    return pts
+
+
+def _rayts_args(density, feat, ts_ray, rays, bg, rand):
+    density, feat, ts_ray, rays = _f32(density, "density"), _f32(feat, "feat"), _f32(ts_ray, "ts_ray"), _f32(rays, "rays")
+    T = ts_ray.shape[-1]
+    Cn = feat.shape[-1]
+    R = rays.numel() // 6
+    assert ts_ray.numel() == R * T and density.numel() == T * R and feat.numel() == T * R * Cn, \
+        (density.shape, feat.shape, ts_ray.shape, rays.shape)
+    if bg not in BG_RAYTS:
+        raise NotImplementedError(bg)
+    if bg == "random":
+        rand = _f32(rand, "rand")
+        assert rand.numel() == R, (rand.shape, rays.shape)
+    else:
+        rand = None
+    return density, feat, ts_ray, rays, rand, T, R, Cn
+
+
+def composite_rayts(density: torch.Tensor, feat: torch.Tensor, ts_ray: torch.Tensor, rays: torch.Tensor, softplus: bool = True,
+                    bg: str = "black", want_weights: bool = True, rand: Optional[torch.Tensor] = None):
+    """`composite` over per-ray steps: density [T,...], feat [T,...,C], ts_ray [...,T] (increasing along T), rays [...,6] ->
+    (out [...,C], alpha [T,...], weights [T,...]).  bg "random" takes the per-ray draw `rand` [..., 1]."""
+    lib = _lib.load()
+    density, feat, ts_ray, rays, rand, T, R, Cn = _rayts_args(density, feat, ts_ray, rays, bg, rand)
+    out = torch.empty(tuple(rays.shape[:-1]) + (Cn,), device=rays.device, dtype=torch.float32)
+    alpha = torch.empty_like(density) if want_weights else None
+    weights = torch.empty_like(density) if want_weights else None
+    check(lib.na_composite_rayts(_ptr(density), _ptr(feat), _ptr(ts_ray), _ptr(rays), T, R, Cn, 0 if softplus else 1, BG_RAYTS[bg],
+                                 _ptr(rand), _ptr(out), _ptr(alpha), _ptr(weights), _stream()))
+    return out, alpha, weights
+
+
+def composite_rayts_backward(density, feat, ts_ray, rays, g_out, softplus: bool = True, bg: str = "black", rand=None, form: str = "auto"):
+    """(g_density [T,...], g_feat [T,...,C]) of `composite_rayts` given g_out [...,C]; form: the decomposition over T -- "auto" (by T),
+    "seq" (one thread per ray) or "seg" (16-step segments, 17 .. 256 steps)."""
+    lib = _lib.load()
+    density, feat, ts_ray, rays, rand, T, R, Cn = _rayts_args(density, feat, ts_ray, rays, bg, rand)
+    g_out = _f32(g_out, "g_out")
+    assert g_out.numel() == R * Cn, (g_out.shape, rays.shape, Cn)
+    gd = torch.empty_like(density)
+    gf = torch.empty_like(feat)
+    check(lib.na_composite_rayts_backward_form(_ptr(density), _ptr(feat), _ptr(ts_ray), _ptr(rays), T, R, Cn, 0 if softplus else 1,
+                                               BG_RAYTS[bg], _ptr(rand), _ptr(g_out), _ptr(gd), _ptr(gf), RAYTS_BWD_FORM[form], _stream()))
+    return gd, gf
+
+
 def render_plain_view_ls_rayts(rays: torch.Tensor, ts_ray: torch.Tensor, hash_tables: torch.Tensor, packed: torch.Tensor,
                                precision: str, sigmoid_kind: str = "thin", bg: str = "black", want_weights: bool = False,
                                workspace: Optional[torch.Tensor] = None):

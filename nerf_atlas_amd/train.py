@@ -28,7 +28,7 @@ from .render import render, render_frame
 # the reference's CLI defaults for the fields used here (runner.py:38-424)
 DEFAULTS = dict(
     data=None, data_kind="original", derive_kind=True, size=32, render_size=16, epochs=30000, batch_size=8,
-    crop_size=16, test_crop_size=0, steps=64, mip=None, sigmoid_kind="upshifted", feature_space=3, model="plain",
+    crop_size=16, test_crop_size=0, steps=64, steps_fine=0, mip=None, sigmoid_kind="upshifted", feature_space=3, model="plain",
     dyn_model=None, bg="black", learning_rate=5e-4, seed=1337, decay=0.0, loss_fns=["l2"], sched_min=5e-5,
     no_sched=False, shape_to_refl_size=64, refl_kind="view", refl_order=2, space_kind="identity", normal_kind=None,
     refl_bidirectional=True, sdf_kind="mlp", near=2.0, far=6.0, spline=0, dyn_refl_latent=0, time_gamma=False,
@@ -102,6 +102,17 @@ def load_model(args, is_dyn=False, device="cuda"):
     """runner.py:1169-1211 for the supported kinds."""
     if args.model == "sdf":
         raise NotImplementedError("--model sdf (surface rendering) is outside the volume-rendering hot path")
+    steps_fine = int(getattr(args, "steps_fine", 0) or 0)
+    if steps_fine < 0:
+        raise ValueError(f"--steps-fine {steps_fine}: the number of resampled steps per ray cannot be negative")
+    if steps_fine > 0:
+        # coarse -> fine training (DESIGN.md 3h): PlainNeRF with the View head over shared positions only
+        why = (f"--model {args.model}" if args.model != "plain" else f"--refl-kind {args.refl_kind}" if args.refl_kind != "view" else
+               f"--mip {args.mip}" if args.mip is not None else
+               f"--dyn-model {args.dyn_model}" if (args.dyn_model is not None or is_dyn) else None)
+        if why is not None:
+            raise ValueError(f"--steps-fine {steps_fine} (coarse -> fine training) needs --model plain --refl-kind view without --mip "
+                             f"and without a --dyn-model; got {why}")
     model = nerf.load_nerf(args)
     if is_dyn:
         model = nerf.load_dyn(args, model, device)
@@ -109,6 +120,8 @@ def load_model(args, is_dyn=False, device="cuda"):
     # columns here, runner.py:1182-1183, and dies at the first forward: DESIGN.md 7)
     latent = model.intermediate_size + (args.encoding_size if args.model == "ae" else 0)
     model.set_refl(refl.load(args, args.refl_kind, args.space_kind, latent))
+    if steps_fine > 0:
+        model.steps_fine = steps_fine
     return model.to(device)
 
 
@@ -264,6 +277,9 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
         loss = loss_fn(out, ref)
         assert loss.isfinite(), f"Got {loss.item()} loss"
         losses.append(loss.item())
+        if getattr(args, "steps_fine", 0) > 0:
+            # --steps-fine: NeRF's joint loss, the coarse image of the same network next to the fine one (the recorded loss stays the fine image's)
+            loss = loss + loss_fn(model.nerf.coarse, ref)
         if getattr(args, "latent_l2_weight", 0) > 0:
             # runner.py:681 (which names a bare `latent_l2_weight`: the intended args.latent_l2_weight)
             loss = loss + args.latent_l2_weight * model.nerf.latent_l2_loss
