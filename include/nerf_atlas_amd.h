@@ -748,6 +748,36 @@ int na_row_sqnorm_mean(const float* x, int64_t x_ld, int64_t N, int W, float* ou
 int na_row_sqnorm_mean_backward(const float* x, int64_t x_ld, const float* g, int64_t N, int W, float* g_x, int64_t gx_ld,
                                 void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * NeRFVoxel (src/nerf.py:401-524): a dense S^3 grid, densities [S,S,S,1] and rgb [S,S,S,C] (C = 3; another C returns
+ * NA_EUNSUPPORTED), read by the reference's 8-neighbour lookup (grid_coords_trilin_weights, src/nerf.py:493-515): neighbours
+ * p -+ voxel_len / 2 clamped to +-grid_radius, centres (floor(n / voxel_len + 1e-10) + 0.5) voxel_len clamped to
+ * +-(grid_radius - voxel_len / 2), xyz = (p - centre of corner 0) / voxel_len UNclamped (points outside the grid are extrapolated
+ * with sign-alternating weights that sum to 1), ids floor(centre / voxel_len + 1e-10) + S / 2.  Cell membership and xyz are fixed in
+ * fp32: every operation of that chain is the reference's fp32 operation in its order (no fma contraction, correctly rounded
+ * division), with voxel_len etc. the fp32 images of the Python doubles formed from `grid_radius` (a double for that reason).
+ * S even, 2 .. 1024.  Positions: explicit pts [T*R,3] (rays / ts may then be NULL), or rays [R,6] x ts [T] formed in the kernel as
+ * na_compute_pts forms them, sample n = t * R + r.  Every grid read and every accumulate goes through an id clamped to 0 .. S-1 as an
+ * integer: a NaN or Inf coordinate gives NaN in that sample's outputs (and in the <= 8 grid rows its gradient lands in) and
+ * touches no other address.
+ * raw and g_raw rows are read and written as one 16-byte access: both pointers must be 16-byte aligned.
+ * na_voxel_sample           raw [T*R, 1 + C] = [density | C colour parameters], before any activation.
+ * na_voxel_sample_backward  g_densities [S^3] += , g_rgb [S^3, C] += the 8 weights x g_raw [T*R, 1 + C] (outputs zeroed by the
+ *                           caller; no gradient w.r.t. the positions).  fp32 atomics by default; under na_set_deterministic the
+ *                           2^-40 fixed-point path with EVERY contribution converted on its own, so the result is bitwise
+ *                           independent of the order of the samples as well (workspace >= 8 * 4 S^3 bytes = 8 MiB at S = 64,
+ *                           else NA_EWORKSPACE).
+ * na_voxel_render           the eval route as one launch: positions -> lookup -> NA_SIG_* act_kind on the colour parameters ->
+ *                           na_composite's arithmetic (softplus(density - 1) form) against NA_BG_BLACK / NA_BG_WHITE; alpha / weights
+ *                           NULL or [T,R]; out [R,C].  bg random: composite against black, then na_sky_random.              */
+int na_voxel_sample(const float* pts, const float* rays, int64_t R, const float* ts, int T, const float* densities, const float* rgb,
+                    int S, int C, double grid_radius, float* raw, void* stream);
+int na_voxel_sample_backward(const float* pts, const float* rays, int64_t R, const float* ts, int T, const float* g_raw, int S, int C,
+                             double grid_radius, float* g_densities, float* g_rgb, void* stream);
+int na_voxel_render(const float* rays, const float* pts, int64_t R, const float* ts, int T, const float* densities, const float* rgb,
+                    int S, int C, double grid_radius, int act_kind, int bg_kind, float* alpha, float* weights, float* out,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,11 @@ SIGNATURES = {
     "na_render_ls_workspace_bytes": (C.c_size_t, [C.c_int, c_i64]),
     "na_render_plain_view_ls": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_int, C.c_int,
                                           C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "na_voxel_sample": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_double, c_f32p, C.c_void_p]),
+    "na_voxel_sample_backward": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_double, c_f32p, c_f32p,
+                                           C.c_void_p]),
+    "na_voxel_render": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                  c_f32p, c_f32p, c_f32p, C.c_void_p]),
 }
 
 _lib = None

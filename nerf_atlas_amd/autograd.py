@@ -516,3 +516,22 @@ class ViewInputFn(Function):
     @staticmethod
     def backward(ctx, g):
         return (g[..., :3] if ctx.needs_input_grad[0] else None), None
+
+
+class VoxelSampleFn(Function):
+    """raw [..., 1 + C] of NeRFVoxel's grid lookup (ops.voxel_sample); backward scatters into the two grids (ops.voxel_sample_backward).
+    Only the positions are saved -- explicit pts, or rays and ts -- and the cells are recomputed.  No gradient w.r.t. the positions."""
+
+    @staticmethod
+    def forward(ctx, densities, rgb, grid_radius, pts, rays, ts):
+        ctx.grid_radius, ctx.S = grid_radius, densities.shape[0]
+        ctx.explicit = pts is not None
+        ctx.save_for_backward(*((pts,) if ctx.explicit else (rays, ts)))
+        return ops.voxel_sample(densities, rgb, grid_radius, pts=pts, rays=rays, ts=ts)
+
+    @staticmethod
+    def backward(ctx, g):
+        pos = ctx.saved_tensors
+        kw = {"pts": pos[0]} if ctx.explicit else {"rays": pos[0], "ts": pos[1]}
+        g_den, g_rgb = ops.voxel_sample_backward(g.contiguous(), ctx.S, ctx.grid_radius, **kw)
+        return g_den, g_rgb, None, None, None, None

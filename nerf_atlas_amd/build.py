@@ -37,6 +37,7 @@ UNITS = [
     ("ae_front.hip", [], ""),
     ("fourier_grad.hip", [], ""),
     ("composite_rayts.hip", [], ""),
+    ("voxel.hip", [], ""),
     ("backward.hip", [], ""),
     ("train_gemm.hip", [], ""),
     ("train_bwd.hip", [], ""),

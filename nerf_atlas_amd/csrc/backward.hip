@@ -164,20 +164,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const float* __restri
 // 10.2 ms for 262 144 samples).  One wave handles 64 consecutive samples of ONE level; per corner the lanes that share
 // a table row are combined first (leader loop: readfirstlane -> match mask -> wave reduction) and one lane adds the
 // 4 sums.
-// wave total on DPP (row shifts inside rows of 16, row_bcast:15 / :31 across them): 6 VALU instructions instead of the 6
-// dependent ds_bpermute round trips of a __shfl_xor butterfly (402 -> 170 us for the kernel below); the total arrives in lane 63 only
-#define NA_DPP_ADD(X, CTRL, ROWS) \
-  X += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, X), CTRL, ROWS, 0xF, false))
-__device__ __forceinline__ float wave_total_lane63(float x) {
-  NA_DPP_ADD(x, 0x111, 0xF);
-  NA_DPP_ADD(x, 0x112, 0xF);
-  NA_DPP_ADD(x, 0x114, 0xF);
-  NA_DPP_ADD(x, 0x118, 0xF);
-  NA_DPP_ADD(x, 0x142, 0xA);
-  NA_DPP_ADD(x, 0x143, 0xC);
-  return x;
-}
-
+// (wave_total_lane63: common.h, shared with the voxel scatter)
 // Round 3: the wave leaders no longer go to memory.  A workgroup takes a CONTIGUOUS run of samples of one level and sums
 // into a small table in LDS (1024 direct-mapped rows keyed by the table index; a row taken by another index falls through
 // to the global atomic), flushed once at the end: the 4096 waves of a coarse level used to queue on the same few dozen

@@ -65,6 +65,20 @@ __device__ __forceinline__ void accumulate(float* out, long long* fix, int64_t i
   else atomicAdd(out + idx, v);
 }
 
+// wave total on DPP (row shifts inside rows of 16, row_bcast:15 / :31 across them): 6 VALU instructions instead of the 6
+// dependent ds_bpermute round trips of a __shfl_xor butterfly (402 -> 170 us for hash_backward_kernel); the total arrives in lane 63 only
+#define NA_DPP_ADD(X, CTRL, ROWS) \
+  X += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, X), CTRL, ROWS, 0xF, false))
+__device__ __forceinline__ float wave_total_lane63(float x) {
+  NA_DPP_ADD(x, 0x111, 0xF);
+  NA_DPP_ADD(x, 0x112, 0xF);
+  NA_DPP_ADD(x, 0x114, 0xF);
+  NA_DPP_ADD(x, 0x118, 0xF);
+  NA_DPP_ADD(x, 0x142, 0xA);
+  NA_DPP_ADD(x, 0x143, 0xC);
+  return x;
+}
+
 __device__ __forceinline__ float leaky_relu(float v) { return v > 0.f ? v : v * 0.01f; }
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }

@@ -1,5 +1,5 @@
 """Model-variant plugins of the hot path with the reference's protocol (src/nerf.py):
-TinyNeRF, PlainNeRF, NeRFAE, VolSDF, DynamicNeRF(spline) + the registries model_kinds / dyn_model_kinds / load_nerf /
+TinyNeRF, PlainNeRF, NeRFAE, NeRFVoxel, VolSDF, DynamicNeRF(spline) + the registries model_kinds / dyn_model_kinds / load_nerf /
 load_dyn.  Every forward runs HIP kernels only; PlainNeRF with the View head takes the fully fused renderer.
 
 Protocol kept for callers (runner.py): forward(rays) / forward((rays, times)), from_pts(...), .nerf, .refl,
@@ -577,6 +577,101 @@ class NeRFAE(CommonNeRF):
         return self._composite(density, rgb, ts, rays)
 
 
+# ------------------------------------------------------------------------------------------------- NeRFVoxel
+class NeRFVoxel(CommonNeRF):
+    """src/nerf.py:401-524: a dense grid of densities [S,S,S,1] and per-voxel colour parameters rgb [S,S,S,C], read by the reference's
+    8-neighbour lookup (csrc/voxel.hip) -- no MLP anywhere.  The static model with the per-voxel RGB head
+    (`--refl-kind pos`, refl.Positional.to_voxel); the parameters keep the reference's names, so its state_dict loads.
+
+    Routes of `forward` / `from_pts`:
+      eval, no gradients  ops.voxel_render: positions, lookup, activation and compositing as ONE launch (two with bg "random")
+      otherwise           autograd.VoxelSampleFn (lookup; its backward is the scatter-add into the two grids), the head's activation on
+                          the colour columns (autograd.SigmoidFn), CommonNeRF._composite's nodes
+    There is no density noise (the reference class has no noise_std) and no gradient w.r.t. the sample positions."""
+
+    def __init__(self, out_features: int = 3, resolution: int = 64, alpha_init: float = 0.1, grid_radius: float = 1.3,
+                 t_near: float = 0.2, t_far: float = 2, steps: int = 64, sigmoid_kind: str = "upshifted", bg: str = "black", **kwargs):
+        if resolution <= 0 or resolution % 2 != 0:
+            raise ValueError(f"NeRFVoxel resolution {resolution}: even resolutions only (the reference's ids are floor(.) + resolution / 2, "
+                             "a half-integer truncated by .long() when the resolution is odd)")
+        # (unknown kwargs of load_nerf -- mip, intermediate_size, ... -- are swallowed like the reference's **kwargs)
+        super().__init__(steps=steps, t_near=t_near, t_far=t_far, sigmoid_kind=sigmoid_kind, bg=bg)
+        self.resolution = resolution
+        self.densities = nn.Parameter(torch.full([resolution] * 3 + [1], float(alpha_init)))
+        self.rgb = nn.Parameter(torch.rand([resolution] * 3 + [out_features]))
+        self.grid_radius = grid_radius
+        self.voxel_len = grid_radius * 2 / resolution
+        self.brdf = self._bare_brdf
+        self._head = None
+
+    def _bare_brdf(self, params, view):
+        """src/nerf.py:425: before a head is installed the colour is act(parameters)"""
+        return self.feat_act(params)
+
+    @property
+    def refl(self):
+        """the head installed by set_refl, else a parameter-free stand-in like the reference's property (src/nerf.py:434-435)"""
+        return self._head if self._head is not None else refl.Reflectance(act=self.sigmoid_kind, latent_size=0, out_features=3)
+
+    def set_refl(self, r):
+        """src/nerf.py:436-439: the head gives up its MLP (`to_voxel`) and `rgb` is drawn again with its parameter count"""
+        num_params, self.brdf = r.to_voxel()
+        self._head = r
+        self.rgb = nn.Parameter(torch.rand(*self.rgb.shape[:-1], num_params, device=self.rgb.device))
+
+    @property
+    def intermediate_size(self): return 0
+
+    def total_latent_size(self) -> int: return 0
+
+    def set_sigmoid(self, kind="thin"):
+        self.sigmoid_kind = kind
+        self.feat_act = load_sigmoid(kind)
+        if getattr(self, "_head", None) is not None:
+            self._head.act, self._head.act_kind = self.feat_act, kind
+
+    def _act_kind(self):
+        """name of the colour activation for the one-launch route (the head's, once a head is installed), or None"""
+        kind = self.sigmoid_kind if self._head is None else getattr(self._head, "act_kind", None)
+        return kind if kind in ops.SIGMOID else None
+
+    def _fusable(self, pts=None):
+        return (not self.training and not ag.needs_grad(pts, self.densities, self.rgb) and self.rgb.shape[-1] == 3
+                and self._act_kind() is not None and (self._head is None or type(self._head) is refl.Positional))
+
+    def _render(self, rays, ts, pts=None):
+        out, self.alpha, self.weights = ops.voxel_render(rays.contiguous(), ts, self.densities.data, self.rgb.data, self.grid_radius,
+                                                         self._act_kind(), self._kernel_bg(), True, pts=pts)
+        return self._finish_sky(out)
+
+    def _operators(self, rays, ts, r_d, pts=None):
+        if pts is None:
+            raw = ag.VoxelSampleFn.apply(self.densities, self.rgb, self.grid_radius, None, rays.contiguous(), ts)
+        else:
+            raw = ag.VoxelSampleFn.apply(self.densities, self.rgb, self.grid_radius, pts.contiguous(), None, None)
+        if ag.needs_grad(raw):
+            density, params = ag.SplitHeadFn.apply(raw)
+        else:
+            density, params = raw[..., 0].contiguous(), raw[..., 1:]
+        return self._composite(density, self.brdf(params=params.contiguous(), view=r_d), ts, rays)
+
+    def forward(self, rays):
+        r_o, r_d, self.ts, _ = compute_ts(rays, self.t_near, self.t_far, self.steps, perturb=self._perturb())
+        self.ts_ray = None
+        if self._fusable():
+            return self._render(rays, self.ts)
+        return self._operators(rays, self.ts, r_d)  # (positions o + t d are formed inside the lookup kernels, as na_compute_pts forms them)
+
+    def from_pts(self, pts, ts, r_o, r_d, refl_latent=None, rays=None):
+        if rays is None: rays = torch.cat([r_o, r_d], dim=-1).contiguous()
+        if ag.needs_grad(pts):
+            raise NotImplementedError("NeRFVoxel: d(lookup)/d(position) has no HIP backward (sample positions that need a gradient)")
+        self.ts, self.ts_ray = ts, None
+        if self._fusable(pts):
+            return self._render(rays, ts, pts=pts.contiguous())
+        return self._operators(rays, ts, r_d, pts=pts)
+
+
 # ------------------------------------------------------------------------------------------------- VolSDF
 class VolSDF(CommonNeRF):
     """src/nerf.py:861-1018, volume path only (uniform samples, Laplace density, relu, no sky term)."""
@@ -836,8 +931,8 @@ def _experimental(name):
 
 
 # src/nerf.py:1706-1720 / 1698-1704: same keys
-model_kinds = {"tiny": TinyNeRF, "plain": PlainNeRF, "ae": NeRFAE, "volsdf": VolSDF,
-               **{k: _experimental(k) for k in ["coarse_fine", "mpi", "voxel", "rig", "hist"]}}
+model_kinds = {"tiny": TinyNeRF, "plain": PlainNeRF, "ae": NeRFAE, "volsdf": VolSDF, "voxel": NeRFVoxel,
+               **{k: _experimental(k) for k in ["coarse_fine", "mpi", "rig", "hist"]}}
 dyn_model_kinds = {"plain": DynamicNeRF, **{k: _experimental(k) for k in ["ae", "rig", "long", "voxel"]}}
 
 
@@ -868,6 +963,9 @@ def load_dyn(args, model, device=None):
     if isinstance(model, NeRFAE) and cons is DynamicNeRF:
         raise NotImplementedError("--model ae under --dyn-model plain: training the deformation needs d(FourierEncoder)/d(position), which "
                                   "has no HIP backward (DESIGN.md 8); the reference's own pairing, --dyn-model ae, is broken at HEAD")
+    if isinstance(model, NeRFVoxel):
+        raise NotImplementedError(f"--model voxel under --dyn-model {args.dyn_model}: training the deformation needs the gradient of the grid "
+                                  "lookup w.r.t. the sample positions, which has no HIP backward (DESIGN.md 8)")
     if isinstance(model, VolSDF) and cons is DynamicNeRF and args.dyn_refl_latent > 0:
         raise NotImplementedError("--dyn-refl-latent over --model volsdf: VolSDF.from_pts drops the reflectance latent (src/nerf.py:995-1013) "
                                   "while the head is built for it (runner.py:1182-1183), so the reference's first forward raises a shape error")

@@ -1604,3 +1604,82 @@ def eikonal_loss_backward(normals: torch.Tensor, g: torch.Tensor) -> torch.Tenso
     out = torch.empty_like(normals)
     check(lib.na_eikonal_loss_backward(_ptr(normals), normals.shape[1], _ptr(g), _ptr(out), _stream()))
     return out
+
+
+# ------------------------------------------------------------------------------------------------- NeRFVoxel (csrc/voxel.hip)
+def _voxel_grid(densities: torch.Tensor, rgb: torch.Tensor):
+    """(S, C) of densities [S,S,S,1] and rgb [S,S,S,C]; an odd resolution makes the reference's ids `floor + x.5` truncated."""
+    densities, rgb = _f32(densities, "densities"), _f32(rgb, "rgb")
+    S = densities.shape[0]
+    if densities.dim() != 4 or tuple(densities.shape) != (S, S, S, 1) or rgb.dim() != 4 or tuple(rgb.shape[:3]) != (S, S, S):
+        raise ValueError(f"voxel grids must be densities [S,S,S,1] and rgb [S,S,S,C], got {tuple(densities.shape)} and {tuple(rgb.shape)}")
+    if S % 2 != 0 or S < 2:
+        raise ValueError(f"voxel resolution {S}: even resolutions only (the reference's ids are floor(.) + S / 2)")
+    return densities, rgb, S, rgb.shape[-1]
+
+
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """the kernels read and write [density | 3 colours] rows as one 16-byte access: a contiguous view at an odd storage offset is copied"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _voxel_positions(pts, rays, ts):
+    """(pts, rays, ts, R, T, batch shape of one row of samples): explicit pts [..., 3] (T = 1), or rays [..., 6] x ts [T]"""
+    if pts is not None:
+        pts = _f32(pts, "pts")
+        if pts.shape[-1] != 3:
+            raise ValueError(f"pts must be [..., 3], got {tuple(pts.shape)}")
+        return pts, None, None, pts.numel() // 3, 1, tuple(pts.shape[:-1])
+    if rays is None or ts is None:
+        raise ValueError("voxel lookup needs explicit pts, or rays and ts")
+    rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
+    if rays.shape[-1] != 6 or ts.dim() != 1:
+        raise ValueError(f"rays must be [..., 6] and ts [T], got {tuple(rays.shape)} and {tuple(ts.shape)}")
+    return None, rays, ts, rays.numel() // 6, ts.shape[0], (ts.shape[0],) + tuple(rays.shape[:-1])
+
+
+def voxel_sample(densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float, pts: Optional[torch.Tensor] = None,
+                 rays: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """raw [..., 1 + C] = [density | C colour parameters] of the reference's 8-neighbour lookup (src/nerf.py:493-524) at explicit
+    pts [..., 3], or at o + t d of rays [..., 6] x ts [T] formed in the kernel ([T, ..., 1 + C])."""
+    lib = _lib.load()
+    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
+    pts, rays, ts, R, T, batch = _voxel_positions(pts, rays, ts)
+    raw = torch.empty(batch + (1 + Cn,), device=densities.device, dtype=torch.float32)
+    check(lib.na_voxel_sample(_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, Cn, float(grid_radius), _ptr(raw),
+                              _stream()))
+    return raw
+
+
+def voxel_sample_backward(g_raw: torch.Tensor, S: int, grid_radius: float, pts: Optional[torch.Tensor] = None,
+                          rays: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None):
+    """(g_densities [S,S,S,1], g_rgb [S,S,S,C]) of voxel_sample given g_raw [..., 1 + C] and the same positions."""
+    lib = _lib.load()
+    g_raw = _f32(g_raw, "g_raw")
+    if S % 2 != 0 or S < 2:
+        raise ValueError(f"voxel resolution {S}: even resolutions only")
+    pts, rays, ts, R, T, _ = _voxel_positions(pts, rays, ts)
+    Cn = g_raw.shape[-1] - 1
+    if Cn < 1 or g_raw.numel() != T * R * (1 + Cn):
+        raise ValueError(f"g_raw must be [..., 1 + C] with one row per sample ({T * R}), got {tuple(g_raw.shape)}")
+    g_raw = _aligned16(g_raw)
+    g_den = torch.zeros(S, S, S, 1, device=g_raw.device, dtype=torch.float32)
+    g_rgb = torch.zeros(S, S, S, Cn, device=g_raw.device, dtype=torch.float32)
+    check(lib.na_voxel_sample_backward(_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(g_raw), S, Cn, float(grid_radius), _ptr(g_den),
+                                       _ptr(g_rgb), _stream()))
+    return g_den, g_rgb
+
+
+def voxel_render(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float,
+                 sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True, pts: Optional[torch.Tensor] = None):
+    """NeRFVoxel's eval route as ONE launch: positions (o + t d, or explicit pts [T, ..., 3]) -> lookup -> activation -> compositing.
+    (out [..., C], alpha [T, ...], weights [T, ...]); bg black | white (random: composite against black, then sky_random)."""
+    lib = _lib.load()
+    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
+    rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
+    T = ts.shape[0]
+    R, pts = _ls_batch(rays, T, pts)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
+    check(lib.na_voxel_render(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, Cn, float(grid_radius),
+                              SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
+    return out, alpha, weights

@@ -40,6 +40,10 @@ class Reflectance(nn.Module):
     @property
     def can_use_light(self): return False
 
+    def to_voxel(self):
+        """src/refl.py:129: (parameters per voxel, voxel_forward) of the heads that have a per-voxel form (NeRFVoxel.set_refl)"""
+        raise NotImplementedError(f"{type(self)} does not have a voxel repr")
+
 
 def _normalize(v):
     """F.normalize(view, dim=-1) on the GPU; one normalisation per RAY when the directions are broadcast along the
@@ -80,6 +84,15 @@ class Positional(Reflectance):
         self.mlp = SkipConnMLP(in_size=3, out=self.out_features, latent_size=self.latent_size, enc=HashEncoder(),
                                num_layers=5, hidden_size=256)
 
+    def voxel_forward(self, params, view):
+        """src/refl.py:240: the interpolated per-voxel parameters are the colour logits (self.act: autograd.SigmoidFn in a graph)"""
+        return self.act(params)
+
+    def to_voxel(self):
+        """src/refl.py:241-243: the MLP is deleted, the grid holds `out_features` parameters per voxel"""
+        del self.mlp
+        return self.out_features, self.voxel_forward
+
     def forward(self, x, view, normal=None, light=None, latent=None):
         return self.act(self.mlp(x, latent))
 
@@ -95,6 +108,10 @@ class PosLinearView(Reflectance):
                                enc=HashEncoder(input_dims=3), num_layers=2, hidden_size=256)
         self.view = SkipConnMLP(in_size=6, out=1, latent_size=self.latent_size + self.im, num_layers=2,
                                 hidden_size=128, init="siren", activation=torch.sin)
+
+    def to_voxel(self):
+        raise NotImplementedError("refl kind 'pos-linear-view' as a voxel head (src/refl.py:265-280: rgb | 25 spherical-harmonic "
+                                  "coefficients per voxel) is not built: --model voxel takes --refl-kind pos")
 
     def forward(self, x, view, normal=None, light=None, latent=None):
         if hasattr(latent, "tensor") and not torch.is_tensor(latent):
@@ -130,6 +147,10 @@ class SphericalHarmonic(Reflectance):
         self.order = order
         self.mlp = SkipConnMLP(in_size=2, out=self.out_features * (order + 1) * (order + 1), latent_size=self.latent_size,
                                enc=FourierEncoder(input_dims=2), num_layers=5, hidden_size=128, init="xavier")
+
+    def to_voxel(self):
+        raise NotImplementedError("refl kind 'sph-har' as a voxel head is not built (the reference's own form raises a TypeError, "
+                                  "torch.Size + list, at src/refl.py:720): --model voxel takes --refl-kind pos")
 
     def _hoistable(self, view, latent):
         m = self.mlp

@@ -1007,9 +1007,79 @@ def g22():
         save(f"g22_dnerf_volsdf_{name}", **kw)
 
 
+VOXEL_CASES = {  # name: (S, T, ray batch shape, act, bg)
+    "s64_black": (64, 64, (2, 4, 4), "upshifted", "black"),
+    "s64_white": (64, 64, (2, 4, 4), "thin", "white"),
+    "s16_ragged": (16, 24, (1, 5, 7), "leaky_relu", "black"),
+    "s4": (4, 16, (2, 4, 4), "upshifted", "white"),
+    "s2": (2, 7, (2, 4, 4), "thin", "black"),
+}
+
+
+def _voxel_build(S, T, act, bg):
+    """the reference's NeRFVoxel + Positional constructed directly (its runner wiring is dead: DESIGN.md 7), procedural grids"""
+    m = rnerf.NeRFVoxel(resolution=S, t_near=2.0, t_far=6.0, steps=T)
+    m.set_refl(rrefl.Positional(act=act, latent_size=0, out_features=3))
+    m.set_bg(bg)
+    m.eval()
+    names, shapes = fill_procedural(m)
+    return m, names, shapes
+
+
+def g23():
+    """g23_voxel_<case>: the reference's NeRFVoxel (src/nerf.py:401-524) with the per-voxel Positional head, eval mode, near 2 / far 6,
+    generic rays (tests/voxel_ref.py generic_rays: origins on the radius-4 sphere, so the first samples of every ray are extrapolated),
+    in fp32 AND fp64: out, alpha, weights and the reference's own fp32 - fp64 deviation.  A case whose two precisions disagree by more
+    than 1e-5 pins nothing (a sample on a cell-membership plane): the next seed is taken.  S <= 16 also stores the fp64 gradients of
+    densities and rgb for loss = sum(out^2) (and how far the reference's own fp32 gradients are from them, `g_dev`), and the reference's fp32 neighbor_ids and xyz (the argument of its trilinear_weights) on
+    the lattice point set (voxel_ref.lattice_points), which the fixture carries."""
+    import copy
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import voxel_ref as V
+    for name, (S, T, shape, act, bg) in VOXEL_CASES.items():
+        m, names, shapes = _voxel_build(S, T, act, bg)
+        m64 = copy.deepcopy(m).double()
+        for seed in range(4500, 4600, 2):
+            rays = V.generic_rays(shape, seed)
+            out, alpha, weights, ts = m(rays), m.alpha, m.weights, m.ts
+            out64, alpha64, weights64 = m64(rays.double()), m64.alpha, m64.weights
+            dev = {k: float((a.double() - b).abs().max()) for k, a, b in (("out", out, out64), ("alpha", alpha, alpha64), ("weights", weights, weights64))}
+            if max(dev.values()) <= 1e-5:
+                break
+            print(f"g23 {name}: seed {seed} skipped, the reference's fp32 and fp64 disagree by {max(dev.values()):.2e}")
+        else:
+            raise AssertionError(f"g23 {name}: no seed on which the reference agrees with itself")
+        opac = weights64[:-1].sum(0)
+        print(f"g23 {name}: seed {seed}, opacity before the last sample {float(opac.min()):.2f}..{float(opac.max()):.2f}; fp32 vs fp64: "
+              + " ".join(f"{k} {v:.2e}" for k, v in dev.items()))
+        kw = dict(rays=rays, S=S, steps=T, near=2.0, far=6.0, act=act, bg=bg, grid_radius=m.grid_radius, seed=seed, ts=ts,
+                  out=out, out64=out64, alpha=alpha, alpha64=alpha64, weights=weights, weights64=weights64,
+                  dev=np.array([dev["out"], dev["alpha"], dev["weights"]]), **spec(names, shapes))
+        if S <= 16:
+            with torch.enable_grad():
+                for p_ in m64.parameters(): p_.requires_grad_(True)
+                m64(rays.double()).square().sum().backward()
+            with torch.enable_grad():
+                for p_ in m.parameters(): p_.requires_grad_(True)
+                m(rays).square().sum().backward()
+            g_dev = [float((a.grad.double() - b.grad).abs().max() / b.grad.abs().max()) for a, b in ((m.densities, m64.densities), (m.rgb, m64.rgb))]
+            print(f"g23 {name}: the reference's fp32 gradients are {g_dev[0]:.2e} (densities) / {g_dev[1]:.2e} (rgb) of the largest entry off its fp64 ones")
+            kw.update(g_densities64=m64.densities.grad, g_rgb64=m64.rgb.grad, g_dev=np.array(g_dev))
+            lat = V.lattice_points(S, m.grid_radius)
+            seen, orig = [], rnerf.trilinear_weights
+            rnerf.trilinear_weights = lambda xyzs: (seen.append(xyzs), orig(xyzs))[1]
+            try:
+                ids, _ = m.grid_coords_trilin_weights(lat)
+            finally:
+                rnerf.trilinear_weights = orig
+            assert ids.dtype == torch.int64 and seen[0].dtype == torch.float32
+            kw.update(lat_pts=lat, lat_ids=ids, lat_xyz=seen[0])
+        save(f"g23_voxel_{name}", **kw)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23"]
     for g in which:
         globals()[g]()
     with open(os.path.join(OUT, "PROVENANCE.txt"), "w") as f:
