@@ -778,6 +778,30 @@ int na_voxel_render(const float* rays, const float* pts, int64_t R, const float*
                     int S, int C, double grid_radius, int act_kind, int bg_kind, float* alpha, float* weights, float* out,
                     void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Operators on a dense channel-last grid [s0,s1,s2,C], 1 <= C <= 32 (NeRFVoxel's densities and rgb; csrc/grid_ops.hip).
+ * na_grid_tv            total_variation (src/nerf.py:381-399) at n flat indices idxs (int64): x = idx % s0, y = (idx / s0) % s1,
+ *                       z = (idx / (s0 s1)) % s2 -- x is the fastest digit of idx and the slowest axis in memory, as in the
+ *                       reference --, neighbour v + 1 (v - 1 at v == s - 1) per axis, t = sqrt(clamp(dx^2 + dy^2 + dz^2, min = 1e-10))
+ *                       per (sample, channel) in the reference's fp32 operations, out[0] = mean of t over the K = n C elements.  One
+ *                       launch.  out is TWO floats zeroed by the caller (out[1] counts the arriving waves).  An index outside
+ *                       0 .. s0 s1 s2 - 1 is clamped before any address is formed; a NaN / Inf voxel among the sampled rows gives a
+ *                       non-finite value.  Under na_set_deterministic the waves' partial sums are combined in 2^-40 fixed point
+ *                       (sum of t below 2^23) and the value is bitwise reproducible.
+ * na_grid_tv_backward   g_grid [s0,s1,s2,C] += the gradient of that mean times the device scalar g_up[0] (g_grid zeroed by the
+ *                       caller): nothing where q = dx^2 + dy^2 + dz^2 < fp32(1e-10), else (dx + dy + dz) w to the voxel and -d w to
+ *                       each neighbour, w = (g_up / K) / t; duplicates of an index add up.  fp32 atomics by default; under
+ *                       na_set_deterministic every addend goes through 2^-40 fixed point on its own (workspace >= 8 s0 s1 s2 C
+ *                       bytes, else NA_EWORKSPACE) and the result is bitwise independent of the order of idxs.
+ * na_grid_upsample      dst [R,R,R,C] = F.interpolate(mode="trilinear", align_corners=False) of src [S,S,S,C] (src/nerf.py:377-379):
+ *                       per axis scale = (float)S / R, src = max(fmaf(scale, i + 0.5f, -0.5f), 0) in fp32 as torch's builds form it, i0 = floor,
+ *                       i1 = min(i0 + 1, S - 1), the output the sum of 8 products.  One launch.  S, R even, 2 .. 1024; R < S samples
+ *                       the grid down the same way.                                                                              */
+int na_grid_tv(const float* grid, int s0, int s1, int s2, int C, const int64_t* idxs, int64_t n, float* out, void* stream);
+int na_grid_tv_backward(const float* grid, int s0, int s1, int s2, int C, const int64_t* idxs, int64_t n, const float* g_up,
+                        float* g_grid, void* stream);
+int na_grid_upsample(const float* src, int S, float* dst, int R, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -518,6 +518,22 @@ class ViewInputFn(Function):
         return (g[..., :3] if ctx.needs_input_grad[0] else None), None
 
 
+class GridTVFn(Function):
+    """nerf.total_variation (src/nerf.py:381-399) of a grid [s0,s1,s2,C] at flat indices (ops.grid_tv: one launch); backward is
+    ops.grid_tv_backward, one launch that recomputes the differences and reads the upstream scalar on the device."""
+
+    @staticmethod
+    def forward(ctx, grid, idxs, trusted):
+        ctx.trusted = trusted
+        ctx.save_for_backward(grid, idxs)
+        return ops.grid_tv(grid, idxs, trusted)
+
+    @staticmethod
+    def backward(ctx, g):
+        grid, idxs = ctx.saved_tensors
+        return ops.grid_tv_backward(grid, idxs, g.contiguous(), True), None, None  # (the forward checked the indices)
+
+
 class VoxelSampleFn(Function):
     """raw [..., 1 + C] of NeRFVoxel's grid lookup (ops.voxel_sample); backward scatters into the two grids (ops.voxel_sample_backward).
     Only the positions are saved -- explicit pts, or rays and ts -- and the cells are recomputed.  No gradient w.r.t. the positions."""

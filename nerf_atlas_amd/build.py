@@ -38,6 +38,7 @@ UNITS = [
     ("fourier_grad.hip", [], ""),
     ("composite_rayts.hip", [], ""),
     ("voxel.hip", [], ""),
+    ("grid_ops.hip", [], ""),
     ("backward.hip", [], ""),
     ("train_gemm.hip", [], ""),
     ("train_bwd.hip", [], ""),

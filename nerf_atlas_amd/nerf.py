@@ -577,6 +577,26 @@ class NeRFAE(CommonNeRF):
         return self._composite(density, rgb, ts, rays)
 
 
+# ------------------------------------------------------------------------------------------------- grid regulariser
+def random_sample_grid(grid, samples: int = 32 ** 3):
+    """src/nerf.py:391-399: `samples` flat indices into grid [s0,s1,s2,C], drawn with replacement through utils.randint (under
+    replay_reference_rng: torch's CPU stream at the reference's position).  The reference decodes them at once -- x = idxs % s0,
+    y = idxs // s0 % s1, z = idxs // (s0 s1) % s2 --; here the kernels do (csrc/grid_ops.hip), so the flat indices are returned."""
+    s0, s1, s2, _ = grid.shape
+    return utils.randint(0, s0 * s1 * s2, (samples,), grid.device)
+
+
+def total_variation(grid, samples: int = 32 ** 3, idxs=None):
+    """src/nerf.py:381-389 as one launch forward and one backward (autograd.GridTVFn).  idxs: explicit flat indices
+    (range-checked on the host) instead of a draw."""
+    trusted = idxs is None
+    if trusted:
+        idxs = random_sample_grid(grid, samples)
+    if ag.needs_grad(grid):
+        return ag.GridTVFn.apply(grid, idxs, trusted)
+    return ops.grid_tv(grid.detach(), idxs, trusted)
+
+
 # ------------------------------------------------------------------------------------------------- NeRFVoxel
 class NeRFVoxel(CommonNeRF):
     """src/nerf.py:401-524: a dense grid of densities [S,S,S,1] and per-voxel colour parameters rgb [S,S,S,C], read by the reference's
@@ -618,6 +638,39 @@ class NeRFVoxel(CommonNeRF):
         num_params, self.brdf = r.to_voxel()
         self._head = r
         self.rgb = nn.Parameter(torch.rand(*self.rgb.shape[:-1], num_params, device=self.rgb.device))
+
+    def upsample(self, reso: int = 512):
+        """src/nerf.py:454-459: both grids resampled to reso^3 by F.interpolate(mode="trilinear")'s arithmetic (ops.grid_upsample, one
+        launch each; reso below the current resolution samples down the same way) and installed as NEW Parameters -- an optimiser that
+        holds the old ones must be told (train.upsample_voxels)."""
+        reso = int(reso)
+        if reso < 2 or reso % 2 != 0:
+            raise ValueError(f"NeRFVoxel.upsample({reso}): even resolutions only")
+        if not self.densities.is_cuda:
+            raise ValueError("NeRFVoxel.upsample: the grids must live on the GPU (the upsampling has no CPU implementation)")
+        with torch.no_grad():
+            self.rgb = nn.Parameter(ops.grid_upsample(self.rgb.data.contiguous(), reso))
+            self.densities = nn.Parameter(ops.grid_upsample(self.densities.data.contiguous(), reso))
+        self._set_resolution(reso)
+
+    def _set_resolution(self, reso: int):
+        self.resolution = reso
+        self.voxel_len = self.grid_radius * 2 / reso
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        """a checkpoint's grids decide the resolution (a model saved after `upsample` loads into a freshly built one): `densities` and
+        `rgb` are resized before torch copies into them.  Anything else about the shapes (the channel counts) stays torch's size check."""
+        den, rgb = state_dict.get(prefix + "densities"), state_dict.get(prefix + "rgb")
+        if den is not None and rgb is not None and den.dim() == 4 and rgb.dim() == 4 and tuple(den.shape[:3]) != tuple(self.densities.shape[:3]):
+            S = den.shape[0]
+            if tuple(den.shape[:3]) != (S, S, S) or tuple(rgb.shape[:3]) != (S, S, S) or S < 2 or S % 2 != 0:
+                raise ValueError(f"NeRFVoxel: a state_dict with densities {tuple(den.shape)} and rgb {tuple(rgb.shape)}: both grids must be "
+                                 "cubic, of one even resolution")
+            with torch.no_grad():
+                self.densities = nn.Parameter(self.densities.new_empty((S, S, S, self.densities.shape[-1])))
+                self.rgb = nn.Parameter(self.rgb.new_empty((S, S, S, self.rgb.shape[-1])))
+            self._set_resolution(S)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     @property
     def intermediate_size(self): return 0

@@ -1683,3 +1683,73 @@ def voxel_render(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, 
     check(lib.na_voxel_render(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, Cn, float(grid_radius),
                               SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
     return out, alpha, weights
+
+
+# ------------------------------------------------------------------------------------------------- grid operators (csrc/grid_ops.hip)
+GRID_MAX_C = 32
+
+
+def _grid4(grid: torch.Tensor, name: str = "grid") -> torch.Tensor:
+    """a channel-last grid [s0,s1,s2,C] as the kernels read it: device, fp32, contiguous (nothing is converted or copied silently)"""
+    if not grid.is_cuda:
+        raise ValueError(f"{name} must be a CUDA(HIP) tensor: the hot path has no CPU implementation")
+    if grid.dim() != 4 or grid.dtype != torch.float32 or not grid.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float32 [s0,s1,s2,C], got {grid.dtype} {tuple(grid.shape)} "
+                         f"{'contiguous' if grid.is_contiguous() else 'strided'}")
+    if not 1 <= grid.shape[-1] <= GRID_MAX_C:
+        raise ValueError(f"{name} has {grid.shape[-1]} channels: 1 .. {GRID_MAX_C} have a kernel")
+    if min(grid.shape[:3]) < 2 or max(grid.shape[:3]) > 1024:
+        raise ValueError(f"{name} {tuple(grid.shape[:3])}: 2 .. 1024 voxels per axis (a voxel's neighbour is v + 1, or v - 1 on the last plane)")
+    return grid
+
+
+def _grid_idxs(grid: torch.Tensor, idxs: torch.Tensor, trusted: bool) -> torch.Tensor:
+    if not idxs.is_cuda or idxs.device != grid.device:
+        raise ValueError("idxs must live on the grid's device")
+    if idxs.dtype != torch.int64:
+        raise ValueError(f"idxs must be int64 (what torch.randint draws), got {idxs.dtype}")
+    idxs = idxs.reshape(-1).contiguous()
+    if idxs.numel() < 1:
+        raise ValueError("idxs is empty: the mean over no samples")
+    n_elem = grid.shape[0] * grid.shape[1] * grid.shape[2]
+    if not trusted and bool(((idxs < 0) | (idxs >= n_elem)).any()):  # (ONE host check; the kernels clamp whatever they are given)
+        raise ValueError(f"idxs outside the grid: flat indices 0 .. {n_elem - 1}")
+    return idxs
+
+
+def grid_tv(grid: torch.Tensor, idxs: torch.Tensor, trusted: bool = False) -> torch.Tensor:
+    """0-dim total_variation (src/nerf.py:381-399) of grid [s0,s1,s2,C] at the flat indices idxs [n] int64 (x = idx % s0 ...): one launch.
+    trusted: the indices were drawn inside the grid (nerf.random_sample_grid) -- the host range check, a synchronisation, is skipped."""
+    lib = _lib.load()
+    grid = _grid4(grid)
+    idxs = _grid_idxs(grid, idxs, trusted)
+    out = torch.zeros(2, device=grid.device, dtype=torch.float32)  # [value | arrival counter]
+    s0, s1, s2, Cn = grid.shape
+    check(lib.na_grid_tv(_ptr(grid), s0, s1, s2, Cn, _ptr(idxs), idxs.numel(), _ptr(out), _stream()))
+    return out[0]
+
+
+def grid_tv_backward(grid: torch.Tensor, idxs: torch.Tensor, g: torch.Tensor, trusted: bool = False) -> torch.Tensor:
+    """gradient of grid_tv w.r.t. grid times the device scalar g (read by the kernel: no host synchronisation)"""
+    lib = _lib.load()
+    grid = _grid4(grid)
+    idxs = _grid_idxs(grid, idxs, trusted)
+    g = _f32(g.reshape(1), "g")
+    out = torch.zeros_like(grid)
+    s0, s1, s2, Cn = grid.shape
+    check(lib.na_grid_tv_backward(_ptr(grid), s0, s1, s2, Cn, _ptr(idxs), idxs.numel(), _ptr(g), _ptr(out), _stream()))
+    return out
+
+
+def grid_upsample(grid: torch.Tensor, reso: int) -> torch.Tensor:
+    """[R,R,R,C] = F.interpolate(mode="trilinear", align_corners=False) of the cubic grid [S,S,S,C] (src/nerf.py:377-379): one launch"""
+    lib = _lib.load()
+    grid = _grid4(grid)
+    S, reso = grid.shape[0], int(reso)
+    if tuple(grid.shape[:3]) != (S, S, S):
+        raise ValueError(f"grid_upsample takes a cubic grid, got {tuple(grid.shape)}")
+    if S % 2 != 0 or reso % 2 != 0 or not 2 <= reso <= 1024:
+        raise ValueError(f"grid_upsample {S} -> {reso}: even resolutions 2 .. 1024 only")
+    out = torch.empty(reso, reso, reso, grid.shape[-1], device=grid.device, dtype=torch.float32)
+    check(lib.na_grid_upsample(_ptr(grid), S, _ptr(out), reso, grid.shape[-1], _stream()))
+    return out

@@ -4,7 +4,8 @@ cosine schedule, random crops/views from Python's `random`, pixel jitter 0.1, st
 in training mode, `--volsdf-scale-decay`, `--delta-x-decay`, `--offset-decay`, `--sdf-eikonal` (SDF normals by forward-mode
 tangents through the MLP), `--smooth-normals` in the reference's default epsilon-perturbation form (`--smooth-eps`,
 `--smooth-eps-rng`, `--smooth-n-ord`), `--dyn-diverge-decay` (one differentiable direction tangent), `--ffjord-div-decay`
-(forward-mode divergence estimate); `--smooth-normals --smooth-eps 0` (double backward) raises.
+(forward-mode divergence estimate), `--voxel-tv-sigma` / `--voxel-tv-rgb` (total variation of NeRFVoxel's grids) and this build's
+`--voxel-upsample ITER:RESO`; `--smooth-normals --smooth-eps 0` (double backward) raises.
 
 Every forward and backward is a HIP kernel (nerf_atlas_amd/autograd.py); torch.optim owns the parameter update, like
 in the reference.  With `replay_reference_rng=True` the stochastic tensors come from torch's CPU generator in the
@@ -14,6 +15,7 @@ against tests/golden/train_parity_*.json).
 import argparse
 import os
 import random
+import re
 from types import SimpleNamespace
 
 import numpy as np
@@ -38,6 +40,8 @@ DEFAULTS = dict(
     smooth_eps_rng=False, smooth_n_ord=[2],
     neural_upsample=False, quiet=False,
     encoding_size=32, normalize_latent=False, latent_l2_weight=0.0,  # NeRFAE (runner.py:412-416)
+    voxel_tv_sigma=0.0, voxel_tv_rgb=0.0, voxel_tv_bezier=0.0, voxel_tv_rigidity=0.0,  # runner.py:289-301
+    voxel_upsample=[],  # this build's flag: ITER:RESO pairs, NeRFVoxel.upsample(RESO) at the start of iteration ITER
 )
 
 loss_map = {
@@ -57,7 +61,26 @@ def make_args(**overrides) -> SimpleNamespace:
         a.feature_space = 3
     if a.test_crop_size <= 0:
         a.test_crop_size = a.crop_size
+    a.voxel_upsample = parse_voxel_upsample(a.voxel_upsample)
     return a
+
+
+def parse_voxel_upsample(specs):
+    """--voxel-upsample ITER:RESO [ITER:RESO ...] -> [(iteration, resolution)]: iterations strictly increasing, resolutions even."""
+    plan = []
+    for spec in specs:
+        if isinstance(spec, str):
+            m = re.fullmatch(r"(\d+):(\d+)", spec)
+            if m is None:
+                raise ValueError(f"--voxel-upsample {spec!r}: expected ITER:RESO, two non-negative integers")
+            spec = (int(m.group(1)), int(m.group(2)))
+        it, reso = (int(v) for v in spec)
+        if reso < 2 or reso % 2 != 0:
+            raise ValueError(f"--voxel-upsample {it}:{reso}: even resolutions only (NeRFVoxel's ids are floor(.) + resolution / 2)")
+        if it < 0 or (plan and it <= plan[-1][0]):
+            raise ValueError(f"--voxel-upsample: iterations must be increasing, got {it} after {[p[0] for p in plan]}")
+        plan.append((it, reso))
+    return plan
 
 
 def args_from_argv(argv) -> SimpleNamespace:
@@ -76,7 +99,7 @@ def args_from_argv(argv) -> SimpleNamespace:
         elif isinstance(v, bool):
             p.add_argument(flag, action="store_true", default=False)
         elif isinstance(v, list):
-            p.add_argument(flag, nargs="+", default=v, type=type(v[0]))
+            p.add_argument(flag, nargs="+", default=v, type=type(v[0]) if v else str)
         elif v is None:
             p.add_argument(flag, default=None, type=(int if k == "spline" else str))
         else:
@@ -217,6 +240,37 @@ def offset_decay_term(model, curr_percent: float):
     return exp_ratio * reg.mean()
 
 
+def unset_voxel_tv(args, model):
+    """set_per_run (runner.py:1135-1148): total-variation weights the model has no grid for are unset with the reference's warnings,
+    never an error.  (The reference's second test forgets --voxel-tv-rigidity and dies in its first iteration when that weight alone is
+    set on a non-voxel model; here it is unset with the others.)"""
+    tv_dyn = args.voxel_tv_bezier > 0 or args.voxel_tv_rigidity > 0
+    if isinstance(model, nerf.NeRFVoxel):
+        if tv_dyn:
+            print("[warn]: model does not have bezier control points or rigidity for static scene")
+            args.voxel_tv_bezier = args.voxel_tv_rigidity = 0
+    elif args.voxel_tv_sigma > 0 or args.voxel_tv_rgb > 0 or tv_dyn:
+        print("[warn]: model is not voxel, unsetting total variation")
+        args.voxel_tv_sigma = args.voxel_tv_rgb = args.voxel_tv_bezier = args.voxel_tv_rigidity = 0
+
+
+def upsample_voxels(model, opt, reso: int):
+    """--voxel-upsample: NeRFVoxel.upsample(reso), then the two new Parameters take the old ones' places in the optimiser's groups and the
+    old ones' state is deleted -- moments and step count restart for the grids (their shapes changed).  The schedule is left alone."""
+    vox = model.nerf
+    old = (vox.densities, vox.rgb)
+    vox.upsample(reso)
+    new = (vox.densities, vox.rgb)
+    for group in opt.param_groups:
+        for j, p in enumerate(group["params"]):
+            for o, n in zip(old, new):
+                if p is o:
+                    group["params"][j] = n
+    for o in old:
+        opt.state.pop(o, None)
+    opt.zero_grad()
+
+
 def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0, world: int = 1):
     """runner.py:609-850.  Returns the list of per-iteration l2 losses (what save_losses() plots).
     world > 1: data-parallel replicas (one process per GPU, identical seeds): every rank draws the same views and
@@ -241,6 +295,11 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
         raise NotImplementedError("--sdf-eikonal under a dynamic model: the reference's second, dynamic-only eikonal term (runner.py:804-808) "
                                   "adds the points to the (dp, enc) tuple of DynamicNeRF.time_estim and raises a TypeError in its first "
                                   "iteration; `make dnerf_volsdf` (makefile:127-133) trains without --sdf-eikonal")
+    voxel_tv = getattr(args, "voxel_tv_sigma", 0) > 0 or getattr(args, "voxel_tv_rgb", 0) > 0
+    upsample_at = dict(parse_voxel_upsample(getattr(args, "voxel_upsample", [])))
+    if (voxel_tv or upsample_at) and not isinstance(model.nerf, nerf.NeRFVoxel):
+        raise ValueError(f"{'--voxel-upsample' if upsample_at else '--voxel-tv-sigma / --voxel-tv-rgb'} needs --model voxel (fit() unsets the "
+                         "total-variation weights of another model with the reference's warning)")
     device = next(model.parameters()).device
     loss_fn = load_loss_fn(args)
     times = None
@@ -264,9 +323,12 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
                          f"(every replica renders batch_size / world views per step)")
     losses = []
     reg_terms = train.last_reg_terms = []  # (the --dyn-diverge-decay term per iteration: a diagnostic next to the losses)
+    tv_terms = train.last_tv_terms = []    # ([TV(densities), TV(rgb)] per iteration, device scalars: read after the run, no sync in the loop)
     model.train()
     opt.zero_grad()
     for i in range(args.epochs):
+        if i in upsample_at:
+            upsample_voxels(model, opt, upsample_at[i])
         idxs = next_idxs(i)
         if world > 1:
             idxs = na_dist.shard_batch(idxs, rank, world)
@@ -330,6 +392,18 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
             for o in args.smooth_n_ord:
                 smoothness = smoothness + torch.linalg.norm(delta_n, ord=int(o), dim=0).sum()
             loss = loss + args.smooth_normals * smoothness
+        if voxel_tv:
+            # runner.py:772-773: one draw of 32^3 voxels per term, densities first (every data-parallel rank draws the same ones from
+            # the same seed, so the averaged gradient is the single-process one)
+            tv_terms.append([float("nan"), float("nan")])
+            if args.voxel_tv_sigma > 0:
+                tv = nerf.total_variation(model.nerf.densities)
+                tv_terms[-1][0] = tv.detach()
+                loss = loss + args.voxel_tv_sigma * tv
+            if args.voxel_tv_rgb > 0:
+                tv = nerf.total_variation(model.nerf.rgb)
+                tv_terms[-1][1] = tv.detach()
+                loss = loss + args.voxel_tv_rgb * tv
         if args.opt_step != 1:
             loss = loss / args.opt_step
         loss.backward()
@@ -392,6 +466,7 @@ def fit(args, device="cuda", replay_reference_rng=False, init=None, on_iter=None
             labels = tuple(l[:args.train_imgs] for l in labels) if is_dyn else labels[:args.train_imgs]
             cam = cam[:args.train_imgs]
         model.nerf.steps, model.nerf.t_near, model.nerf.t_far = args.steps, args.near, args.far  # set_per_run :1048-1050
+        unset_voxel_tv(args, model)
         opt = load_optim(args, model.parameters())
         sched = None if args.no_sched else torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=args.epochs,
                                                                                        eta_min=args.sched_min)
@@ -403,5 +478,6 @@ def fit(args, device="cuda", replay_reference_rng=False, init=None, on_iter=None
     if args.test_white_bg:
         model.set_bg("white")
     psnrs, gots = test(model, test_cam, test_labels, args)
-    return dict(model=model, losses=losses, reg_terms=list(getattr(train, "last_reg_terms", [])), test_psnr=psnrs, test_psnr_mean=float(np.mean(psnrs)), frames=gots,
+    return dict(model=model, losses=losses, reg_terms=list(getattr(train, "last_reg_terms", [])),
+                tv_terms=[[float(v) for v in row] for row in getattr(train, "last_tv_terms", [])],test_psnr=psnrs, test_psnr_mean=float(np.mean(psnrs)), frames=gots,
                 test_labels=test_labels, rank=rank, world=world)

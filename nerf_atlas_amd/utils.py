@@ -120,6 +120,7 @@ class DeviceRandom:
 
     def rand(self, shape, device): return torch.rand(shape, device=device)
     def randn(self, shape, device): return torch.randn(shape, device=device)
+    def randint(self, low, high, shape, device): return torch.randint(low, high, shape, device=device)
 
 
 class ReferenceStreamRandom:
@@ -130,6 +131,7 @@ class ReferenceStreamRandom:
 
     def rand(self, shape, device): return torch.rand(shape).to(device)
     def randn(self, shape, device): return torch.randn(shape).to(device)
+    def randint(self, low, high, shape, device): return torch.randint(low, high, shape).to(device)
 
 
 random_source = DeviceRandom()
@@ -143,6 +145,7 @@ def set_random_source(src):
 
 def rand(shape, device): return random_source.rand(tuple(shape), device)
 def randn(shape, device): return random_source.randn(tuple(shape), device)
+def randint(low, high, shape, device): return random_source.randint(int(low), int(high), tuple(shape), device)
 
 
 PACK_CACHE_ATTRS = ("_packed", "_packed_ls", "_packed_mip_ls", "_packed_view_ls", "_packed_siren_ls", "_packed_fourier_ls", "_packed_front",

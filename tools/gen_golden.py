@@ -1077,9 +1077,42 @@ def g23():
         save(f"g23_voxel_{name}", **kw)
 
 
+GRID_TV_CASES = {
+    # name: (grid shape, samples, seed of the grid's proc_uniform values, torch seed of the draw)
+    "462x5": ((4, 6, 2, 5), 257, 5501, 11),    # non-cubic: pins x = idx % s0 against the memory order
+    "6x3": ((6, 6, 6, 3), 1000, 5502, 12),     # more samples than voxels: duplicates
+    "8x1": ((8, 8, 8, 1), 64, 5503, 13),
+}
+
+
+def g24():
+    """g24_grid_tv_<case>: the reference's total_variation (src/nerf.py:381-399) on a grid of proc_uniform values in +-1 (regenerated by
+    the tests from `grid_seed`): the indices it drew (the seed replayed through the same torch.randint call, checked against its
+    random_sample_grid), its fp32 value, and its value and gradient on the `.double()` grid.  Data only."""
+    for name, (shape, n, grid_seed, seed) in GRID_TV_CASES.items():
+        grid = torch.from_numpy(proc_uniform(shape, grid_seed, 1.0))
+        n_elem = shape[0] * shape[1] * shape[2]
+        torch.manual_seed(seed)
+        value = rnerf.total_variation(grid, n)
+        torch.manual_seed(seed)
+        idxs = torch.randint(0, n_elem, (n,))
+        torch.manual_seed(seed)
+        x, y, z = rnerf.random_sample_grid(grid, n)
+        assert torch.equal(x, idxs % shape[0]) and torch.equal(z, idxs // (shape[0] * shape[1]) % shape[2]) and idxs.dtype == torch.int64
+        with torch.enable_grad():
+            g64 = grid.double().requires_grad_(True)
+            torch.manual_seed(seed)
+            value64 = rnerf.total_variation(g64, n)
+            value64.backward()
+        assert value.dtype == torch.float32 and value64.dtype == torch.float64
+        print(f"g24 {name}: value {float(value):.7f} (fp32) {float(value64):.12f} (fp64), {len(set(idxs.tolist()))} distinct of {n} indices")
+        save(f"g24_grid_tv_{name}", shape=np.array(shape), samples=n, grid_seed=grid_seed, seed=seed, idxs=idxs, value=value,
+             value64=value64, grad64=g64.grad)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24"]
     for g in which:
         globals()[g]()
     with open(os.path.join(OUT, "PROVENANCE.txt"), "w") as f:

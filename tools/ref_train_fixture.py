@@ -55,6 +55,13 @@ RECIPES = {
     # `--model voxel` as shipped (runner.py:1048 reads model.nerf.steps, NeRFVoxel has no `nerf`): the load_model hook below installs
     # the property and everything else is runner.main.  Recorded with --epochs 200 --size 32 --crop-size 16 --steps 32 --batch-size 4
     "voxel": (False, ["--model", "voxel", "--refl-kind", "pos", "--loss-fns", "l2", "-lr", "5e-2"]),
+    # the `voxel` recipe plus both total-variation terms (runner.py:289-295, 772-773: two draws of 32^3 voxel indices per iteration
+    # from torch's stream, densities first).  Recorded with the `voxel` recipe's flags; the fixture also carries that recipe's
+    # trajectory (`losses_without_tv`, copied from train_parity_voxel.json after checking that the two argv differ in the two weights
+    # only) and the two TV values of every iteration (`tv_terms`).  The weights are chosen so that the two trajectories separate by ten
+    # times the parity bar (2e-3) within the first 50 iterations: the fixture then pins the terms, not only the stream position.
+    "voxel_tv": (False, ["--model", "voxel", "--refl-kind", "pos", "--loss-fns", "l2", "-lr", "5e-2", "--voxel-tv-sigma", "0.02",
+                         "--voxel-tv-rgb", "0.02"]),
     "dnerf": (True, ["--model", "plain", "--refl-kind", "view", "--data-kind", "dnerf", "--dyn-model", "plain",
                      "--spline", "4"]),
     # `make dnerf`'s regularisers (reference makefile:106-114) on the small scene: NR-NeRF offset decay + the FFJORD
@@ -168,6 +175,13 @@ def main():
         captured.setdefault("reg_terms", []).append(float(v.mean().detach()))
         return v
     rutils.divergence = divergence
+    real_tv = rnerf.total_variation
+
+    def total_variation(grid, samples=32 ** 3):  # (the two --voxel-tv-* terms per iteration, densities then rgb)
+        v = real_tv(grid, samples)
+        captured.setdefault("tv_terms", []).append(float(v.detach()))
+        return v
+    rnerf.total_variation = total_variation
     runner.save_losses = lambda args, losses: captured.__setitem__("losses", list(losses))
     real_load_model = runner.load_model
 
@@ -209,6 +223,16 @@ def main():
         test_psnr=psnrs, test_psnr_mean=mean, reg_terms=captured.get("reg_terms", []),
         torch=torch.__version__, threads=cfg.threads, wall_s=round(dt, 1),
     )
+    if cfg.name == "voxel_tv":
+        tv = captured["tv_terms"]
+        fixture["tv_terms"] = [tv[i:i + 2] for i in range(0, len(tv), 2)]
+        with open(os.path.join(REPO, "tests", "golden", "train_parity_voxel.json")) as f:
+            base = json.load(f)
+        drop = lambda av: [x for i, x in enumerate(av) if not (x.startswith("--voxel-tv-") or (i and av[i - 1].startswith("--voxel-tv-")))]
+        assert drop(fixture["argv"]) == base["argv"] and base["seed"] == cfg.seed, "record voxel_tv with the flags of the voxel fixture"
+        fixture["losses_without_tv"] = base["losses"]
+        sep = np.abs(np.array(fixture["losses"][:50]) - np.array(base["losses"][:50])).max()
+        print(f"voxel_tv: the trajectories with and without the terms separate by {sep:.2e} within the first 50 iterations")
     path = cfg.out or os.path.join(REPO, "tests", "golden", f"train_parity_{cfg.name}.json")
     with open(path, "w") as f:
         json.dump(fixture, f, indent=1)
