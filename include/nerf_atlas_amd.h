@@ -453,6 +453,23 @@ int na_fourier_encode_backward_input_saved(const float* x, int64_t N, int D, con
 int na_adam_step(int n, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                  const int64_t* numel, double one_minus_beta1, double beta2, double one_minus_beta2, double bias_correction2_sqrt,
                  double eps, double neg_step_size, int fma_mask, void* stream);
+/* The optimiser table of runner.py:440-458 (optim.SGD / RMSprop / Adam with --decay / AdamW as the reference builds them: no momentum,
+ * not centered, no amsgrad) the same way: n tensors by ONE launch per 48 non-empty tensors, per element torch's foreach operations in
+ * torch's order, each rounded like the ATen kernel rounds it (nerf_atlas_amd/csrc/optim.hip lists them).  params / grads / state0 /
+ * state1: HOST arrays of n device pointers (state0: square_avg or exp_avg, state1: exp_avg_sq; NULL where the rule has no such
+ * state), numel[n]; an empty tensor is skipped.  The gradients are never written.  scalars[n_scalars], doubles as torch's Python
+ * computes them, rounded to float here:
+ *   NA_OPTIM_SGD      1: -lr
+ *   NA_OPTIM_RMSPROP  4: alpha, 1 - alpha, eps, -lr
+ *   NA_OPTIM_ADAM     7: 1 - beta1, beta2, 1 - beta2, sqrt(1 - beta2^t), eps, -lr / (1 - beta1^t), weight_decay (0: none)
+ *   NA_OPTIM_ADAMW    7: the same six, then 1 - lr * weight_decay (1: none)
+ * fma_mask: which multiply-adds ATen contracts -- bit 0 lerp, bit 1 addcmul, bit 2 addcdiv, bit 3 add(alpha) (SGD's update, Adam's
+ * coupled decay); nerf_atlas_amd/train.py holds the values pinned against torch bit for bit.  The whole list is validated before
+ * the first launch. */
+enum { NA_OPTIM_SGD = 0, NA_OPTIM_RMSPROP = 1, NA_OPTIM_ADAM = 2, NA_OPTIM_ADAMW = 3 };
+enum { NA_OPTIM_MAX_SCALARS = 7 };
+int na_optim_step(int rule, int n, float* const* params, const float* const* grads, float* const* state0, float* const* state1,
+                  const int64_t* numel, const double* scalars, int n_scalars, int fma_mask, void* stream);
 /* Forward-mode derivative of the hash features along a per-point direction e (the deformation network's input
  * Jacobian-vector product that the FFJORD divergence estimate needs: runner.py:697-700, src/utils.py:467-478;
  * src/neural_blocks.py:166-190 is what is differentiated).

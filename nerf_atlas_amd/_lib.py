@@ -50,6 +50,8 @@ SIGNATURES = {
     "na_plain_head_rows_backward": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, c_f32p, c_f32p, C.c_void_p]),
     "na_adam_step": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "na_optim_step": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                C.c_void_p]),
     "na_sigmoid": (C.c_int, [c_f32p, c_i64, C.c_int, c_f32p, C.c_void_p]),
     "na_mip_encode": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int, C.c_float, C.c_int,
                                 C.c_int, c_f32p, C.c_void_p]),

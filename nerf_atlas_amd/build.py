@@ -39,6 +39,7 @@ UNITS = [
     ("composite_rayts.hip", [], ""),
     ("voxel.hip", [], ""),
     ("grid_ops.hip", [], ""),
+    ("optim.hip", [], ""),
     ("backward.hip", [], ""),
     ("train_gemm.hip", [], ""),
     ("train_bwd.hip", [], ""),

@@ -783,17 +783,60 @@ def train_reduce_many(entries):
 def adam_step(params, grads, exp_avgs, exp_avg_sqs, one_minus_beta1: float, beta2: float, one_minus_beta2: float,
               bias_correction2_sqrt: float, eps: float, neg_step_size: float, fma_mask: int):
     """torch's foreach Adam update of every tensor by ONE launch (na_adam_step): lists of contiguous fp32 device tensors."""
+    optim_check("adam", params, grads, exp_avgs, exp_avg_sqs)
     lib = _lib.load()
     n = len(params)
     if n == 0:
         return
-    for t in (*params, *grads, *exp_avgs, *exp_avg_sqs):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise ValueError("adam_step: contiguous fp32 device tensors only")
     vp, ip = C.c_void_p * n, C.c_int64 * n
     check(lib.na_adam_step(n, vp(*[t.data_ptr() for t in params]), vp(*[t.data_ptr() for t in grads]), vp(*[t.data_ptr() for t in exp_avgs]),
                            vp(*[t.data_ptr() for t in exp_avg_sqs]), ip(*[t.numel() for t in params]), float(one_minus_beta1), float(beta2),
                            float(one_minus_beta2), float(bias_correction2_sqrt), float(eps), float(neg_step_size), int(fma_mask), _stream()))
+
+
+OPTIM_RULES = {"sgd": 0, "rmsprop": 1, "adam": 2, "adamw": 3}   # include/nerf_atlas_amd.h NA_OPTIM_*
+_OPTIM_STATES = {"sgd": 0, "rmsprop": 1, "adam": 2, "adamw": 2}
+_OPTIM_SCALARS = {"sgd": 1, "rmsprop": 4, "adam": 7, "adamw": 7}
+
+
+def optim_check(rule: str, params, grads, state0=(), state1=(), known: int = 0):
+    """The argument checks of optim_step (and adam_step) on their own, for a caller that must know the call will be taken before it
+    changes anything: every list as long as `params` (an unused state list empty), contiguous fp32 device tensors, the shapes of a
+    slot equal.  known: the first `known` lists are already known to hold contiguous fp32 device tensors (the host time of a step is
+    part of its price); their shapes are still compared.  Raises ValueError."""
+    if rule not in OPTIM_RULES:
+        raise ValueError(f"optim_step: unknown update rule {rule!r} (one of {sorted(OPTIM_RULES)})")
+    lists = (params, grads, state0, state1)[:2 + _OPTIM_STATES[rule]]
+    if any(len(l) != len(params) for l in lists) or any(len(l) for l in (state0, state1)[_OPTIM_STATES[rule]:]):
+        raise ValueError(f"optim_step: rule {rule!r} takes params, grads and {_OPTIM_STATES[rule]} state lists of one length")
+    f32 = torch.float32
+    for slot in zip(*lists):
+        shape = slot[0].shape if isinstance(slot[0], torch.Tensor) else None
+        for t in slot[known:]:
+            if not (isinstance(t, torch.Tensor) and not t.is_sparse and t.is_cuda and t.dtype is f32 and t.is_contiguous()):
+                raise ValueError("optim_step: contiguous fp32 device tensors only")
+        for t in slot[1:]:
+            if t.shape != shape:
+                raise ValueError(f"optim_step: the tensors of a slot differ in shape ({tuple(t.shape)} vs {tuple(slot[0].shape)})")
+
+
+def optim_step(rule: str, params, grads, state0, state1, scalars, fma_mask: int, checked: bool = False):
+    """One optimiser step of every tensor by ONE launch per 48 non-empty tensors (na_optim_step; csrc/optim.hip): `rule` "sgd" /
+    "rmsprop" / "adam" / "adamw", lists of contiguous fp32 device tensors (state0: square_avg or exp_avg, state1: exp_avg_sq; empty
+    where the rule has none), the rule's scalars in the header's order as the doubles torch's Python computes.  The gradients are
+    not written.  checked: optim_check has already passed on these lists."""
+    if not checked:
+        optim_check(rule, params, grads, state0, state1)
+    lib = _lib.load()
+    if len(scalars) != _OPTIM_SCALARS[rule]:
+        raise ValueError(f"optim_step: rule {rule!r} takes {_OPTIM_SCALARS[rule]} scalars, got {len(scalars)}")
+    n = len(params)
+    if n == 0:
+        return
+    vp, ip, dp = C.c_void_p * n, C.c_int64 * n, C.c_double * len(scalars)
+    ptrs = lambda ts: vp(*[t.data_ptr() for t in ts]) if len(ts) else None
+    check(lib.na_optim_step(OPTIM_RULES[rule], n, ptrs(params), ptrs(grads), ptrs(state0), ptrs(state1), ip(*[t.numel() for t in params]),
+                            dp(*[float(s) for s in scalars]), len(scalars), int(fma_mask), _stream()))
 
 
 def linear_wgrad_cols(x: torch.Tensor, dY: torch.Tensor, pre_act: str, dW: torch.Tensor, col0: int):

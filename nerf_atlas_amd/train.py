@@ -7,9 +7,9 @@ tangents through the MLP), `--smooth-normals` in the reference's default epsilon
 (forward-mode divergence estimate), `--voxel-tv-sigma` / `--voxel-tv-rgb` (total variation of NeRFVoxel's grids) and this build's
 `--voxel-upsample ITER:RESO`; `--smooth-normals --smooth-eps 0` (double backward) raises.
 
-Every forward and backward is a HIP kernel (nerf_atlas_amd/autograd.py); torch.optim owns the parameter update, like
-in the reference.  With `replay_reference_rng=True` the stochastic tensors come from torch's CPU generator in the
-reference's order, so a run is comparable with the reference's iteration by iteration (tests/test_gpu_train.py
+Every forward and backward is a HIP kernel (nerf_atlas_amd/autograd.py); the parameter update is the reference's table of torch.optim
+classes (`--opt-kind adam | sgd | adamw | rmsprop`, `--decay`), each with its step as one HIP launch (load_optim below).
+With `replay_reference_rng=True` the stochastic tensors come from torch's CPU generator in the reference's order, so a run is comparable with the reference's iteration by iteration (tests/test_gpu_train.py
 against tests/golden/train_parity_*.json).
 """
 import argparse
@@ -21,6 +21,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 import torch.nn.functional as F
+from torch.optim.optimizer import _get_scalar_dtype
 
 from . import autograd as ag
 from . import dist as na_dist
@@ -156,13 +157,57 @@ def load_loss_fn(args):
     return lambda x, ref: sum(fn(x, ref) for fn in fns) / len(fns)
 
 
-class NaAdam(torch.optim.Adam):
-    """torch.optim.Adam whose step is ONE kernel (na_adam_step) for the parameter groups it fits: fp32 contiguous device tensors with
-    dense gradients, no amsgrad / maximize / weight decay / capturable / differentiable -- per element exactly the operations of
-    torch's foreach implementation (torch/optim/adam.py::_multi_tensor_adam) in its order, each rounded like the ATen kernel rounds it
-    (FMA_MASK: which multiply-adds ATen contracts).  Same state (`step`, `exp_avg`, `exp_avg_sq`): state_dicts interchange with
-    torch.optim.Adam.  Any other group takes torch's own step."""
-    FMA_MASK = 7
+class _OneLaunchStep:
+    """In front of a torch.optim class: its step as ONE kernel (na_optim_step, csrc/optim.hip) for the parameter groups the kernel fits
+    -- fp32 contiguous device tensors with dense gradients and the plain form of the rule (`_fits`) -- per element exactly the
+    operations of torch's foreach implementation (torch/optim/*.py::_multi_tensor_*) in its order, each rounded like the ATen kernel
+    rounds it (FMA_MASK: which multiply-adds ATen contracts; bit 0 lerp, 1 addcmul, 2 addcdiv, 3 add(alpha); tools/optim_probe.py).
+    Same state keys, same state_dict: interchangeable with the torch class in both directions.  Any other group takes torch's own step
+    for that group (the unhooked one: step hooks fire once per step)."""
+    RULE = None       # ops.OPTIM_RULES
+    TORCH = None      # the torch class whose step a group that does not fit takes
+    STATE = ()        # the state tensors the kernel updates, in its order
+    FMA_MASK = 0
+
+    def _fits(self, group) -> bool:
+        raise NotImplementedError
+
+    def _launches(self, group, steps):
+        """[(indices into the group's parameters with a gradient or None for all, rule, scalars, mask)]: one entry per launch, the
+        scalars as torch's Python computes them; steps: the step count of every such parameter (None for a rule without state)"""
+        raise NotImplementedError
+
+    @staticmethod
+    def _common_fit(group) -> bool:
+        return (not group.get("maximize") and not group.get("capturable") and not group.get("differentiable") and not group.get("fused")
+                and not isinstance(group["lr"], torch.Tensor))
+
+    @staticmethod
+    def _tensors_fit(ps, grads) -> bool:
+        f32 = torch.float32
+        for p, g in zip(ps, grads):
+            if not (p.is_cuda and g.is_cuda and p.dtype is f32 and g.dtype is f32 and not p.is_sparse and not g.is_sparse
+                    and p.is_contiguous() and g.is_contiguous()):
+                return False
+        return True
+
+    def _count_steps(self, group, ps):
+        """step += 1 for every parameter of the group, as ONE host operation where nothing changed since the last step: the step
+        counts of the parameters that step together are 0-dim views of one host tensor (each still the `step` of torch's state: a
+        0-dim tensor of torch's scalar dtype on the host).  Anything else -- a new parameter, a loaded state_dict, a step torch took
+        -- is seen by identity, and the counts are gathered into a new tensor.  Returns the counts as floats."""
+        cache = self.__dict__.setdefault("_na_steps", {})
+        hit = cache.get(id(group))
+        if hit is not None and len(hit[1]) == len(ps) and all(self.state[p]["step"] is v for p, v in zip(ps, hit[1])):
+            buf = hit[0]
+        else:
+            buf = torch.tensor([float(self.state[p]["step"]) for p in ps], dtype=_get_scalar_dtype())
+            views = buf.unbind(0)
+            for p, v in zip(ps, views):
+                self.state[p]["step"] = v
+            cache[id(group)] = (buf, views)
+        buf += 1
+        return buf.tolist()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -172,61 +217,137 @@ class NaAdam(torch.optim.Adam):
             with torch.enable_grad():
                 loss = closure()
         for group in self.param_groups:
-            ps = [p for p in group["params"] if p.grad is not None]
-            ok = (not group.get("amsgrad") and not group.get("maximize") and group.get("weight_decay", 0) == 0
-                  and not group.get("capturable") and not group.get("differentiable") and not group.get("fused")
-                  and not isinstance(group["lr"], torch.Tensor)
-                  and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and not p.grad.is_sparse
-                          and p.grad.dtype == torch.float32 and p.grad.is_contiguous() for p in ps))
-            if not ok or not ps:
+            ps, grads = [], []
+            for p in group["params"]:
+                g = p.grad
+                if g is not None:
+                    ps.append(p)
+                    grads.append(g)
+            if not ps or not self._fits(group) or not self._tensors_fit(ps, grads):
                 self._torch_group_step(group)
                 continue
-            beta1, beta2 = group["betas"]
-            exp_avgs, exp_avg_sqs, steps = [], [], []
-            for p in ps:
-                st = self.state[p]
-                if len(st) == 0:  # (torch.optim.Adam._init_group's state)
-                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1
-                steps.append(float(st["step"]))
-                exp_avgs.append(st["exp_avg"])
-                exp_avg_sqs.append(st["exp_avg_sq"])
-            # one launch per distinct step count (parameters that joined later): the scalars as torch's Python computes them
-            for t in sorted(set(steps)):
-                idx = [i for i, s in enumerate(steps) if s == t]
-                bc1, bc2 = 1 - beta1 ** t, 1 - beta2 ** t
-                ops.adam_step([ps[i] for i in idx], [ps[i].grad for i in idx], [exp_avgs[i] for i in idx], [exp_avg_sqs[i] for i in idx],
-                              1 - beta1, beta2, 1 - beta2, bc2 ** 0.5, group["eps"], (group["lr"] / bc1) * -1, self.FMA_MASK)
-            # the kernel wrote the parameters through raw pointers: tell torch (an in-place update, like torch.optim.Adam's own) -- the
+            # every tensor is validated BEFORE any state is created or counted: a refused call leaves the optimiser as it was (a state
+            # that does not exist yet will be zeros_like(p): p stands in for it; the gate above has looked at ps and grads)
+            steps = None
+            if self.STATE:   # (a rule without state tensors keeps no state at all, like torch's SGD, and has nothing left to validate)
+                have = [self.state.get(p) for p in ps]
+                ops.optim_check(self.RULE, ps, grads, *[[st[k] if st else p for p, st in zip(ps, have)] for k in self.STATE], known=2)
+                for p, st in zip(ps, have):
+                    if not st:  # (the torch class's _init_group)
+                        st = self.state[p]
+                        st["step"] = torch.tensor(0.0, dtype=_get_scalar_dtype())
+                        for k in self.STATE:
+                            st[k] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                steps = self._count_steps(group, ps)
+            state = [[self.state[p][k] for p in ps] for k in self.STATE] + [[], []]
+            for idx, rule, scalars, mask in self._launches(group, steps):
+                pick = (lambda l: l) if idx is None else (lambda l: [l[i] for i in idx] if l else l)
+                ops.optim_step(rule, pick(ps), pick(grads), pick(state[0]), pick(state[1]), scalars, mask, checked=True)
+            # the kernel wrote the parameters through raw pointers: tell torch (an in-place update, like the torch class's own) -- the
             # packed weight streams of the fused renderers are keyed on the version counters (utils.pack_stamp) and a validation render
             # between two training steps would otherwise keep the weights of its first call
             torch.autograd.graph.increment_version(ps)
         return loss
 
     def _torch_group_step(self, group):
-        """torch.optim.Adam.step for ONE group (a group the kernel does not fit)"""
+        """the torch class's step for ONE group (a group the kernel does not fit).  This runs inside the hooked step of this class: the
+        torch class's own hook wrapper, where it has one, is taken off so that the step hooks fire once."""
+        fn = self.TORCH.step
+        if getattr(fn, "hooked", False):
+            fn = fn.__wrapped__
         keep = self.param_groups
         try:
             self.param_groups = [group]
-            torch.optim.Adam.step(self)
+            fn(self)
         finally:
             self.param_groups = keep
 
 
+class NaSGD(_OneLaunchStep, torch.optim.SGD):
+    """torch.optim.SGD without momentum, dampening, nesterov and weight decay: p = p + (-lr) g.  No state."""
+    RULE, TORCH, STATE, FMA_MASK = "sgd", torch.optim.SGD, (), 8
+
+    def _fits(self, group):
+        return (self._common_fit(group) and group["momentum"] == 0 and group["dampening"] == 0 and not group["nesterov"]
+                and group["weight_decay"] == 0)
+
+    def _launches(self, group, steps):
+        return [(None, "sgd", [-group["lr"]], self.FMA_MASK)]
+
+
+class NaRMSprop(_OneLaunchStep, torch.optim.RMSprop):
+    """torch.optim.RMSprop, not centered, without momentum and weight decay.  State: `step`, `square_avg`."""
+    RULE, TORCH, STATE, FMA_MASK = "rmsprop", torch.optim.RMSprop, ("square_avg",), 6
+
+    def _fits(self, group):
+        return self._common_fit(group) and group["momentum"] == 0 and not group["centered"] and group["weight_decay"] == 0
+
+    def _launches(self, group, steps):
+        alpha = group["alpha"]
+        return [(None, "rmsprop", [alpha, 1 - alpha, group["eps"], -group["lr"]], self.FMA_MASK)]
+
+
+class NaAdam(_OneLaunchStep, torch.optim.Adam):
+    """torch.optim.Adam without amsgrad, with either form of weight decay (coupled: g + wd p in front of the update, the gradient tensor
+    itself untouched; `decoupled_weight_decay`: p (1 - lr wd) in front of it).  State: `step`, `exp_avg`, `exp_avg_sq`.  FMA_MASK holds
+    the three contractions of the update proper, DECAY_FMA the coupled decay's."""
+    RULE, TORCH, STATE, FMA_MASK = "adam", torch.optim.Adam, ("exp_avg", "exp_avg_sq"), 7
+    DECAY_FMA = 8
+
+    def _fits(self, group):
+        beta1, beta2 = group["betas"]
+        # (1 - beta1 >= 0.5: ATen's lerp evaluates its other branch, b - (b - a)(1 - w), which the kernel does not)
+        return (self._common_fit(group) and not group.get("amsgrad") and not isinstance(beta1, torch.Tensor)
+                and not isinstance(beta2, torch.Tensor) and 1 - beta1 < 0.5)
+
+    def _launches(self, group, steps):
+        beta1, beta2 = group["betas"]
+        lr, wd = group["lr"], group.get("weight_decay", 0)
+        decoupled = bool(group.get("decoupled_weight_decay"))
+        decay = (1 - lr * wd if wd != 0 else 1.0) if decoupled else wd
+        out = []
+        # one launch per distinct step count (parameters that joined later)
+        counts = sorted(set(steps))
+        for t in counts:
+            bc1, bc2 = 1 - beta1 ** t, 1 - beta2 ** t
+            out.append((None if len(counts) == 1 else [i for i, s in enumerate(steps) if s == t], "adamw" if decoupled else "adam",
+                        [1 - beta1, beta2, 1 - beta2, bc2 ** 0.5, group["eps"], (lr / bc1) * -1, decay], self.FMA_MASK | self.DECAY_FMA))
+        return out
+
+
+class NaAdamW(NaAdam, torch.optim.AdamW):
+    """torch.optim.AdamW (torch.optim.Adam with decoupled_weight_decay=True and the default decay 1e-2)."""
+    TORCH = torch.optim.AdamW
+
+
+OPT_KINDS = {  # runner.py:440-447: --opt-kind -> (this build's class, torch's)
+    "adam": (NaAdam, torch.optim.Adam),
+    "sgd": (NaSGD, torch.optim.SGD),
+    "adamw": (NaAdamW, torch.optim.AdamW),
+    "rmsprop": (NaRMSprop, torch.optim.RMSprop),
+}
+
+
 def load_optim(args, params):
-    """runner.py:448-458."""
-    if args.opt_kind != "adam":
-        raise NotImplementedError(f"opt kind {args.opt_kind}")
-    params = list(params)
-    # torch.optim.Adam's update (runner.py:448-458) as ONE launch where every parameter lives on the GPU (NaAdam below: the foreach
-    # form's operations, order and rounding -- bit for bit the same trajectory, tests/test_gpu_train.py); NA_ADAM=torch keeps
-    # torch's own seven launches.  (torch's `fused=True` is NOT used: its update rounds differently and the `--dyn-diverge-decay`
-    # recipe, whose end point measures accumulation precision, leaves the reference's basin with it --
+    """runner.py:440-458: lr for every kind, eps 1e-7 except for sgd, --decay as Adam's (coupled) weight decay only."""
+    if args.opt_kind == "uniform_adam":
+        raise NotImplementedError("opt kind uniform_adam: the reference's UniformAdam (src/opt.py) is a dense cdist + solve per parameter, "
+                                  "an experiment outside the training hot path")
+    if args.opt_kind not in OPT_KINDS:
+        raise NotImplementedError(f"unknown opt kind {args.opt_kind}")
+    # torch's update as ONE launch where every parameter lives on the GPU (the classes above: the foreach form's operations, order and
+    # rounding -- bit for bit the same trajectory, tests/test_gpu_train.py, tests/test_gpu_optim.py); NA_OPTIM=torch keeps torch's own
+    # classes for every kind, NA_ADAM=torch for adam.  (torch's `fused=True` is NOT used: its update rounds differently and the
+    # `--dyn-diverge-decay` recipe, whose end point measures accumulation precision, leaves the reference's basin with it --
     # profiles/r06/adam_fused_dnerf_div.log.)
-    cls = NaAdam if os.environ.get("NA_ADAM") != "torch" else torch.optim.Adam
-    return cls(params, lr=args.learning_rate, eps=1e-7, weight_decay=args.decay)
+    use_torch = os.environ.get("NA_OPTIM") == "torch" or (args.opt_kind == "adam" and os.environ.get("NA_ADAM") == "torch")
+    cls = OPT_KINDS[args.opt_kind][1 if use_torch else 0]
+    hyper = dict(lr=args.learning_rate, eps=1e-7)
+    if args.opt_kind == "adam":
+        hyper["weight_decay"] = args.decay
+    if args.opt_kind == "sgd":
+        del hyper["eps"]
+    return cls(list(params), **hyper)
 
 
 def offset_decay_term(model, curr_percent: float):

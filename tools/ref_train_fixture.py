@@ -62,6 +62,12 @@ RECIPES = {
     # times the parity bar (2e-3) within the first 50 iterations: the fixture then pins the terms, not only the stream position.
     "voxel_tv": (False, ["--model", "voxel", "--refl-kind", "pos", "--loss-fns", "l2", "-lr", "5e-2", "--voxel-tv-sigma", "0.02",
                          "--voxel-tv-rgb", "0.02"]),
+    # the `voxel` recipe under the other optimisers of the reference's table (runner.py:440-458: --opt-kind rmsprop / adamw / sgd; eps
+    # 1e-7, AdamW with torch's default decay 1e-2).  Recorded with the `voxel` recipe's flags.  Each kind at a rate at which it learns on
+    # this scene in 200 iterations: SGD at rates 1 .. 500 does not leave the start (the l2 gradient of a voxel is ~1e-6).
+    "voxel_rmsprop": (False, ["--model", "voxel", "--refl-kind", "pos", "--loss-fns", "l2", "--opt-kind", "rmsprop", "-lr", "2e-2"]),
+    "voxel_adamw": (False, ["--model", "voxel", "--refl-kind", "pos", "--loss-fns", "l2", "--opt-kind", "adamw", "-lr", "5e-2"]),
+    "voxel_sgd": (False, ["--model", "voxel", "--refl-kind", "pos", "--loss-fns", "l2", "--opt-kind", "sgd", "-lr", "5000"]),
     "dnerf": (True, ["--model", "plain", "--refl-kind", "view", "--data-kind", "dnerf", "--dyn-model", "plain",
                      "--spline", "4"]),
     # `make dnerf`'s regularisers (reference makefile:106-114) on the small scene: NR-NeRF offset decay + the FFJORD

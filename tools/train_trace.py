@@ -10,7 +10,7 @@ import sys
 
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-idx = [i for i, r in enumerate(rows) if "adam_many" in r["Kernel_Name"]]
+idx = [i for i, r in enumerate(rows) if "optim_many" in r["Kernel_Name"]]
 a, b = idx[-2] + 1, idx[-1] + 1
 t0 = int(rows[a]["Start_Timestamp"])
 tot = 0.0
