@@ -354,6 +354,7 @@ int na_set_deterministic(void* workspace, size_t bytes);
  * na_mul_bcast          out[j,i] = a[i] * b[j,i], a [n], b/out [J,n]: one multiplier row shared by J tangent rows.
  * na_mul_reduce         out[i] = sum_j g[j,i] * b[j,i] (gradient of na_mul_bcast w.r.t. a).
  * na_eikonal_loss       loss[0] += mean_n (|normals[:,n]| - 1)^2, normals [3,N] tangent-major; loss zeroed by caller.
+ *                       N == 0: loss[0] = NaN, the mean of nothing (torch's); the backward writes nothing.
  * na_eikonal_loss_backward  g_normals [3,N] = g[0] * d loss / d normals.                                          */
 int na_act_deriv(const float* x, int64_t n, int act, int order, float* out, void* stream);
 int na_mul_bcast(const float* a, const float* b, int64_t n, int J, float* out, void* stream);

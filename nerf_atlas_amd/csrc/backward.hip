@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256) void laplace_density_backward_kernel(const flo
     const float s = -v / sc;
     const float e = expf(-fabsf(s)) * 0.5f;
     const float cdf = s <= 0.f ? e : 1.f - e;
-    g_sdf[i] = -gi * e * r2;
+    g_sdf[i] = v != v ? 0.f : -gi * e * r2;  // (torch: the clamps of laplace_cdf pass no gradient where their comparison fails, a NaN included)
     acc += gi * (e * v * r2 * r - cdf * r2);
   }
   if (g_beta == nullptr) return;
@@ -762,8 +762,13 @@ int na_mul_reduce(const float* g, const float* b, int64_t n, int J, float* out, 
 }
 
 int na_eikonal_loss(const float* normals, int64_t N, float* loss, void* stream) {
-  NA_REQUIRE(normals && loss, NA_ENULL, "na_eikonal_loss: null pointer");
-  NA_REQUIRE(N > 0, NA_EINVAL, "na_eikonal_loss: N=%lld", (long long)N);
+  NA_REQUIRE(N >= 0, NA_EINVAL, "na_eikonal_loss: N=%lld", (long long)N);
+  NA_REQUIRE(loss, NA_ENULL, "na_eikonal_loss: null pointer");
+  if (N == 0) {  // the mean of nothing is NaN, as torch's (all bits set is a quiet NaN); zero-size normals carry a null pointer
+    (void)hipMemsetAsync(loss, 0xFF, sizeof(float), (hipStream_t)stream);
+    return check_launch("na_eikonal_loss");
+  }
+  NA_REQUIRE(normals, NA_ENULL, "na_eikonal_loss: null pointer");
   int rc;
   long long* fix = det_begin(1, (hipStream_t)stream, "na_eikonal_loss", &rc);
   if (rc != NA_OK) return rc;
@@ -774,8 +779,9 @@ int na_eikonal_loss(const float* normals, int64_t N, float* loss, void* stream) 
 }
 
 int na_eikonal_loss_backward(const float* normals, int64_t N, const float* g, float* g_normals, void* stream) {
+  NA_REQUIRE(N >= 0, NA_EINVAL, "na_eikonal_loss_backward: N=%lld", (long long)N);
+  if (N == 0) return NA_OK;  // empty: nothing to write, zero-size tensors carry null pointers
   NA_REQUIRE(normals && g && g_normals, NA_ENULL, "na_eikonal_loss_backward: null pointer");
-  NA_REQUIRE(N > 0, NA_EINVAL, "na_eikonal_loss_backward: N=%lld", (long long)N);
   hipLaunchKernelGGL(eikonal_backward_kernel, dim3(grid_for(N, 256, 4096)), dim3(256), 0, (hipStream_t)stream, normals, N, g,
                      1.0f / (float)N, g_normals);
   return check_launch("na_eikonal_loss_backward");

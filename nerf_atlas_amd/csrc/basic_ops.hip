@@ -530,7 +530,12 @@ __device__ __forceinline__ float laplace_density_of(float sdf, float sc, float i
   const float scaled = (-sdf) / sc;
   // (fast_exp: v_exp_f32 with the product's rounding error recovered, 2e-7 relative -- libm's expf made this elementwise
   // kernel ALU-bound at 30 % of the HBM rate)
-  const float cdf = scaled <= 0.f ? fast_exp(scaled) / 2.f : 1.f - fast_exp(-scaled) / 2.f;  // (no fminf / fmaxf: they drop a NaN distance)
+  // v_exp_f32 flushes a denormal result: fast_exp is 0 where its exponent x log2(e) (the very product it forms) is below -126, while
+  // exp(x) / 2 / beta may still be a normal number (beta 1e-3: 3e-36 at x = -88).  There -- and only there, every other result keeps
+  // its bits -- exp(x) = exp(x / 2)^2: the product rounds into the denormals like any fp32 product.
+  const bool deep = scaled * 1.4426950408889634f < -126.f;
+  const float ex = fast_exp(deep ? scaled * 0.5f : scaled);
+  const float cdf = scaled <= 0.f ? (deep ? ex * ex : ex) / 2.f : 1.f - fast_exp(-scaled) / 2.f;  // (no fminf / fmaxf: they drop a NaN distance)
   return inv * cdf;
 }
 __global__ void laplace_density_kernel(const float* __restrict__ sdf, int64_t N, const float* __restrict__ beta,
@@ -625,7 +630,8 @@ __global__ __launch_bounds__(256) void bezier_warp_kernel(const float* __restric
 __global__ void normalize3_kernel(const float* __restrict__ v, int64_t N, float* __restrict__ out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
     const float x = v[i * 3], y = v[i * 3 + 1], z = v[i * 3 + 2];
-    const float n = fmaxf(sqrtf((x * x + y * y) + z * z), 1e-12f);
+    const float len = sqrtf((x * x + y * y) + z * z);
+    const float n = len < 1e-12f ? 1e-12f : len;  // clamp_min(1e-12): a NaN norm stays and makes the whole row NaN (fmaxf drops it)
     out[i * 3] = x / n; out[i * 3 + 1] = y / n; out[i * 3 + 2] = z / n;
   }
 }
@@ -977,8 +983,9 @@ int na_integrate(const float* weights, const float* other, int T, int64_t R, int
 }
 
 int na_laplace_density(const float* sdf, int64_t N, const float* beta, float* density, void* stream) {
+  if (N == 0) return NA_OK;  // empty: zero-size tensors carry null pointers
+  NA_REQUIRE(N > 0, NA_EINVAL, "na_laplace_density: N=%lld", (long long)N);
   NA_REQUIRE(sdf && beta && density, NA_ENULL, "na_laplace_density: null pointer");
-  if (N <= 0) return N == 0 ? NA_OK : NA_EINVAL;
   hipLaunchKernelGGL(laplace_density_kernel, dim3(grid_for(N, 256, 8192)), dim3(256), 0, (hipStream_t)stream, sdf, N,
                      beta, density);
   return check_launch("na_laplace_density");
@@ -986,10 +993,10 @@ int na_laplace_density(const float* sdf, int64_t N, const float* beta, float* de
 
 int na_bezier_warp(const float* est, int est_stride, const float* pts, const float* t, int64_t N, int n_ctrl,
                    float* out_pts, float* dp, float* rigidity_out, void* stream) {
+  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 8 && est_stride >= 1 + 3 * n_ctrl && N >= 0, NA_EINVAL,
+             "na_bezier_warp: n_ctrl=%d (2..8) stride=%d N=%lld", n_ctrl, est_stride, (long long)N);
+  if (N == 0) return NA_OK;  // empty (a valid shape): zero-size tensors carry null pointers
   NA_REQUIRE(est && pts && t && out_pts, NA_ENULL, "na_bezier_warp: null pointer");
-  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 8 && est_stride >= 1 + 3 * n_ctrl, NA_EINVAL,
-             "na_bezier_warp: n_ctrl=%d (2..8) stride=%d", n_ctrl, est_stride);
-  if (N <= 0) return N == 0 ? NA_OK : NA_EINVAL;
   NA_REQUIRE(est_stride <= 255, NA_EINVAL, "na_bezier_warp: est_stride %d (<= 255)", est_stride);
   const int bw = est_stride <= 63 ? 256 : 64;
   hipLaunchKernelGGL(bezier_warp_kernel, dim3(grid_for(N, bw, 32768)), dim3(bw), est_stride >= 32 ? bw * (est_stride | 1) * sizeof(float) : 0, (hipStream_t)stream, est,
@@ -999,11 +1006,11 @@ int na_bezier_warp(const float* est, int est_stride, const float* pts, const flo
 
 int na_bezier_warp_latent(const float* est, int est_stride, const float* pts, const float* t, int64_t N, int n_ctrl,
                           int n_rl, float* out_pts, float* dp, float* rigidity_out, float* refl_latent, void* stream) {
+  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 8 && n_rl >= 1 && n_rl <= 16 && est_stride >= 2 + (3 + n_rl) * n_ctrl && N >= 0, NA_EINVAL,
+             "na_bezier_warp_latent: n_ctrl=%d (2..8) n_rl=%d (1..16) stride=%d (>= 2 + (3 + n_rl) * n_ctrl) N=%lld", n_ctrl, n_rl,
+             est_stride, (long long)N);
+  if (N == 0) return NA_OK;  // empty (a valid shape): zero-size tensors carry null pointers
   NA_REQUIRE(est && pts && t && out_pts && refl_latent, NA_ENULL, "na_bezier_warp_latent: null pointer");
-  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 8 && n_rl >= 1 && n_rl <= 16 && est_stride >= 2 + (3 + n_rl) * n_ctrl, NA_EINVAL,
-             "na_bezier_warp_latent: n_ctrl=%d (2..8) n_rl=%d (1..16) stride=%d (>= 2 + (3 + n_rl) * n_ctrl)", n_ctrl, n_rl,
-             est_stride);
-  if (N <= 0) return N == 0 ? NA_OK : NA_EINVAL;
   NA_REQUIRE(est_stride <= 255, NA_EINVAL, "na_bezier_warp_latent: est_stride %d (<= 255)", est_stride);
   const int bw = est_stride <= 63 ? 256 : 64;
   hipLaunchKernelGGL(bezier_warp_kernel, dim3(grid_for(N, bw, 32768)), dim3(bw), est_stride >= 32 ? bw * (est_stride | 1) * sizeof(float) : 0, (hipStream_t)stream, est,

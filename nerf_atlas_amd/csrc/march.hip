@@ -116,7 +116,10 @@ __global__ void sign_change_update_kernel(const float* __restrict__ sdf, int str
     const float sd = sdf[r * stride];
     const float cm = curr_min[r];
     if (sd < cm) idxs[r] = step + 1;
-    curr_min[r] = fminf(cm, sd);
+    // torch.minimum: a NaN on either side stays (fminf drops it).  Finite values keep fminf's bits: of +0 and -0, equal in value, it
+    // returned -0, the one with the larger bit pattern
+    const bool tie_neg_zero = sd == cm && __float_as_uint(sd) > __float_as_uint(cm);
+    curr_min[r] = (sd < cm || sd != sd || tie_neg_zero) ? sd : cm;
     if (first_neg[r] == -1 && sd < 0.f) {
       last_pos[r] = step;
       first_neg[r] = step + 1;
@@ -180,7 +183,7 @@ __global__ void point_light_kernel(const float* __restrict__ x, const float* __r
     const float* in = intensity + n * i_stride;
     const float dx = c[0] - x[3 * n], dy = c[1] - x[3 * n + 1], dz = c[2] - x[3 * n + 2];
     const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-    const float den = fmaxf(len, 1e-6f);
+    const float den = len < 1e-6f ? 1e-6f : len;  // clamp_min(1e-6) of F.normalize: a NaN length stays (fmaxf drops it)
     dir[3 * n] = dx / den; dir[3 * n + 1] = dy / den; dir[3 * n + 2] = dz / den;
     dist[n] = len;
     const float att = (len * len) * 12.566370614359172f;  // 4 * pi * dist^2 in the reference's order
