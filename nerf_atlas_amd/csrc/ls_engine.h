@@ -126,7 +126,10 @@ struct Cfg {
   static constexpr int PAIR = 2 * FRAG;
   static constexpr int HREG = PREC == NA_PREC_F16X ? NBLK * x::BLKH : NBLK * 16 * FRAG;  // hidden activations of one group
   static constexpr int IREG = NBLK * 4 * FRAG;                  // init-input chunks of one group
-  static constexpr int GROUP = HREG + IREG;                     // 80 KiB (f16x: 74 KiB)
+  // 80 KiB in every precision (f16x: 64 + 16): the launch asks for 2 x GROUP = ALL 160 KiB of the CU.  Nothing is left over, so
+  // the f16x View MLP's parked geometry fragments (x::geo_raw_at, x::geo_sin_at below) live in bytes of these regions that are idle
+  // for exactly as long as the fragment is needed.
+  static constexpr int GROUP = HREG + IREG;
   static constexpr int STREAM = kPairsPerPass * PAIR;           // weight stream of one row group
 };
 
@@ -619,6 +622,65 @@ __device__ __forceinline__ void geo_pair(f32x16 (&acc)[2][NB], Regs& R, __amdgpu
     const Frag<PREC> B = geo_make(b, graw[b], act);
     mma<PREC>(acc[0][b], R.pr[I & 1].t0, B);
     mma<PREC>(acc[1][b], R.pr[I & 1].t1, B);
+  }
+  __builtin_amdgcn_s_setprio(0);
+}
+
+// ---- the View MLP's geometry fragments, PARKED (MODEL 0 / 6): the four row-group waves of a sample group need the same B fragment of
+// a block, so one wave builds it in the epilogue in front of the phase and every wave reads it back.  The group's LDS has no byte
+// to spare (Cfg::GROUP), so the two versions live where nothing else does while they are needed:
+//   raw (view.init)  -- block b's whole fragment (hi plane | lo plane, lane-linear, 2 KiB) at the head of K64 region (block 1, group b)
+//     of the hidden space: idle from the barrier that closes first.out until wave b's OWN store of that region at the end of E7
+//     (the raw latent rows, the region's tenant until now, wait in the regions of groups 2 and 3 instead).
+//   through the sine (view.L0, MODEL 0) -- every byte of the group is live in that phase except dword 7 of the lane's second
+//     16-byte part of each fp6 operand (the header comment above: "dword 7 unused"; the MFMA reads dwords 0..5 as data, 6 as scale).
+//     Only the hi = 0 lanes of the fragment hold data, and only elements 0..4 of them: three dwords of the hi plane, three of the lo
+//     plane per sample.  Builder wave b (block b) keeps them in the spare dwords of its OWN K64 group, which it has just
+//     stored (so nobody overwrites them before E8): slot j = 2 * block + plane (0 R, 1 T) of lane s holds hi dwords 0, 1, 2 and lo dword 0,
+//     slots 0, 1 of lane s + 32 lo dwords 1, 2.  MODEL 6 regenerates IPE groups in block 0's regions between the two MFMA phases of
+//     view.L0 and keeps building this fragment in registers.
+__device__ __forceinline__ char* geo_raw_at(char* hb, int b) { return hb + BLKH + b * KQ; }
+__device__ __forceinline__ char* geo_sin_at(char* hb, int b, int j) {
+  return hb + (j >> 1) * BLKH + b * KQ + 4096 + (j & 1) * 2048 + 1024 + 12;
+}
+__device__ __forceinline__ void geo_sin_park(char* hb, int b, int lane, const Frag<NA_PREC_F16X>& f) {
+  const u32x4 h = __builtin_bit_cast(u32x4, f.hi), l = __builtin_bit_cast(u32x4, f.lo);
+  if (lane < 32) {
+    *(uint32_t*)(geo_sin_at(hb, b, 0) + lane * 16) = h[0];
+    *(uint32_t*)(geo_sin_at(hb, b, 1) + lane * 16) = h[1];
+    *(uint32_t*)(geo_sin_at(hb, b, 2) + lane * 16) = h[2];
+    *(uint32_t*)(geo_sin_at(hb, b, 3) + lane * 16) = l[0];
+    *(uint32_t*)(geo_sin_at(hb, b, 0) + (lane + 32) * 16) = l[1];
+    *(uint32_t*)(geo_sin_at(hb, b, 1) + (lane + 32) * 16) = l[2];
+  }
+}
+__device__ __forceinline__ Frag<NA_PREC_F16X> geo_sin_fetch(char* hb, int b, int lane) {
+  u32x4 h = {0u, 0u, 0u, 0u}, l = {0u, 0u, 0u, 0u};  // (the hi = 1 lanes and elements 5..7: sin(0) = +0 in both planes)
+  if (lane < 32) {
+    h[0] = *(const uint32_t*)(geo_sin_at(hb, b, 0) + lane * 16);
+    h[1] = *(const uint32_t*)(geo_sin_at(hb, b, 1) + lane * 16);
+    h[2] = *(const uint32_t*)(geo_sin_at(hb, b, 2) + lane * 16);
+    l[0] = *(const uint32_t*)(geo_sin_at(hb, b, 3) + lane * 16);
+    l[1] = *(const uint32_t*)(geo_sin_at(hb, b, 0) + (lane + 32) * 16);
+    l[2] = *(const uint32_t*)(geo_sin_at(hb, b, 1) + (lane + 32) * 16);
+  }
+  Frag<NA_PREC_F16X> f;
+  f.hi = __builtin_bit_cast(bf16x8, h);
+  f.lo = __builtin_bit_cast(bf16x8, l);
+  return f;
+}
+// the geometry pair against parked fragments: the same products in the same order as geo_pair
+template <int I, int NB, bool SIN>
+__device__ __forceinline__ void geo_pair_parked(f32x16 (&acc)[2][NB], Regs& R, int lane, char* hb) {
+  constexpr int PREC = NA_PREC_F16X;
+  __builtin_amdgcn_s_setprio(1);
+  Frag<PREC> B[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) B[b] = SIN ? geo_sin_fetch(hb, b, lane) : fread<PREC>(geo_raw_at(hb, b) + lane * 16);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    mma<PREC>(acc[0][b], R.pr[I & 1].t0, B[b]);
+    mma<PREC>(acc[1][b], R.pr[I & 1].t1, B[b]);
   }
   __builtin_amdgcn_s_setprio(0);
 }

@@ -54,6 +54,7 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
   // 190-207).  The ray of a block is wave-uniform: its origin, direction and elev/azim (from the pre-kernel) are read once
   // per pass (in the short epilogue of first.out) and kept in SGPRs (geo_u, readfirstlane), together with the block's step
   // offset; the two MFMA phases that consume the chunk only load t (or the explicit position) of their lane at their start.
+  // (NA_PREC_F16X, MODEL 0 / 6: not even that -- one wave per block builds the fragment in the epilogue in front: geo_park below)
   float geo_u[NB][8];   // ox oy oz dx dy dz elev azim of block b's ray (uniform)
   int geo_t0[NB];       // first step of block b
   int geo_ray[NB];
@@ -171,6 +172,22 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
     if (hi == 0) { v4[0] = px; v4[1] = py; v4[2] = pz; v4[3] = geo_u[b][6]; v4[4] = geo_u[b][7]; }
     Frag<PREC> f = make_frag<PREC>(v4);
     if (act) frag_activate<PREC, NA_ACT_SIN>(f);
+    return f;
+  };
+  // NA_PREC_F16X, MODEL 0 / 6: the four row-group waves of a sample group need the SAME geometry fragment of a block, so ONE wave
+  // builds it (geo_load + geo_make: the identical arithmetic, explicit positions included) and parks it in LDS (ls_engine.h,
+  // x::geo_raw_at / geo_sin_at: where, and for how long) -- raw in the epilogue of first.out, geo_setup(pass) has run; the skip
+  // layer's version from the parked raw one, frag_activate as on registers.  The MFMA phases read them back (x::geo_pair_parked).
+  auto geo_park = [&](int b) {
+    if constexpr (PREC == NA_PREC_F16X) {
+#pragma unroll
+      for (int bb = 0; bb < NB; ++bb)
+        if (bb == b) fwrite<PREC>(x::geo_raw_at(hb, bb) + lane * 16, geo_make(bb, geo_load(bb), false));
+    }
+  };
+  auto geo_sin_of_parked = [&](int b) -> Frag<PREC> {
+    Frag<PREC> f = fread<PREC>(x::geo_raw_at(hb, b) + lane * 16);
+    frag_activate<PREC, NA_ACT_SIN>(f);
     return f;
   };
   struct Geom {

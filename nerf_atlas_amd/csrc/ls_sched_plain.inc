@@ -129,36 +129,34 @@
         load_bias2(6);
         geo_setup(pass);
         if (rg < 2) {
-          // the latent group of block rg: raw rows into the wave's own (idle) K64 region for the skip connection, the group
-          // itself into the init region
-          char* st = hb + x::BLKH + rg * x::KQ + lane * 16;  // (the wave's K64 region of block 1: E7 stores it last)
+          // the latent group of block rg: raw rows into the (idle) K64 region of wave rg + 2, which converts them for the skip
+          // connection in E7, the group itself into the init region
+          char* st = hb + x::BLKH + (rg + 2) * x::KQ + lane * 16;  // (that wave's K64 region of block 1: its E7 stores it last)
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             *(f32x4*)(st + c * 1024) = f32x4{ol[0][0][4 * c], ol[0][0][4 * c + 1], ol[0][0][4 * c + 2], ol[0][0][4 * c + 3]};
             *(f32x4*)(st + 4096 + c * 1024) = f32x4{ol[1][0][4 * c], ol[1][0][4 * c + 1], ol[1][0][4 * c + 2], ol[1][0][4 * c + 3]};
           }
           x::store_block<NA_ACT_NONE, 4, true>(ib + rg * x::KQ, ol[0][0], ol[1][0], lane, a.sat_gen);
-        } else if (hi == 0) {
+        } else {
           // density of block rg & 1 -> the spare dword of the latent group's T operand (lane = step), where it waits for the
           // compositing at the end of the pass: carried in a register it was the one value spilled AND re-stored every pass
-          *(float*)(ib + (rg & 1) * x::KQ + 6144 + 1024 + ln * 16 + 12) = ol[0][0][0];
+          if (hi == 0) *(float*)(ib + (rg & 1) * x::KQ + 6144 + 1024 + ln * 16 + 12) = ol[0][0][0];
+          geo_park(rg & 1);  // view.init's geometry fragment of that block, once for the four waves (these two have the slack)
         }
         if constexpr (MIP) { mip_setup(); gen_ipe(std::integral_constant<int, NA_ACT_NONE>{}); }
         x::pairs_prefetch(XR, wrs, xpair, lane, 0, 1);
       }
       SYNC();
       {
-        GeoRaw graw[NB];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) graw[b] = geo_load(b);
         if constexpr (MIP) x::recs<2, NB, true, XNR, 3, 1, 0, 4, false, IPS, 3, 2>(acc, bvx, XR, wrs, xrec, RVI, hb, lane, ib);
         else x::recs<2, NB, true, XNR, 1, 1, 0, 4>(acc, bvx, XR, wrs, xrec, RVI, hb, lane, ib);  // view.init: latent group + geometry
-        x::geo_pair<0, NB>(acc, XR, wrs, xpair, lane, graw, geo_make, false);
+        x::geo_pair_parked<0, NB, false>(acc, XR, lane, hb);
       }
       SYNC();
       {
         x::store_acts<NA_ACT_SIN, NB, 0, 1>(acc, hb, rg, lane, a.sat_gen);
-        if (rg < 2) {  // sin(latent) for the skip connection, from the raw rows (before block 1's store overwrites their region)
+        if (rg >= 2) {  // sin(latent) of block rg & 1 for the skip connection, from the raw rows (before this wave's block 1 store overwrites their region)
           const char* st = hb + x::BLKH + rg * x::KQ + lane * 16;
           f32x16 l0, l1;
 #pragma unroll
@@ -167,9 +165,18 @@
             l0[4 * c] = u[0]; l0[4 * c + 1] = u[1]; l0[4 * c + 2] = u[2]; l0[4 * c + 3] = u[3];
             l1[4 * c] = w[0]; l1[4 * c + 1] = w[1]; l1[4 * c + 2] = w[2]; l1[4 * c + 3] = w[3];
           }
-          x::store_block<NA_ACT_SIN, 4, true>(ib + rg * x::KQ, l0, l1, lane, a.sat_gen);
+          x::store_block<NA_ACT_SIN, 4, true>(ib + (rg & 1) * x::KQ, l0, l1, lane, a.sat_gen);
+        }
+        // view.L0's geometry fragment of block rg, once for the four waves: the parked raw one (in this wave's region of block 1, which
+        // the store below overwrites) through the sine, into the spare dwords of the operands this wave has stored by then
+        Frag<PREC> gsin;
+        if constexpr (!MIP) {
+          if (rg < 2) gsin = geo_sin_of_parked(rg);
         }
         x::store_acts<NA_ACT_SIN, NB, 1, 2>(acc, hb, rg, lane, a.sat_gen);
+        if constexpr (!MIP) {
+          if (rg < 2) x::geo_sin_park(hb, rg, lane, gsin);
+        }
         load_bias2(7);
         if constexpr (!MIP) XR.pr[0] = x::wpair(wrs, lane, xpair, 1);  // (the second geometry pair, into the same ring slot: the first one is spent)
       }
@@ -184,13 +191,10 @@
 #pragma unroll
         for (int b = 0; b < NB; ++b) graw[b] = geo_load(b);
         x::recs<2, NB, false, XNR, 2, 0, 0, 4, false, IPS, 3, 2>(acc, bvx, XR, wrs, xrec, RVL0 + 5, hb, lane);  // ... + IPE + geometry
-        x::geo_pair<0, NB>(acc, XR, wrs, xpair, lane, graw, geo_make, true);
+        x::geo_pair<0, NB>(acc, XR, wrs, xpair, lane, graw, geo_make, true);  // (in registers: gen_ipe has rewritten block 0's operands)
       } else {
-        GeoRaw graw[NB];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) graw[b] = geo_load(b);
         x::recs<2, NB, true, XNR, 5, 1, 1, 4>(acc, bvx, XR, wrs, xrec, RVL0, hb, lane, ib);  // view.L0: skip group, K = 256, geometry
-        x::geo_pair<0, NB>(acc, XR, wrs, xpair, lane, graw, geo_make, true);
+        x::geo_pair_parked<0, NB, true>(acc, XR, lane, hb);
       }
       SYNC();
 #pragma unroll 1
