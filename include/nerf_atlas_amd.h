@@ -795,6 +795,34 @@ int na_voxel_sample_backward(const float* pts, const float* rays, int64_t R, con
 int na_voxel_render(const float* rays, const float* pts, int64_t R, const float* ts, int T, const float* densities, const float* rgb,
                     int S, int C, double grid_radius, int act_kind, int bg_kind, float* alpha, float* weights, float* out,
                     void* stream);
+/* na_voxel_sample_backward_pts  g_pts [N,3] = the gradient of na_voxel_sample w.r.t. explicit positions pts [N,3] given g_raw [N, 1 + C]
+ *                           (16-byte aligned).  In the reference only xyz depends on p -- the floors and both clamps carry no gradient --
+ *                           so g_pts[n,a] = (1 / voxel_len) sum_u (dw_u / dxyz_a) (g_raw[n,0] densities[row_u] + sum_c g_raw[n,1+c]
+ *                           rgb[row_u,c]) with dw_u / dx = +-(wy wz): the derivative of the cell's (inside the grid: trilinear; outside:
+ *                           extrapolating) polynomial.  A gather, no atomics; a non-finite coordinate gives a NaN row.             */
+int na_voxel_sample_backward_pts(const float* pts, int64_t N, const float* densities, const float* rgb, const float* g_raw, int S, int C,
+                                 double grid_radius, float* g_pts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * DynamicNeRFVoxel (src/nerf.py:1526-1586; csrc/dyn_voxel.hip): the deformation of a voxel D-NeRF.  ctrl_pts_grid [S,S,S,3(n-1)] holds
+ * control points 1 .. n-1 of a Bezier spline per voxel (control point 0 is zero), rigidity_grid [S,S,S,1] a rigidity logit; both are
+ * read by NeRFVoxel's lookup above at the UNWARPED pts [N,3] (same cells, same weights, same memory-safety rule), t [N] is the time of
+ * each sample (expanded by the caller).  n = n_ctrl is 2 .. 11 (else NA_EUNSUPPORTED), S even, 2 .. 1024.
+ * na_dyn_voxel_warp           one launch: dp [N,3] = cubic_bezier (n == 4, src/nerf.py:1201-1206) else de_casteljau (:1173-1178) of the
+ *                             interpolated control points at t; rigidity [N] = sigmoid(interpolated logit) (the plain sigmoid);
+ *                             warped [N,3] = pts + dp * rigidity.  dp and rigidity may be NULL.  A non-finite coordinate gives NaN in
+ *                             that sample's outputs only.
+ * na_dyn_voxel_warp_backward  g_ctrl_pts_grid += and g_rigidity_grid += (zeroed by the caller) given any of g_warped [N,3], g_dp [N,3],
+ *                             g_rigidity [N] (NULL = zero) and the forward's dp and rigidity: with r the rigidity, G = g_warped,
+ *                             D = G r + g_dp and q = (G . dp + g_rigidity) r (1 - r), control block k of the 8 rows gets w_u B_k(t) D and
+ *                             the rigidity row w_u q.  No gradient w.r.t. pts.  fp32 atomics by default; under na_set_deterministic
+ *                             every contribution goes to 2^-40 fixed point on its own (workspace >= 8 S^3 (1 + 3(n-1)) bytes, else
+ *                             NA_EWORKSPACE) and the result is bitwise independent of the order of the samples.                    */
+int na_dyn_voxel_warp(const float* pts, const float* t, int64_t N, const float* ctrl_pts_grid, const float* rigidity_grid, int S, int n_ctrl,
+                      double grid_radius, float* warped, float* dp, float* rigidity, void* stream);
+int na_dyn_voxel_warp_backward(const float* pts, const float* t, int64_t N, const float* dp, const float* rigidity, const float* g_warped,
+                               const float* g_dp, const float* g_rigidity, int S, int n_ctrl, double grid_radius, float* g_ctrl_pts_grid,
+                               float* g_rigidity_grid, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Operators on a dense channel-last grid [s0,s1,s2,C], 1 <= C <= 32 (NeRFVoxel's densities and rgb; csrc/grid_ops.hip).

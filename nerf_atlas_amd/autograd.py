@@ -536,18 +536,46 @@ class GridTVFn(Function):
 
 class VoxelSampleFn(Function):
     """raw [..., 1 + C] of NeRFVoxel's grid lookup (ops.voxel_sample); backward scatters into the two grids (ops.voxel_sample_backward).
-    Only the positions are saved -- explicit pts, or rays and ts -- and the cells are recomputed.  No gradient w.r.t. the positions."""
+    Only the positions are saved -- explicit pts, or rays and ts -- and the cells are recomputed.  Explicit pts that require a gradient
+    (DynamicNeRFVoxel's warped points) get one (ops.voxel_sample_backward_pts: a gather; the grids are saved for it); the
+    rays x ts form has no position gradient."""
 
     @staticmethod
     def forward(ctx, densities, rgb, grid_radius, pts, rays, ts):
         ctx.grid_radius, ctx.S = grid_radius, densities.shape[0]
         ctx.explicit = pts is not None
-        ctx.save_for_backward(*((pts,) if ctx.explicit else (rays, ts)))
+        ctx.pts_grad = ctx.explicit and ctx.needs_input_grad[3]
+        ctx.save_for_backward(*((pts,) if ctx.explicit else (rays, ts)), *((densities, rgb) if ctx.pts_grad else ()))
         return ops.voxel_sample(densities, rgb, grid_radius, pts=pts, rays=rays, ts=ts)
 
     @staticmethod
     def backward(ctx, g):
         pos = ctx.saved_tensors
         kw = {"pts": pos[0]} if ctx.explicit else {"rays": pos[0], "ts": pos[1]}
-        g_den, g_rgb = ops.voxel_sample_backward(g.contiguous(), ctx.S, ctx.grid_radius, **kw)
-        return g_den, g_rgb, None, None, None, None
+        g = g.contiguous()
+        g_den = g_rgb = g_pts = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            g_den, g_rgb = ops.voxel_sample_backward(g, ctx.S, ctx.grid_radius, **kw)
+        if ctx.pts_grad and ctx.needs_input_grad[3]:
+            g_pts = ops.voxel_sample_backward_pts(g, pos[0], pos[1], pos[2], ctx.grid_radius)
+        return g_den, g_rgb, None, g_pts, None, None
+
+
+class DynVoxelWarpFn(Function):
+    """(warped, dp, rigidity) of DynamicNeRFVoxel's deformation (ops.dyn_voxel_warp, one launch); all three are differentiable --
+    `warped` feeds the canonical lookup, `dp` and `rigidity` the offset regularisers -- and backward is one scatter-add into the two
+    grids (ops.dyn_voxel_warp_backward).  pts and t carry no gradient (the positions are a leaf in the reference)."""
+
+    @staticmethod
+    def forward(ctx, ctrl_pts_grid, rigidity_grid, pts, t, spline, grid_radius):
+        warped, dp, rigidity = ops.dyn_voxel_warp(pts, t, ctrl_pts_grid, rigidity_grid, spline, grid_radius)
+        ctx.save_for_backward(pts, t, dp, rigidity)
+        ctx.S, ctx.spline, ctx.grid_radius = rigidity_grid.shape[0], spline, grid_radius
+        ctx.set_materialize_grads(False)
+        return warped, dp, rigidity
+
+    @staticmethod
+    def backward(ctx, g_warped, g_dp, g_rigidity):
+        pts, t, dp, rigidity = ctx.saved_tensors
+        g_ctrl, g_rig = ops.dyn_voxel_warp_backward(pts, t, dp, rigidity, ctx.S, ctx.spline, ctx.grid_radius, g_warped, g_dp, g_rigidity)
+        return g_ctrl, g_rig, None, None, None, None

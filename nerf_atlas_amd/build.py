@@ -38,6 +38,7 @@ UNITS = [
     ("fourier_grad.hip", [], ""),
     ("composite_rayts.hip", [], ""),
     ("voxel.hip", [], ""),
+    ("dyn_voxel.hip", [], ""),
     ("grid_ops.hip", [], ""),
     ("optim.hip", [], ""),
     ("backward.hip", [], ""),

@@ -167,5 +167,18 @@ def set_deterministic(on: bool, device="cuda"):
         _det_ws = None
 
 
+def require_deterministic_workspace(nbytes: int):
+    """While the deterministic mode is on, make its workspace at least `nbytes` large (an operator whose accumulated output is larger
+    than the default's 2 Mi elements: DynamicNeRFVoxel's grids at S = 64 hold 2.6 Mi).  The old buffer is released in stream order."""
+    global _det_ws
+    if _det_ws is None or _det_ws.numel() >= nbytes:
+        return
+    import torch
+    from . import _lib
+    ws = torch.empty(nbytes + 4096, device=_det_ws.device, dtype=torch.uint8)
+    _lib.check(_lib.load().na_set_deterministic(ws.data_ptr(), ws.numel()))
+    _det_ws = ws
+
+
 def deterministic() -> bool:
     return _det_ws is not None

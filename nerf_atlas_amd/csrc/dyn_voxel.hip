@@ -1,0 +1,260 @@
+// DynamicNeRFVoxel (src/nerf.py:1526-1586): a D-NeRF without an MLP.  Two more dense grids over NeRFVoxel's S^3 cells --
+// ctrl_pts_grid [S,S,S,3(n-1)], the control points 1 .. n-1 of a Bezier spline (control point 0 is zero), and rigidity_grid [S,S,S,1]
+// -- are read by the SAME 8-neighbour lookup as the canonical grids (voxel_cell.h: cells and weights of the UNWARPED point in the
+// reference's fp32 chain), and
+//   dp       = cubic_bezier (n == 4, src/nerf.py:1201-1206) or de_casteljau (src/nerf.py:1173-1178) of the interpolated control points at t
+//   rigidity = sigmoid(interpolated rigidity_grid)                 (the plain sigmoid, not na_bezier_warp's x / 2 form)
+//   warped   = pts + dp * rigidity
+// Two operators: the deformation as one launch (na_dyn_voxel_warp: a gather of 8 rows of 1 + 3(n-1) floats, the spline) and its
+// backward (na_dyn_voxel_warp_backward: a scatter-add into the two grids on voxel_backward_kernel's scheme).  There is no gradient
+// w.r.t. pts: they are a leaf in the reference.  Kernels are instantiated per n = 2 .. 11 so that the control points stay in registers.
+#include "voxel_cell.h"
+
+namespace na {
+
+// the reference's two spline forms on control points b[0 .. NC-1][3] (b[0] = 0); dp <- b(t)
+template <int NC>
+__device__ __forceinline__ void dv_spline(const float* cp, float t, float dp[3]) {
+  const float m1t = 1.f - t;
+  if (NC == 4) {
+    // (k * coeffs).sum(dim=0) with coeffs[0] = 0: k0 * 0 is the first addend
+    const float m1t_sq = m1t * m1t, t_sq = t * t;
+    const float k0 = m1t_sq * m1t, k1 = (3.f * m1t_sq) * t, k2 = (3.f * t_sq) * m1t, k3 = t_sq * t;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) dp[a] = ((k0 * 0.f + k1 * cp[a]) + k2 * cp[3 + a]) + k3 * cp[6 + a];
+    return;
+  }
+  float b[NC][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    b[0][a] = 0.f;
+#pragma unroll
+    for (int k = 1; k < NC; ++k) b[k][a] = cp[3 * (k - 1) + a];
+  }
+#pragma unroll
+  for (int i = 1; i < NC; ++i) {
+#pragma unroll
+    for (int j = 0; j < NC - i; ++j) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) b[j][a] = b[j][a] * m1t + b[j + 1][a] * t;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) dp[a] = b[0][a];
+}
+
+// d dp / d control point k, k = 0 .. NC-1: the cubic form's own coefficients, else the Bernstein polynomials by the de Casteljau
+// recurrence on the weights (every step a convex combination for t in [0, 1])
+template <int NC>
+__device__ __forceinline__ void dv_bernstein(float t, float B[NC]) {
+  const float m1t = 1.f - t;
+  if (NC == 4) {
+    const float m1t_sq = m1t * m1t, t_sq = t * t;
+    B[0] = m1t_sq * m1t; B[1] = (3.f * m1t_sq) * t; B[2] = (3.f * t_sq) * m1t; B[3] = t_sq * t;
+    return;
+  }
+  B[0] = 1.f;
+#pragma unroll
+  for (int k = 1; k < NC; ++k) B[k] = 0.f;
+#pragma unroll
+  for (int i = 1; i < NC; ++i) {
+#pragma unroll
+    for (int j = i; j >= 1; --j) B[j] = B[j] * m1t + B[j - 1] * t;
+    B[0] = B[0] * m1t;
+  }
+}
+
+// ------------------------------------------------------------------------------------ the deformation, one launch
+// one thread per sample: 8 rows of 3(n-1) floats + 8 rigidity entries (S = 64, n = 4: 9.4 + 1 MiB of grids, L2 / Infinity Cache resident)
+template <int NC>
+__global__ __launch_bounds__(256) void dyn_voxel_warp_kernel(const float* __restrict__ pts, const float* __restrict__ t, int64_t N, VoxGrid g,
+                                                             const float* __restrict__ ctrl, const float* __restrict__ rig,
+                                                             float* __restrict__ warped, float* __restrict__ dp_out,
+                                                             float* __restrict__ rig_out) {
+  constexpr int CH = 3 * (NC - 1);
+  for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
+    const float px = pts[n * 3], py = pts[n * 3 + 1], pz = pts[n * 3 + 2];
+    const VoxCell c = vox_cell(px, py, pz, g);
+    float cp[CH], rl = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < CH; ++ch) cp[ch] = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int64_t row = vox_row(c, u, g.S);
+      const float w = vox_weight(c, u);
+      const float* q = ctrl + row * CH;
+#pragma unroll
+      for (int ch = 0; ch < CH; ++ch) cp[ch] = cp[ch] + w * q[ch];
+      rl = rl + w * rig[row];
+    }
+    float dp[3];
+    dv_spline<NC>(cp, t[n], dp);
+    const float r = sigmoidf_(rl);
+    warped[n * 3] = px + dp[0] * r; warped[n * 3 + 1] = py + dp[1] * r; warped[n * 3 + 2] = pz + dp[2] * r;
+    if (dp_out != nullptr) { dp_out[n * 3] = dp[0]; dp_out[n * 3 + 1] = dp[1]; dp_out[n * 3 + 2] = dp[2]; }
+    if (rig_out != nullptr) rig_out[n] = r;
+  }
+}
+
+// ------------------------------------------------------------------------------------ scatter-add into the two grids
+// With r the rigidity, G = g_warped, D = G r + g_dp and q = (G . dp + g_rigidity) r (1 - r), corner u of a sample adds
+//   w_u B_k(t) D  to channels 3(k-1) .. 3k-1 of ctrl row_u  (k = 1 .. n-1)      and      w_u q  to rigidity row_u:
+// one "wide row" of W = 1 + 3(n-1) sums per grid row, [rigidity | control channels].  The scheme is voxel_backward_kernel's: a
+// workgroup takes a contiguous run of samples, sums into a hashed LDS table of ROWS wide rows (multiplicative hash, NA_DV_PROBES linear
+// probes, a slot is never freed), flushes it once, and a row that finds no slot falls through to the global accumulators.  A slot is
+// 8 bytes per sum (the fixed-point mode's integers; the fp32 mode uses the low word), so ROWS shrinks with W to keep the table and
+// its tags inside 64 KB -- two workgroups per CU of 160 KB LDS: 1024 rows for W <= 7, 512 for W <= 13, 256 up to W = 31 (62 KB).
+// The flush walks the table element by element, so the lanes of a wave add to consecutive floats of consecutive table rows
+// (segments of 4 W bytes), not one lane per row.  dp and rigidity are the forward's outputs (16 bytes per sample instead of
+// gathering the 8 rows again).  Deterministic mode: every contribution to 2^-40 fixed point on its own, as voxel_backward_kernel.
+#ifndef NA_DV_PROBES
+#define NA_DV_PROBES 4
+#endif
+constexpr int DV_WG = 4096;  // workgroups at most: a workgroup's run is ceil(N / DV_WG) samples rounded up to whole rounds of 256
+constexpr int dv_rows(int W) { return W <= 7 ? 1024 : W <= 13 ? 512 : 256; }
+constexpr int dv_log2(int v) { return v <= 1 ? 0 : 1 + dv_log2(v / 2); }
+
+template <int NC>
+__global__ __launch_bounds__(256) void dyn_voxel_warp_backward_kernel(const float* __restrict__ pts, const float* __restrict__ t, int64_t N,
+                                                                      VoxGrid g, const float* __restrict__ dp, const float* __restrict__ rigidity,
+                                                                      const float* __restrict__ g_warped, const float* __restrict__ g_dp,
+                                                                      const float* __restrict__ g_rigidity, float* __restrict__ g_ctrl,
+                                                                      float* __restrict__ g_rig, long long* __restrict__ fix) {
+  constexpr int CH = 3 * (NC - 1), W = CH + 1, ROWS = dv_rows(W), SHIFT = 32 - dv_log2(ROWS);
+  static_assert(ROWS * W * 8 + ROWS * 4 <= 65536, "the table and its tags stay inside 64 KB of LDS");
+  const int64_t S3 = (int64_t)g.S * g.S * g.S;
+  long long* fix_rig = fix != nullptr ? fix + S3 * CH : nullptr;
+  auto add_global = [&](uint32_t id, int e, float v) {
+    if (e == 0) accumulate(g_rig, fix_rig, (int64_t)id, v);
+    else accumulate(g_ctrl, fix, (int64_t)id * CH + (e - 1), v);
+  };
+  __shared__ uint32_t tags[ROWS];
+  __shared__ unsigned long long vals[ROWS * W];
+  for (int i = threadIdx.x; i < ROWS; i += 256) tags[i] = 0xffffffffu;
+  for (int i = threadIdx.x; i < ROWS * W; i += 256) vals[i] = 0ull;
+  __syncthreads();
+  // W sums for one grid row: the slot of the id (NA_DV_PROBES linear probes from its hash; a slot is never freed, so an id finds the same
+  // slot every time, or none), else the global accumulators
+  auto add_row = [&](uint32_t id, float w, const float (&sv)[W]) {
+    const uint32_t home = (id * 2654435761u) >> SHIFT;
+#pragma unroll
+    for (int p = 0; p < NA_DV_PROBES; ++p) {
+      const uint32_t row = (home + p) & (ROWS - 1);
+      const uint32_t old = atomicCAS(&tags[row], 0xffffffffu, id);
+      if (old == 0xffffffffu || old == id) {
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+          const float v = w * sv[e];
+          if (fix == nullptr) atomicAdd((float*)&vals[row * W + e], v);
+          else if (fabsf(v) < 1048576.0f) atomicAdd(&vals[row * W + e], (unsigned long long)__float2ll_rn(v * kFixScale));
+          else add_global(id, e, v);  // (out of the fixed-point range, NaN: the fp32 path, as accumulate() does)
+        }
+        return;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < W; ++e) add_global(id, e, w * sv[e]);
+  };
+  const int64_t per = ((N + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;  // samples of this workgroup: whole rounds
+  const int64_t n_lo = blockIdx.x * per, n_hi = n_lo + per < N ? n_lo + per : N;
+  for (int64_t base = n_lo; base < n_hi; base += 256) {
+    const int64_t n = base + threadIdx.x;
+    if (n >= n_hi) continue;  // (no barrier inside the loop)
+    const VoxCell c = vox_cell(pts[n * 3], pts[n * 3 + 1], pts[n * 3 + 2], g);
+    const float r = rigidity[n];
+    float G[3] = {0.f, 0.f, 0.f}, D[3], gd = 0.f;
+    if (g_warped != nullptr) { G[0] = g_warped[n * 3]; G[1] = g_warped[n * 3 + 1]; G[2] = g_warped[n * 3 + 2]; }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      D[a] = G[a] * r + (g_dp != nullptr ? g_dp[n * 3 + a] : 0.f);
+      gd = gd + G[a] * dp[n * 3 + a];
+    }
+    if (g_rigidity != nullptr) gd = gd + g_rigidity[n];
+    float B[NC], sv[W];
+    dv_bernstein<NC>(t[n], B);
+    sv[0] = gd * (r * (1.f - r));
+#pragma unroll
+    for (int k = 1; k < NC; ++k) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) sv[1 + 3 * (k - 1) + a] = B[k] * D[a];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) add_row((uint32_t)vox_row(c, u, g.S), vox_weight(c, u), sv);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < ROWS * W; i += 256) {
+    const int row = i / W, e = i - row * W;
+    const uint32_t id = tags[row];
+    if (id == 0xffffffffu) continue;
+    const unsigned long long v = vals[i];
+    const int64_t at = e == 0 ? (int64_t)id : (int64_t)id * CH + (e - 1);
+    if (fix == nullptr) atomicAdd((e == 0 ? g_rig : g_ctrl) + at, __uint_as_float((uint32_t)v));
+    else atomicAdd((unsigned long long*)((e == 0 ? fix_rig : fix) + at), v);
+  }
+}
+
+static int dv_check(const char* who, int64_t N, int S, int n_ctrl, double grid_radius) {
+  NA_REQUIRE(N >= 0, NA_EINVAL, "%s: bad shape N=%lld", who, (long long)N);
+  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED, "%s: spline %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", who,
+             n_ctrl);
+  return vox_check_grid(who, S, 3, grid_radius);
+}
+
+#define NA_DV_DISPATCH(N_CTRL, LAUNCH) \
+  switch (N_CTRL) {                    \
+    case 2: LAUNCH(2); break;          \
+    case 3: LAUNCH(3); break;          \
+    case 4: LAUNCH(4); break;          \
+    case 5: LAUNCH(5); break;          \
+    case 6: LAUNCH(6); break;          \
+    case 7: LAUNCH(7); break;          \
+    case 8: LAUNCH(8); break;          \
+    case 9: LAUNCH(9); break;          \
+    case 10: LAUNCH(10); break;        \
+    default: LAUNCH(11); break;        \
+  }
+
+}  // namespace na
+
+using namespace na;
+
+extern "C" {
+
+int na_dyn_voxel_warp(const float* pts, const float* t, int64_t N, const float* ctrl_pts_grid, const float* rigidity_grid, int S, int n_ctrl,
+                      double grid_radius, float* warped, float* dp, float* rigidity, void* stream) {
+  if (int rc = dv_check("na_dyn_voxel_warp", N, S, n_ctrl, grid_radius)) return rc;
+  if (N == 0) return NA_OK;
+  NA_REQUIRE(pts && t && ctrl_pts_grid && rigidity_grid && warped, NA_ENULL, "na_dyn_voxel_warp: null pointer");
+  const VoxGrid g = vox_grid(S, grid_radius);
+#define NA_DV_FWD(NC)                                                                                                                    \
+  hipLaunchKernelGGL(dyn_voxel_warp_kernel<NC>, dim3(grid_for(N, 256)), dim3(256), 0, (hipStream_t)stream, pts, t, N, g, ctrl_pts_grid, \
+                     rigidity_grid, warped, dp, rigidity)
+  NA_DV_DISPATCH(n_ctrl, NA_DV_FWD)
+#undef NA_DV_FWD
+  return check_launch("na_dyn_voxel_warp");
+}
+
+int na_dyn_voxel_warp_backward(const float* pts, const float* t, int64_t N, const float* dp, const float* rigidity, const float* g_warped,
+                               const float* g_dp, const float* g_rigidity, int S, int n_ctrl, double grid_radius, float* g_ctrl_pts_grid,
+                               float* g_rigidity_grid, void* stream) {
+  if (int rc = dv_check("na_dyn_voxel_warp_backward", N, S, n_ctrl, grid_radius)) return rc;
+  if (N == 0 || (!g_warped && !g_dp && !g_rigidity)) return NA_OK;
+  NA_REQUIRE(pts && t && dp && rigidity && g_ctrl_pts_grid && g_rigidity_grid, NA_ENULL, "na_dyn_voxel_warp_backward: null pointer");
+  const size_t S3 = (size_t)S * S * S, CH = 3 * (size_t)(n_ctrl - 1);
+  int rc;
+  long long* fix = det_begin(S3 * (CH + 1), (hipStream_t)stream, "na_dyn_voxel_warp_backward", &rc);
+  if (rc != NA_OK) return rc;
+  const VoxGrid g = vox_grid(S, grid_radius);
+#define NA_DV_BWD(NC)                                                                                                                        \
+  hipLaunchKernelGGL(dyn_voxel_warp_backward_kernel<NC>, dim3(grid_for(N, 256, DV_WG)), dim3(256), 0, (hipStream_t)stream, pts, t, N, g, dp, \
+                     rigidity, g_warped, g_dp, g_rigidity, g_ctrl_pts_grid, g_rigidity_grid, fix)
+  NA_DV_DISPATCH(n_ctrl, NA_DV_BWD)
+#undef NA_DV_BWD
+  if (fix != nullptr) {
+    if (int rc2 = det_finish(fix, S3 * CH, g_ctrl_pts_grid, (hipStream_t)stream, "na_dyn_voxel_warp_backward")) return rc2;
+    return det_finish(fix + S3 * CH, S3, g_rigidity_grid, (hipStream_t)stream, "na_dyn_voxel_warp_backward");
+  }
+  return check_launch("na_dyn_voxel_warp_backward");
+}
+
+}  // extern "C"

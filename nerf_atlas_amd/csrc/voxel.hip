@@ -1,6 +1,6 @@
 // NeRFVoxel (src/nerf.py:401-524): a dense S^3 grid of density and colour parameters read by the reference's 8-neighbour lookup
-// (grid_coords_trilin_weights, src/nerf.py:493-515).  Three operators: the gather (na_voxel_sample), its scatter-add backward
-// (na_voxel_sample_backward) and the eval route as one launch (na_voxel_render: positions -> gather -> activation -> compositing).
+// (grid_coords_trilin_weights, src/nerf.py:493-515).  Four operators: the gather (na_voxel_sample), its scatter-add backward
+// (na_voxel_sample_backward), its gradient w.r.t. explicit positions (na_voxel_sample_backward_pts) and the eval route as one launch (na_voxel_render: positions -> gather -> activation -> compositing).
 //
 // The lookup is NOT a textbook trilinear interpolation and is reproduced, not improved:
 //   neighbours  p -+ voxel_len / 2 per axis, clamped to +-grid_radius; corner u takes + on axis i when bit i of u is set
@@ -12,85 +12,9 @@
 // between the pairs (k, k+1), (k+1, k+2) and (k, k+2): cell membership is part of the operator's definition and every operation
 // up to and including xyz is the reference's fp32 operation in the reference's order (this unit is built with -ffp-contract=off
 // and hipcc's correctly rounded division; tests/voxel_ref.py restates the chain in fp32 torch and the g23 fixtures pin it).
-#include "common.h"
-#include <math.h>
+#include "voxel_cell.h"
 
 namespace na {
-
-// fp32 images of the reference's Python doubles (src/nerf.py:427-428, 500, 506)
-struct VoxGrid {
-  float vl;    // voxel_len = grid_radius * 2 / S
-  float h;     // 0.5 * voxel_len
-  float gr;    // grid_radius
-  float cmax;  // grid_radius - voxel_len / 2
-  float half;  // S / 2 (S even: an integer)
-  int S;
-};
-
-static VoxGrid vox_grid(int S, double grid_radius) {
-  const double vl = grid_radius * 2 / S;
-  VoxGrid g;
-  g.vl = (float)vl; g.h = (float)(0.5 * vl); g.gr = (float)grid_radius; g.cmax = (float)(grid_radius - vl / 2);
-  g.half = (float)(S / 2); g.S = S;
-  return g;
-}
-
-// id of a (clamped) centre.  Memory safety is unconditional: the float is brought into 0 .. S-1 by selects (a NaN fails both
-// comparisons' "keep" side and becomes 0), converted, and clamped again as an integer.
-__device__ __forceinline__ int vox_id(float c, const VoxGrid& g) {
-  float f = floorf(c / g.vl + 1e-10f) + g.half;
-  const float top = (float)(g.S - 1);
-  f = f >= 0.f ? (f <= top ? f : top) : 0.f;
-  const int i = (int)f;
-  return min(max(i, 0), g.S - 1);
-}
-
-// one axis: ids of the lower / upper neighbour and the fraction x
-__device__ __forceinline__ void vox_axis(float p, const VoxGrid& g, int& ilo, int& ihi, float& x) {
-  const float nlo = clamp_keep_nan(p - g.h, -g.gr, g.gr);  // (-h) + p
-  const float nhi = clamp_keep_nan(g.h + p, -g.gr, g.gr);
-  const float clo = clamp_keep_nan((floorf(nlo / g.vl + 1e-10f) + 0.5f) * g.vl, -g.cmax, g.cmax);
-  const float chi = clamp_keep_nan((floorf(nhi / g.vl + 1e-10f) + 0.5f) * g.vl, -g.cmax, g.cmax);
-  x = (p - clo) / g.vl;
-  // a non-finite coordinate (NaN; Inf, whose neighbours clamp to finite centres and leave x = +-Inf) is made NaN here: the
-  // reference's weights are then a mixture of +-Inf and NaN whose sum is NaN or +-Inf depending on the signs of the corner
-  // values -- this operator's outputs are NaN for that sample whatever the grid holds
-  x = fabsf(x) <= 3.4028234663852886e38f ? x : __builtin_nanf("");
-  ilo = vox_id(clo, g);
-  ihi = vox_id(chi, g);
-}
-
-struct VoxCell { int ix[2], iy[2], iz[2]; float x, y, z; };
-
-__device__ __forceinline__ VoxCell vox_cell(float px, float py, float pz, const VoxGrid& g) {
-  VoxCell c;
-  vox_axis(px, g, c.ix[0], c.ix[1], c.x);
-  vox_axis(py, g, c.iy[0], c.iy[1], c.y);
-  vox_axis(pz, g, c.iz[0], c.iz[1], c.z);
-  return c;
-}
-
-// trilinear_weights (src/nerf.py:363-369): (to_val(x, bit 0) * to_val(y, bit 1)) * to_val(z, bit 2)
-__device__ __forceinline__ float vox_weight(const VoxCell& c, int u) {
-  const float wx = (u & 1) ? c.x : 1.f - c.x, wy = (u & 2) ? c.y : 1.f - c.y, wz = (u & 4) ? c.z : 1.f - c.z;
-  return (wx * wy) * wz;
-}
-
-__device__ __forceinline__ int64_t vox_row(const VoxCell& c, int u, int S) {
-  return ((int64_t)c.ix[u & 1] * S + c.iy[(u >> 1) & 1]) * S + c.iz[(u >> 2) & 1];
-}
-
-// position of sample n = t * R + r: explicit, or o + t d as na_compute_pts forms it (an fp32 multiply, then an fp32 add)
-__device__ __forceinline__ void vox_position(const float* __restrict__ pts, const float* __restrict__ rays, const float* __restrict__ ts,
-                                             int64_t R, int64_t n, float& px, float& py, float& pz) {
-  if (pts != nullptr) {
-    px = pts[n * 3]; py = pts[n * 3 + 1]; pz = pts[n * 3 + 2];
-    return;
-  }
-  const float* ry = rays + (n % R) * 6;
-  const float tt = ts[n / R];
-  px = ry[0] + tt * ry[3]; py = ry[1] + tt * ry[4]; pz = ry[2] + tt * ry[5];
-}
 
 // raw[0] = density, raw[1..3] = colour parameters: sum over the 8 corners in corner order (4-byte + 12-byte loads per corner; the
 // S = 64 grid is 4 MiB and stays in the L2 / Infinity Cache)
@@ -121,6 +45,38 @@ __global__ __launch_bounds__(256) void voxel_sample_kernel(const float* __restri
     vox_position(pts, rays, ts, R, n, px, py, pz);
     vox_gather(px, py, pz, g, den, rgb, v);
     *(float4*)(raw + n * 4) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+// ------------------------------------------------------------------------------------ gather: gradient w.r.t. the positions
+// g_pts[n, a] = (1 / voxel_len) sum_u (dw_u / dxyz_a) (g_raw[n, 0] densities[row_u] + sum_c g_raw[n, 1 + c] rgb[row_u, c]).  In the
+// reference only xyz = (p - centre of corner 0) / voxel_len depends on p -- the floors and both clamps carry no gradient -- so the
+// derivative is the one of the polynomial this cell's weights are, inside the grid and in the extrapolated region alike:
+// dw_u / dx = +-(wy wz), the sign + when corner u takes the upper cell on that axis.  A gather (no atomics), one thread per sample.
+// A non-finite coordinate makes the whole row NaN (one NaN fraction alone would leave the other two axes' sums finite).
+__global__ __launch_bounds__(256) void voxel_backward_pts_kernel(const float* __restrict__ pts, int64_t N, VoxGrid g,
+                                                                 const float* __restrict__ den, const float* __restrict__ rgb,
+                                                                 const float* __restrict__ g_raw, float* __restrict__ g_pts) {
+  for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
+    const VoxCell c = vox_cell(pts[n * 3], pts[n * 3 + 1], pts[n * 3 + 2], g);
+    const float4 gv = *(const float4*)(g_raw + n * 4);
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int64_t row = vox_row(c, u, g.S);
+      const float* q = rgb + row * 3;
+      const float v = ((gv.x * den[row] + gv.y * q[0]) + gv.z * q[1]) + gv.w * q[2];
+      const float wx = (u & 1) ? c.x : 1.f - c.x, wy = (u & 2) ? c.y : 1.f - c.y, wz = (u & 4) ? c.z : 1.f - c.z;
+      const float dx = wy * wz, dy = wx * wz, dz = wx * wy;
+      gx = gx + ((u & 1) ? dx : -dx) * v;
+      gy = gy + ((u & 2) ? dy : -dy) * v;
+      gz = gz + ((u & 4) ? dz : -dz) * v;
+    }
+    const bool bad = (c.x != c.x) | (c.y != c.y) | (c.z != c.z);
+    const float nan = __builtin_nanf("");
+    g_pts[n * 3] = bad ? nan : gx / g.vl;
+    g_pts[n * 3 + 1] = bad ? nan : gy / g.vl;
+    g_pts[n * 3 + 2] = bad ? nan : gz / g.vl;
   }
 }
 
@@ -295,13 +251,6 @@ __global__ __launch_bounds__(64) void voxel_render_kernel(const float* __restric
   }
 }
 
-static int vox_check_grid(const char* who, int S, int C, double grid_radius) {
-  NA_REQUIRE(C == 3, NA_EUNSUPPORTED, "%s: C = %d colour parameters per voxel (3 has a kernel)", who, C);
-  NA_REQUIRE(S >= 2 && S <= 1024 && S % 2 == 0, NA_EINVAL, "%s: resolution %d (even, 2 .. 1024)", who, S);
-  NA_REQUIRE(grid_radius > 0 && grid_radius < 1e30, NA_EINVAL, "%s: grid_radius %g", who, grid_radius);
-  return NA_OK;
-}
-
 }  // namespace na
 
 using namespace na;
@@ -338,6 +287,17 @@ int na_voxel_sample_backward(const float* pts, const float* rays, int64_t R, con
     return det_finish(fix + S3, S3 * 3, g_rgb, (hipStream_t)stream, "na_voxel_sample_backward");
   }
   return check_launch("na_voxel_sample_backward");
+}
+
+int na_voxel_sample_backward_pts(const float* pts, int64_t N, const float* densities, const float* rgb, const float* g_raw, int S, int C,
+                                 double grid_radius, float* g_pts, void* stream) {
+  NA_REQUIRE(N >= 0, NA_EINVAL, "na_voxel_sample_backward_pts: bad shape N=%lld", (long long)N);
+  if (int rc = vox_check_grid("na_voxel_sample_backward_pts", S, C, grid_radius)) return rc;
+  if (N == 0) return NA_OK;
+  NA_REQUIRE(pts && densities && rgb && g_raw && g_pts, NA_ENULL, "na_voxel_sample_backward_pts: null pointer");
+  hipLaunchKernelGGL(voxel_backward_pts_kernel, dim3(grid_for(N, 256)), dim3(256), 0, (hipStream_t)stream, pts, N, vox_grid(S, grid_radius),
+                     densities, rgb, g_raw, g_pts);
+  return check_launch("na_voxel_sample_backward_pts");
 }
 
 int na_voxel_render(const float* rays, const float* pts, int64_t R, const float* ts, int T, const float* densities, const float* rgb,

@@ -607,7 +607,8 @@ class NeRFVoxel(CommonNeRF):
       eval, no gradients  ops.voxel_render: positions, lookup, activation and compositing as ONE launch (two with bg "random")
       otherwise           autograd.VoxelSampleFn (lookup; its backward is the scatter-add into the two grids), the head's activation on
                           the colour columns (autograd.SigmoidFn), CommonNeRF._composite's nodes
-    There is no density noise (the reference class has no noise_std) and no gradient w.r.t. the sample positions."""
+    There is no density noise (the reference class has no noise_std).  Explicit positions that require a gradient (from_pts under
+    DynamicNeRFVoxel) receive one from the lookup's node; the positions o + t d of `forward` are formed in the kernels and have none."""
 
     def __init__(self, out_features: int = 3, resolution: int = 64, alpha_init: float = 0.1, grid_radius: float = 1.3,
                  t_near: float = 0.2, t_far: float = 2, steps: int = 64, sigmoid_kind: str = "upshifted", bg: str = "black", **kwargs):
@@ -717,9 +718,7 @@ class NeRFVoxel(CommonNeRF):
 
     def from_pts(self, pts, ts, r_o, r_d, refl_latent=None, rays=None):
         if rays is None: rays = torch.cat([r_o, r_d], dim=-1).contiguous()
-        if ag.needs_grad(pts):
-            raise NotImplementedError("NeRFVoxel: d(lookup)/d(position) has no HIP backward (sample positions that need a gradient)")
-        self.ts, self.ts_ray = ts, None
+        self.ts, self.ts_ray = ts, None  # (positions that need a gradient get one from VoxelSampleFn: ops.voxel_sample_backward_pts)
         if self._fusable(pts):
             return self._render(rays, ts, pts=pts.contiguous())
         return self._operators(rays, ts, r_d, pts=pts)
@@ -976,6 +975,75 @@ class DynamicNeRF(utils.PackedCacheMixin, nn.Module):
         return frames
 
 
+# ------------------------------------------------------------------------------------------------- DynamicNeRFVoxel
+class DynamicNeRFVoxel(nn.Module):
+    """src/nerf.py:1526-1586: a D-NeRF with no MLP.  `ctrl_pts_grid` [S,S,S,3(spline-1)] (control points 1 .. spline-1 of a Bezier
+    spline per voxel; control point 0 is zero) and `rigidity_grid` [S,S,S,1] are read by the canonical NeRFVoxel's lookup at the
+    unwarped samples; warped = pts + bezier(t) * sigmoid(rigidity) goes to canonical.from_pts (csrc/dyn_voxel.hip).  The
+    parameters keep the reference's names, so its state_dict loads.
+
+    Routes of `forward((rays, t))`:
+      eval, no gradients  ops.dyn_voxel_warp, then the canonical's one-launch render at the warped points (ops.voxel_render)
+      otherwise           autograd.DynVoxelWarpFn, then the canonical's operator route, whose lookup returns the position gradient
+    The reference marks `pts` as requiring a gradient in training for regularisers that are not built here; pts stays a
+    plain tensor and no gradient is formed for it."""
+
+    def __init__(self, canonical=None, spline: int = 4):
+        if not isinstance(canonical, NeRFVoxel):
+            raise NotImplementedError(f"--dyn-model voxel deforms a voxel model (--model voxel), got {type(canonical).__name__}: the "
+                                      "reference asserts the same (src/nerf.py:1532)")
+        if spline is None or spline <= 1:
+            raise ValueError(f"DynamicNeRFVoxel: spline {spline}, must have at least 2 control points (src/nerf.py:1533)")
+        if spline > 11:
+            raise NotImplementedError(f"DynamicNeRFVoxel: spline {spline} needs {3 * (spline - 1)} channels per voxel; the grid kernels "
+                                      f"carry {ops.GRID_MAX_C} (spline <= 11)")
+        super().__init__()
+        self.canonical = canonical
+        reso = canonical.resolution
+        self.spline = spline
+        self.ctrl_pts_grid = nn.Parameter(torch.randn([reso] * 3 + [3 * (spline - 1)]) * 0.3)
+        self.rigidity_grid = nn.Parameter(torch.zeros([reso] * 3 + [1]))
+
+    @property
+    def nerf(self): return self.canonical
+    @property
+    def refl(self): return self.canonical.refl
+    @property
+    def sdf(self): return getattr(self.canonical, "sdf", None)
+    @property
+    def intermediate_size(self): return self.canonical.intermediate_size
+    def total_latent_size(self): return self.canonical.total_latent_size()
+    @property
+    def densities(self): return self.canonical.densities
+    @property
+    def rgb(self): return self.canonical.rgb
+    def set_refl(self, r): self.canonical.set_refl(r)
+    def set_bg(self, bg): self.canonical.set_bg(bg)
+
+    def forward(self, rays_t):
+        rays, t = rays_t
+        c = self.canonical
+        if c.resolution != self.rigidity_grid.shape[0]:
+            raise ValueError(f"DynamicNeRFVoxel: the canonical grids are {c.resolution}^3 and the deformation grids "
+                             f"{self.rigidity_grid.shape[0]}^3 (the deformation grids have no resampling)")
+        self.pts, self.ts, r_o, r_d, _ = compute_pts_ts(rays, c.t_near, c.t_far, c.steps, perturb=1 if self.training else 0)
+        c.ts = self.ts
+        tt = t[None, :, None, None].expand(*self.pts.shape[:-1]).contiguous()
+        if ag.needs_grad(self.ctrl_pts_grid, self.rigidity_grid):
+            warped, self.dp, rigidity = ag.DynVoxelWarpFn.apply(self.ctrl_pts_grid, self.rigidity_grid, self.pts, tt, self.spline,
+                                                                 c.grid_radius)
+        else:
+            warped, self.dp, rigidity = ops.dyn_voxel_warp(self.pts, tt, self.ctrl_pts_grid.data, self.rigidity_grid.data, self.spline,
+                                                           c.grid_radius)
+        self.rigidity = rigidity.unsqueeze(-1)
+        return c.from_pts(warped, self.ts, r_o, r_d, rays=rays)
+
+    @property
+    def rigid_dp(self):
+        """dp * rigidity (src/nerf.py:1585), formed on demand like DynamicNeRF's"""
+        return self.dp * self.rigidity
+
+
 # ------------------------------------------------------------------------------------------------- registries
 def _experimental(name):
     def cons(*a, **k):
@@ -986,7 +1054,7 @@ def _experimental(name):
 # src/nerf.py:1706-1720 / 1698-1704: same keys
 model_kinds = {"tiny": TinyNeRF, "plain": PlainNeRF, "ae": NeRFAE, "volsdf": VolSDF, "voxel": NeRFVoxel,
                **{k: _experimental(k) for k in ["coarse_fine", "mpi", "rig", "hist"]}}
-dyn_model_kinds = {"plain": DynamicNeRF, **{k: _experimental(k) for k in ["ae", "rig", "long", "voxel"]}}
+dyn_model_kinds = {"plain": DynamicNeRF, "voxel": DynamicNeRFVoxel, **{k: _experimental(k) for k in ["ae", "rig", "long"]}}
 
 
 def load_nerf(args):
@@ -1016,9 +1084,18 @@ def load_dyn(args, model, device=None):
     if isinstance(model, NeRFAE) and cons is DynamicNeRF:
         raise NotImplementedError("--model ae under --dyn-model plain: training the deformation needs d(FourierEncoder)/d(position), which "
                                   "has no HIP backward (DESIGN.md 8); the reference's own pairing, --dyn-model ae, is broken at HEAD")
+    if cons is DynamicNeRFVoxel:
+        # (the reference passes refl_latent= to a constructor that does not take it, a TypeError: DESIGN.md 7; wired as evidently intended)
+        if not isinstance(model, NeRFVoxel):
+            raise NotImplementedError(f"--dyn-model voxel over --model {args.model}: the deformation grids are read with NeRFVoxel's cells, "
+                                      "it needs --model voxel (the reference asserts the same, src/nerf.py:1532)")
+        if args.dyn_refl_latent > 0:
+            raise NotImplementedError(f"--dyn-refl-latent {args.dyn_refl_latent} under --dyn-model voxel: DynamicNeRFVoxel has no "
+                                      "reflectance latent (src/nerf.py:1526-1531)")
+        return cons(canonical=model, spline=args.spline)
     if isinstance(model, NeRFVoxel):
-        raise NotImplementedError(f"--model voxel under --dyn-model {args.dyn_model}: training the deformation needs the gradient of the grid "
-                                  "lookup w.r.t. the sample positions, which has no HIP backward (DESIGN.md 8)")
+        raise NotImplementedError(f"--model voxel under --dyn-model {args.dyn_model}: only --dyn-model voxel deforms the sample positions of "
+                                  "a voxel model (no fixture pins this pairing, DESIGN.md 8)")
     if isinstance(model, VolSDF) and cons is DynamicNeRF and args.dyn_refl_latent > 0:
         raise NotImplementedError("--dyn-refl-latent over --model volsdf: VolSDF.from_pts drops the reflectance latent (src/nerf.py:995-1013) "
                                   "while the head is built for it (runner.py:1182-1183), so the reference's first forward raises a shape error")

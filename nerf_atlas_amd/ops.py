@@ -1728,6 +1728,94 @@ def voxel_render(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, 
     return out, alpha, weights
 
 
+def voxel_sample_backward_pts(g_raw: torch.Tensor, pts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor,
+                              grid_radius: float) -> torch.Tensor:
+    """g_pts [..., 3]: the gradient of voxel_sample w.r.t. explicit pts [..., 3] given g_raw [..., 1 + C] (a gather: one launch, no atomics)"""
+    lib = _lib.load()
+    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
+    pts, _, _, N, _, _ = _voxel_positions(pts, None, None)
+    g_raw = _f32(g_raw, "g_raw")
+    if g_raw.shape[-1] != 1 + Cn or g_raw.numel() != N * (1 + Cn):
+        raise ValueError(f"g_raw must be [..., {1 + Cn}] with one row per sample ({N}), got {tuple(g_raw.shape)}")
+    g_raw = _aligned16(g_raw)
+    g_pts = torch.empty(pts.shape, device=pts.device, dtype=torch.float32)
+    check(lib.na_voxel_sample_backward_pts(_ptr(pts), N, _ptr(densities), _ptr(rgb), _ptr(g_raw), S, Cn, float(grid_radius), _ptr(g_pts),
+                                           _stream()))
+    return g_pts
+
+
+# ------------------------------------------------------------------------------------------------- DynamicNeRFVoxel (csrc/dyn_voxel.hip)
+def _dyn_voxel_grids(ctrl_pts_grid: torch.Tensor, rigidity_grid: torch.Tensor, spline: int):
+    """S of ctrl_pts_grid [S,S,S,3(spline-1)] and rigidity_grid [S,S,S,1]"""
+    ctrl, rig = _f32(ctrl_pts_grid, "ctrl_pts_grid"), _f32(rigidity_grid, "rigidity_grid")
+    _dyn_voxel_spline(spline)
+    S = rig.shape[0]
+    if rig.dim() != 4 or tuple(rig.shape) != (S, S, S, 1) or tuple(ctrl.shape) != (S, S, S, 3 * (spline - 1)):
+        raise ValueError(f"dyn voxel grids must be ctrl_pts_grid [S,S,S,{3 * (spline - 1)}] and rigidity_grid [S,S,S,1], got "
+                         f"{tuple(ctrl.shape)} and {tuple(rig.shape)}")
+    _dyn_voxel_reso(S)
+    return ctrl, rig, S
+
+
+def _dyn_voxel_spline(spline: int):
+    if not 2 <= spline <= 11:
+        raise ValueError(f"spline {spline}: 2 .. 11 control points have a kernel (3 (spline - 1) <= {GRID_MAX_C} channels per voxel)")
+
+
+def _dyn_voxel_reso(S: int):
+    if S % 2 != 0 or not 2 <= S <= 1024:
+        raise ValueError(f"voxel resolution {S}: even resolutions 2 .. 1024 only (the reference's ids are floor(.) + S / 2)")
+
+
+def _dyn_voxel_samples(pts: torch.Tensor, t: torch.Tensor):
+    pts, t = _f32(pts, "pts"), _f32(t, "t")
+    if pts.shape[-1] != 3 or tuple(t.shape) != tuple(pts.shape[:-1]):
+        raise ValueError(f"pts must be [..., 3] and t [...] (one time per sample, expanded by the caller), got {tuple(pts.shape)} and "
+                         f"{tuple(t.shape)}")
+    return pts, t, pts.numel() // 3
+
+
+def dyn_voxel_warp(pts: torch.Tensor, t: torch.Tensor, ctrl_pts_grid: torch.Tensor, rigidity_grid: torch.Tensor, spline: int,
+                   grid_radius: float):
+    """DynamicNeRFVoxel's deformation (src/nerf.py:1571-1586) as ONE launch: (warped [..., 3], dp [..., 3], rigidity [...]) of pts [..., 3]
+    at times t [...]: the two grids interpolated at the unwarped points, the Bezier spline, warped = pts + dp * rigidity."""
+    lib = _lib.load()
+    ctrl, rig, S = _dyn_voxel_grids(ctrl_pts_grid, rigidity_grid, spline)
+    pts, t, N = _dyn_voxel_samples(pts, t)
+    warped, dp = torch.empty_like(pts), torch.empty_like(pts)
+    rigidity = torch.empty(pts.shape[:-1], device=pts.device, dtype=torch.float32)
+    check(lib.na_dyn_voxel_warp(_ptr(pts), _ptr(t), N, _ptr(ctrl), _ptr(rig), S, spline, float(grid_radius), _ptr(warped), _ptr(dp),
+                                _ptr(rigidity), _stream()))
+    return warped, dp, rigidity
+
+
+def dyn_voxel_warp_backward(pts: torch.Tensor, t: torch.Tensor, dp: torch.Tensor, rigidity: torch.Tensor, S: int, spline: int,
+                            grid_radius: float, g_warped: Optional[torch.Tensor] = None, g_dp: Optional[torch.Tensor] = None,
+                            g_rigidity: Optional[torch.Tensor] = None):
+    """(g_ctrl_pts_grid [S,S,S,3(spline-1)], g_rigidity_grid [S,S,S,1]) of dyn_voxel_warp given any of g_warped, g_dp [..., 3] and
+    g_rigidity [...] (None = zero) and the forward's dp and rigidity"""
+    lib = _lib.load()
+    _dyn_voxel_spline(spline)
+    _dyn_voxel_reso(S)
+    pts, t, N = _dyn_voxel_samples(pts, t)
+    dp, rigidity = _f32(dp, "dp"), _f32(rigidity, "rigidity")
+    if dp.shape != pts.shape or rigidity.numel() != N:
+        raise ValueError(f"dp must be {tuple(pts.shape)} and rigidity one value per sample, got {tuple(dp.shape)} and {tuple(rigidity.shape)}")
+    grads = []
+    for name, g, numel in (("g_warped", g_warped, 3 * N), ("g_dp", g_dp, 3 * N), ("g_rigidity", g_rigidity, N)):
+        if g is not None:
+            g = _f32(g, name)
+            if g.numel() != numel:
+                raise ValueError(f"{name} has {g.numel()} elements, {numel} expected")
+        grads.append(g)
+    config.require_deterministic_workspace(8 * S ** 3 * (3 * spline - 2))  # (a no-op outside config.set_deterministic's mode)
+    g_ctrl = torch.zeros(S, S, S, 3 * (spline - 1), device=pts.device, dtype=torch.float32)
+    g_rig = torch.zeros(S, S, S, 1, device=pts.device, dtype=torch.float32)
+    check(lib.na_dyn_voxel_warp_backward(_ptr(pts), _ptr(t), N, _ptr(dp), _ptr(rigidity), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]),
+                                         S, spline, float(grid_radius), _ptr(g_ctrl), _ptr(g_rig), _stream()))
+    return g_ctrl, g_rig
+
+
 # ------------------------------------------------------------------------------------------------- grid operators (csrc/grid_ops.hip)
 GRID_MAX_C = 32
 
@@ -1778,6 +1866,7 @@ def grid_tv_backward(grid: torch.Tensor, idxs: torch.Tensor, g: torch.Tensor, tr
     grid = _grid4(grid)
     idxs = _grid_idxs(grid, idxs, trusted)
     g = _f32(g.reshape(1), "g")
+    config.require_deterministic_workspace(8 * grid.numel())  # (ctrl_pts_grid at S = 64 is larger than config's default workspace)
     out = torch.zeros_like(grid)
     s0, s1, s2, Cn = grid.shape
     check(lib.na_grid_tv_backward(_ptr(grid), s0, s1, s2, Cn, _ptr(idxs), idxs.numel(), _ptr(g), _ptr(out), _stream()))

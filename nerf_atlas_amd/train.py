@@ -5,7 +5,7 @@ in training mode, `--volsdf-scale-decay`, `--delta-x-decay`, `--offset-decay`, `
 tangents through the MLP), `--smooth-normals` in the reference's default epsilon-perturbation form (`--smooth-eps`,
 `--smooth-eps-rng`, `--smooth-n-ord`), `--dyn-diverge-decay` (one differentiable direction tangent), `--ffjord-div-decay`
 (forward-mode divergence estimate), `--voxel-tv-sigma` / `--voxel-tv-rgb` (total variation of NeRFVoxel's grids) and this build's
-`--voxel-upsample ITER:RESO`; `--smooth-normals --smooth-eps 0` (double backward) raises.
+`--voxel-upsample ITER:RESO`; over `--dyn-model voxel` also `--voxel-tv-bezier` / `--voxel-tv-rigidity`; `--smooth-normals --smooth-eps 0` (double backward) raises.
 
 Every forward and backward is a HIP kernel (nerf_atlas_amd/autograd.py); the parameter update is the reference's table of torch.optim
 classes (`--opt-kind adam | sgd | adamw | rmsprop`, `--decay`), each with its step as one HIP launch (load_optim below).
@@ -366,6 +366,8 @@ def unset_voxel_tv(args, model):
     never an error.  (The reference's second test forgets --voxel-tv-rigidity and dies in its first iteration when that weight alone is
     set on a non-voxel model; here it is unset with the others.)"""
     tv_dyn = args.voxel_tv_bezier > 0 or args.voxel_tv_rigidity > 0
+    if isinstance(model, nerf.DynamicNeRFVoxel):
+        return  # (all four grids exist: every weight is kept, runner.py:1137)
     if isinstance(model, nerf.NeRFVoxel):
         if tv_dyn:
             print("[warn]: model does not have bezier control points or rigidity for static scene")
@@ -399,6 +401,13 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
     optimiser step (dist.allreduce_gradients); the reference's own --data-parallel is broken (SURVEY header table)."""
     if args.epochs == 0:
         return []
+    dyn_voxel = isinstance(model, nerf.DynamicNeRFVoxel)
+    if dyn_voxel:
+        # both terms differentiate rigid_dp / dp w.r.t. the sample positions (runner.py:694-699), which the deformation's node does not form
+        for flag in ("ffjord_div_decay", "dyn_diverge_decay"):
+            if getattr(args, flag, 0):
+                raise NotImplementedError(f"--{flag.replace('_', '-')} over --dyn-model voxel needs d(dp)/d(pts) of the grid lookup, "
+                                          "which is not built (DESIGN.md 8)")
     if getattr(args, "dyn_diverge_decay", 0) > 0 and not hasattr(model, "sum_jacobian_div"):
         raise ValueError("--dyn-diverge-decay needs a dynamic model (--data-kind dnerf --dyn-model plain --spline N): the "
                          "reference reads model.pts / model.dp (runner.py:694-696)")
@@ -416,8 +425,12 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
         raise NotImplementedError("--sdf-eikonal under a dynamic model: the reference's second, dynamic-only eikonal term (runner.py:804-808) "
                                   "adds the points to the (dp, enc) tuple of DynamicNeRF.time_estim and raises a TypeError in its first "
                                   "iteration; `make dnerf_volsdf` (makefile:127-133) trains without --sdf-eikonal")
-    voxel_tv = getattr(args, "voxel_tv_sigma", 0) > 0 or getattr(args, "voxel_tv_rgb", 0) > 0
+    tv_dyn = dyn_voxel and (getattr(args, "voxel_tv_bezier", 0) > 0 or getattr(args, "voxel_tv_rigidity", 0) > 0)
+    voxel_tv = getattr(args, "voxel_tv_sigma", 0) > 0 or getattr(args, "voxel_tv_rgb", 0) > 0 or tv_dyn
     upsample_at = dict(parse_voxel_upsample(getattr(args, "voxel_upsample", [])))
+    if upsample_at and dyn_voxel:
+        raise ValueError("--voxel-upsample with --dyn-model voxel: the reference has no resampling of ctrl_pts_grid / rigidity_grid "
+                         "(src/nerf.py:1526-1586), so the deformation grids would keep the old resolution")
     if (voxel_tv or upsample_at) and not isinstance(model.nerf, nerf.NeRFVoxel):
         raise ValueError(f"{'--voxel-upsample' if upsample_at else '--voxel-tv-sigma / --voxel-tv-rgb'} needs --model voxel (fit() unsets the "
                          "total-variation weights of another model with the reference's warning)")
@@ -444,7 +457,9 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
                          f"(every replica renders batch_size / world views per step)")
     losses = []
     reg_terms = train.last_reg_terms = []  # (the --dyn-diverge-decay term per iteration: a diagnostic next to the losses)
-    tv_terms = train.last_tv_terms = []    # ([TV(densities), TV(rgb)] per iteration, device scalars: read after the run, no sync in the loop)
+    # ([TV(densities), TV(rgb)] per iteration, + [TV(ctrl_pts_grid), TV(rigidity_grid)] for DynamicNeRFVoxel; device scalars: read after
+    # the run, no sync in the loop)
+    tv_terms = train.last_tv_terms = []
     model.train()
     opt.zero_grad()
     for i in range(args.epochs):
@@ -516,7 +531,7 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
         if voxel_tv:
             # runner.py:772-773: one draw of 32^3 voxels per term, densities first (every data-parallel rank draws the same ones from
             # the same seed, so the averaged gradient is the single-process one)
-            tv_terms.append([float("nan"), float("nan")])
+            tv_terms.append([float("nan")] * (4 if dyn_voxel else 2))
             if args.voxel_tv_sigma > 0:
                 tv = nerf.total_variation(model.nerf.densities)
                 tv_terms[-1][0] = tv.detach()
@@ -525,6 +540,15 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
                 tv = nerf.total_variation(model.nerf.rgb)
                 tv_terms[-1][1] = tv.detach()
                 loss = loss + args.voxel_tv_rgb * tv
+            # runner.py:774-775: the deformation grids after them, in the reference's draw order
+            if tv_dyn and args.voxel_tv_bezier > 0:
+                tv = nerf.total_variation(model.ctrl_pts_grid)
+                tv_terms[-1][2] = tv.detach()
+                loss = loss + args.voxel_tv_bezier * tv
+            if tv_dyn and args.voxel_tv_rigidity > 0:
+                tv = nerf.total_variation(model.rigidity_grid)
+                tv_terms[-1][3] = tv.detach()
+                loss = loss + args.voxel_tv_rigidity * tv
         if args.opt_step != 1:
             loss = loss / args.opt_step
         loss.backward()

@@ -1110,9 +1110,72 @@ def g24():
              value64=value64, grad64=g64.grad)
 
 
+DYN_VOXEL_CASES = {  # name: (S, spline, T, ray batch shape [B, H, W], times [B], act, bg)
+    "s2_n2": (2, 2, 7, (2, 4, 4), (0.0, 1.0), "thin", "black"),
+    "s4_n4": (4, 4, 16, (3, 4, 4), (0.0, 0.6, 1.0), "upshifted", "white"),
+    "s16_n5_ragged": (16, 5, 24, (2, 5, 7), (0.25, 0.8), "leaky_relu", "black"),
+    "s16_n11": (16, 11, 24, (2, 4, 4), (0.3, 0.9), "upshifted", "black"),
+    "s64_n4": (64, 4, 64, (2, 4, 4), (0.25, 0.8), "upshifted", "black"),  # forward only
+}
+DYN_VOXEL_GRADS = ("canonical.densities", "canonical.rgb", "ctrl_pts_grid", "rigidity_grid")
+
+
+def g25():
+    """g25_dyn_voxel_<case>: the reference's DynamicNeRFVoxel (src/nerf.py:1526-1586) over its NeRFVoxel + Positional, all three built
+    directly (load_dyn's own call is a TypeError: DESIGN.md 7), eval mode, near 2 / far 6, procedural grids (stored as specs; proc_param
+    fills rigidity_grid too, so the rigidity is not the constant 1/2 of the zero init), voxel_ref.generic_rays and 2-3 times per batch,
+    in fp32 AND fp64: out, alpha, weights, dp, rigidity and the reference's own fp32 - fp64 deviation.  g23's rule: a seed on which
+    the two precisions disagree by more than 1e-5 pins nothing and is skipped; no agreeing seed is an error.  S <= 16 also stores the
+    fp64 gradients of the four grids for loss = sum(out^2) and how far the reference's own fp32 gradients are from them (`g_dev`, in units
+    of the largest fp64 entry, in DYN_VOXEL_GRADS' order)."""
+    import copy
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import voxel_ref as V
+    for name, (S, spline, T, shape, times, act, bg) in DYN_VOXEL_CASES.items():
+        canon, _, _ = _voxel_build(S, T, act, bg)
+        m = rnerf.DynamicNeRFVoxel(canon, spline=spline)
+        m.eval()
+        names, shapes = fill_procedural(m)
+        m64 = copy.deepcopy(m).double()
+        t = torch.tensor(times, dtype=torch.float32)
+        keys = ("out", "alpha", "weights", "dp", "rigidity")
+
+        def run(model, dt, rays):
+            out = model((rays.to(dt), t.to(dt)))
+            return dict(out=out, alpha=model.canonical.alpha, weights=model.canonical.weights, dp=model.dp, rigidity=model.rigidity)
+        for seed in range(4500, 4600, 2):
+            rays = V.generic_rays(shape, seed)
+            r32, r64 = run(m, torch.float32, rays), run(m64, torch.float64, rays)
+            dev = {k: float((r32[k].double() - r64[k]).abs().max()) for k in keys}
+            if max(dev.values()) <= 1e-5:
+                break
+            print(f"g25 {name}: seed {seed} skipped, the reference's fp32 and fp64 disagree by {max(dev.values()):.2e}")
+        else:
+            raise AssertionError(f"g25 {name}: no seed on which the reference agrees with itself")
+        opac = r64["weights"][:-1].sum(0)
+        print(f"g25 {name}: seed {seed}, opacity before the last sample {float(opac.min()):.2f}..{float(opac.max()):.2f}, |dp| up to "
+              f"{float(r64['dp'].abs().max()):.2f}, rigidity {float(r64['rigidity'].min()):.2f}..{float(r64['rigidity'].max()):.2f}; "
+              "fp32 vs fp64: " + " ".join(f"{k} {v:.2e}" for k, v in dev.items()))
+        kw = dict(rays=rays, times=t, S=S, spline=spline, steps=T, near=2.0, far=6.0, act=act, bg=bg, grid_radius=canon.grid_radius, seed=seed,
+                  ts=m.ts, dev=np.array([dev[k] for k in keys]), **spec(names, shapes))
+        for k in keys:
+            kw[k], kw[k + "64"] = r32[k], r64[k]
+        if S <= 16:
+            for model, dt in ((m64, torch.float64), (m, torch.float32)):
+                with torch.enable_grad():
+                    for p_ in model.parameters(): p_.requires_grad_(True)
+                    model((rays.to(dt), t.to(dt))).square().sum().backward()
+            g32, g64 = dict(m.named_parameters()), dict(m64.named_parameters())
+            g_dev = [float((g32[k].grad.double() - g64[k].grad).abs().max() / g64[k].grad.abs().max()) for k in DYN_VOXEL_GRADS]
+            print(f"g25 {name}: the reference's fp32 gradients are " + " / ".join(f"{v:.2e}" for v in g_dev)
+                  + " of the largest entry off its fp64 ones (densities, rgb, ctrl_pts_grid, rigidity_grid)")
+            kw.update(g_dev=np.array(g_dev), **{"grad64." + k: g64[k].grad for k in DYN_VOXEL_GRADS})
+        save(f"g25_dyn_voxel_{name}", **kw)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25"]
     for g in which:
         globals()[g]()
     with open(os.path.join(OUT, "PROVENANCE.txt"), "w") as f:
