@@ -848,6 +848,38 @@ int na_grid_tv_backward(const float* grid, int s0, int s1, int s2, int C, const 
                         float* g_grid, void* stream);
 int na_grid_upsample(const float* src, int S, float* dst, int R, int C, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Spline-length regularisers of DynamicNeRFVoxel (arc_len, src/nerf.py:1509-1520; csrc/spline_len.hip): the length of the polyline
+ * through the M points de_casteljau(control points, t[j]), j = 0 .. M-1, in the reference's fp32 operations.  t [M] is an input table
+ * (the caller passes torch.linspace(0, 1, M)'s own values); M is 2 .. 32 (else NA_EUNSUPPORTED).  A segment of length 0 adds 0 to
+ * the length and exactly 0 to the gradient.  out is TWO floats zeroed by the caller (na_grid_tv's protocol: out[1] counts the
+ * arriving waves); under na_set_deterministic the waves' partial sums are combined in 2^-40 fixed point and the value is bitwise
+ * reproducible.  Every entry point is one launch.
+ * na_grid_spline_len                 grid [rows, 3 m]: the m = 1 .. 10 control points of a row (no zero point is prepended); idxs [K]
+ *                                    int64 flat rows, clamped to 0 .. rows-1 before any address is formed.  lens (NULL or [K]) = the
+ *                                    length per index, out[0] = their mean.
+ * na_grid_spline_len_backward        g_grid [rows, 3 m] += the gradient of that mean times the device scalar g_up[0] (g_grid zeroed by
+ *                                    the caller); duplicates of an index add up.  fp32 atomics by default; under na_set_deterministic
+ *                                    every addend goes through 2^-40 fixed point on its own (workspace >= 8 rows 3 m bytes, else
+ *                                    NA_EWORKSPACE) and the result is bitwise independent of the order of idxs.
+ * na_dyn_voxel_spline_len            per sample of pts [N,3]: control points 1 .. n-1 interpolated from ctrl_pts_grid [S,S,S,3(n-1)] by
+ *                                    NeRFVoxel's lookup (the cells, weights and memory-safety rule of na_dyn_voxel_warp) behind the
+ *                                    zero control point 0, n = n_ctrl in 2 .. 11.  lens (NULL or [N]) = the length per sample,
+ *                                    out[0] = mean over N of w[n] lens[n]; w is NULL (1) or [N].  A non-finite coordinate makes
+ *                                    that sample's length, and the value, NaN.
+ * na_dyn_voxel_spline_len_backward   g_ctrl_pts_grid += (zeroed by the caller) the gradient of that mean times g_up[0]: control
+ *                                    block k of the 8 rows of a sample gets w_u (g_up w[n] / N) sum_j dir_j (B_k(t[j+1]) - B_k(t[j])),
+ *                                    dir_j the unit direction of segment j.  No gradient w.r.t. pts or w.  Accumulation modes as
+ *                                    na_dyn_voxel_warp_backward (workspace >= 8 S^3 3(n-1) bytes).                                 */
+int na_grid_spline_len(const float* grid, int64_t rows, int m, const int64_t* idxs, int64_t K, const float* t, int M, float* lens, float* out,
+                       void* stream);
+int na_grid_spline_len_backward(const float* grid, int64_t rows, int m, const int64_t* idxs, int64_t K, const float* t, int M,
+                                const float* g_up, float* g_grid, void* stream);
+int na_dyn_voxel_spline_len(const float* pts, int64_t N, const float* ctrl_pts_grid, int S, int n_ctrl, double grid_radius, const float* w,
+                            const float* t, int M, float* lens, float* out, void* stream);
+int na_dyn_voxel_spline_len_backward(const float* pts, int64_t N, const float* ctrl_pts_grid, int S, int n_ctrl, double grid_radius,
+                                     const float* w, const float* t, int M, const float* g_up, float* g_ctrl_pts_grid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -579,3 +579,36 @@ class DynVoxelWarpFn(Function):
         pts, t, dp, rigidity = ctx.saved_tensors
         g_ctrl, g_rig = ops.dyn_voxel_warp_backward(pts, t, dp, rigidity, ctx.S, ctx.spline, ctx.grid_radius, g_warped, g_dp, g_rigidity)
         return g_ctrl, g_rig, None, None, None, None
+
+
+class GridSplineLenFn(Function):
+    """mean arc length of the splines stored in the rows idxs of a control-point grid (ops.grid_spline_len: one launch); backward is
+    ops.grid_spline_len_backward, one launch that recomputes the points and reads the upstream scalar on the device."""
+
+    @staticmethod
+    def forward(ctx, grid, idxs, trusted):
+        ctx.save_for_backward(grid, idxs)
+        return ops.grid_spline_len(grid, idxs, trusted)
+
+    @staticmethod
+    def backward(ctx, g):
+        grid, idxs = ctx.saved_tensors
+        return ops.grid_spline_len_backward(grid, idxs, g.contiguous(), True), None, None  # (the forward checked the indices)
+
+
+class DynVoxelSplineLenFn(Function):
+    """mean over the samples of w * arc length of the sample's interpolated spline (ops.dyn_voxel_spline_len: one launch); backward is
+    one scatter-add into ctrl_pts_grid (ops.dyn_voxel_spline_len_backward).  pts and w carry no gradient (the reference detaches the
+    weights, and the positions are a leaf)."""
+
+    @staticmethod
+    def forward(ctx, ctrl_pts_grid, pts, w, spline, grid_radius):
+        ctx.save_for_backward(ctrl_pts_grid, pts, *(() if w is None else (w,)))
+        ctx.spline, ctx.grid_radius = spline, grid_radius
+        return ops.dyn_voxel_spline_len(pts, ctrl_pts_grid, spline, grid_radius, w)
+
+    @staticmethod
+    def backward(ctx, g):
+        ctrl, pts, *w = ctx.saved_tensors
+        g_ctrl = ops.dyn_voxel_spline_len_backward(pts, ctrl, ctx.spline, ctx.grid_radius, g.contiguous(), w[0] if w else None)
+        return g_ctrl, None, None, None, None

@@ -8,7 +8,7 @@
 // Two operators: the deformation as one launch (na_dyn_voxel_warp: a gather of 8 rows of 1 + 3(n-1) floats, the spline) and its
 // backward (na_dyn_voxel_warp_backward: a scatter-add into the two grids on voxel_backward_kernel's scheme).  There is no gradient
 // w.r.t. pts: they are a leaf in the reference.  Kernels are instantiated per n = 2 .. 11 so that the control points stay in registers.
-#include "voxel_cell.h"
+#include "dyn_voxel_scatter.h"
 
 namespace na {
 
@@ -99,29 +99,17 @@ __global__ __launch_bounds__(256) void dyn_voxel_warp_kernel(const float* __rest
 // ------------------------------------------------------------------------------------ scatter-add into the two grids
 // With r the rigidity, G = g_warped, D = G r + g_dp and q = (G . dp + g_rigidity) r (1 - r), corner u of a sample adds
 //   w_u B_k(t) D  to channels 3(k-1) .. 3k-1 of ctrl row_u  (k = 1 .. n-1)      and      w_u q  to rigidity row_u:
-// one "wide row" of W = 1 + 3(n-1) sums per grid row, [rigidity | control channels].  The scheme is voxel_backward_kernel's: a
-// workgroup takes a contiguous run of samples, sums into a hashed LDS table of ROWS wide rows (multiplicative hash, NA_DV_PROBES linear
-// probes, a slot is never freed), flushes it once, and a row that finds no slot falls through to the global accumulators.  A slot is
-// 8 bytes per sum (the fixed-point mode's integers; the fp32 mode uses the low word), so ROWS shrinks with W to keep the table and
-// its tags inside 64 KB -- two workgroups per CU of 160 KB LDS: 1024 rows for W <= 7, 512 for W <= 13, 256 up to W = 31 (62 KB).
-// The flush walks the table element by element, so the lanes of a wave add to consecutive floats of consecutive table rows
-// (segments of 4 W bytes), not one lane per row.  dp and rigidity are the forward's outputs (16 bytes per sample instead of
-// gathering the 8 rows again).  Deterministic mode: every contribution to 2^-40 fixed point on its own, as voxel_backward_kernel.
-#ifndef NA_DV_PROBES
-#define NA_DV_PROBES 4
-#endif
-constexpr int DV_WG = 4096;  // workgroups at most: a workgroup's run is ceil(N / DV_WG) samples rounded up to whole rounds of 256
-constexpr int dv_rows(int W) { return W <= 7 ? 1024 : W <= 13 ? 512 : 256; }
-constexpr int dv_log2(int v) { return v <= 1 ? 0 : 1 + dv_log2(v / 2); }
-
+// one "wide row" of W = 1 + 3(n-1) sums per grid row, [rigidity | control channels], summed by the scheme of dyn_voxel_scatter.h (a
+// contiguous run of samples per workgroup, a hashed LDS table, one flush).  dp and rigidity are the forward's outputs (16 bytes per
+// sample instead of gathering the 8 rows again).  Deterministic mode: every contribution to 2^-40 fixed point on its own, as
+// voxel_backward_kernel.
 template <int NC>
 __global__ __launch_bounds__(256) void dyn_voxel_warp_backward_kernel(const float* __restrict__ pts, const float* __restrict__ t, int64_t N,
                                                                       VoxGrid g, const float* __restrict__ dp, const float* __restrict__ rigidity,
                                                                       const float* __restrict__ g_warped, const float* __restrict__ g_dp,
                                                                       const float* __restrict__ g_rigidity, float* __restrict__ g_ctrl,
                                                                       float* __restrict__ g_rig, long long* __restrict__ fix) {
-  constexpr int CH = 3 * (NC - 1), W = CH + 1, ROWS = dv_rows(W), SHIFT = 32 - dv_log2(ROWS);
-  static_assert(ROWS * W * 8 + ROWS * 4 <= 65536, "the table and its tags stay inside 64 KB of LDS");
+  constexpr int CH = 3 * (NC - 1), W = CH + 1, ROWS = DvTable<W>::ROWS;
   const int64_t S3 = (int64_t)g.S * g.S * g.S;
   long long* fix_rig = fix != nullptr ? fix + S3 * CH : nullptr;
   auto add_global = [&](uint32_t id, int e, float v) {
@@ -130,33 +118,10 @@ __global__ __launch_bounds__(256) void dyn_voxel_warp_backward_kernel(const floa
   };
   __shared__ uint32_t tags[ROWS];
   __shared__ unsigned long long vals[ROWS * W];
-  for (int i = threadIdx.x; i < ROWS; i += 256) tags[i] = 0xffffffffu;
-  for (int i = threadIdx.x; i < ROWS * W; i += 256) vals[i] = 0ull;
-  __syncthreads();
-  // W sums for one grid row: the slot of the id (NA_DV_PROBES linear probes from its hash; a slot is never freed, so an id finds the same
-  // slot every time, or none), else the global accumulators
-  auto add_row = [&](uint32_t id, float w, const float (&sv)[W]) {
-    const uint32_t home = (id * 2654435761u) >> SHIFT;
-#pragma unroll
-    for (int p = 0; p < NA_DV_PROBES; ++p) {
-      const uint32_t row = (home + p) & (ROWS - 1);
-      const uint32_t old = atomicCAS(&tags[row], 0xffffffffu, id);
-      if (old == 0xffffffffu || old == id) {
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-          const float v = w * sv[e];
-          if (fix == nullptr) atomicAdd((float*)&vals[row * W + e], v);
-          else if (fabsf(v) < 1048576.0f) atomicAdd(&vals[row * W + e], (unsigned long long)__float2ll_rn(v * kFixScale));
-          else add_global(id, e, v);  // (out of the fixed-point range, NaN: the fp32 path, as accumulate() does)
-        }
-        return;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < W; ++e) add_global(id, e, w * sv[e]);
-  };
-  const int64_t per = ((N + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;  // samples of this workgroup: whole rounds
-  const int64_t n_lo = blockIdx.x * per, n_hi = n_lo + per < N ? n_lo + per : N;
+  const DvTable<W> table{tags, vals, fix};
+  table.clear();
+  int64_t n_lo, n_hi;
+  dv_run(N, n_lo, n_hi);
   for (int64_t base = n_lo; base < n_hi; base += 256) {
     const int64_t n = base + threadIdx.x;
     if (n >= n_hi) continue;  // (no barrier inside the loop)
@@ -179,40 +144,14 @@ __global__ __launch_bounds__(256) void dyn_voxel_warp_backward_kernel(const floa
       for (int a = 0; a < 3; ++a) sv[1 + 3 * (k - 1) + a] = B[k] * D[a];
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) add_row((uint32_t)vox_row(c, u, g.S), vox_weight(c, u), sv);
+    for (int u = 0; u < 8; ++u) table.add_row((uint32_t)vox_row(c, u, g.S), vox_weight(c, u), sv, add_global);
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < ROWS * W; i += 256) {
-    const int row = i / W, e = i - row * W;
-    const uint32_t id = tags[row];
-    if (id == 0xffffffffu) continue;
-    const unsigned long long v = vals[i];
+  table.flush([&](uint32_t id, int e, unsigned long long v) {
     const int64_t at = e == 0 ? (int64_t)id : (int64_t)id * CH + (e - 1);
     if (fix == nullptr) atomicAdd((e == 0 ? g_rig : g_ctrl) + at, __uint_as_float((uint32_t)v));
     else atomicAdd((unsigned long long*)((e == 0 ? fix_rig : fix) + at), v);
-  }
+  });
 }
-
-static int dv_check(const char* who, int64_t N, int S, int n_ctrl, double grid_radius) {
-  NA_REQUIRE(N >= 0, NA_EINVAL, "%s: bad shape N=%lld", who, (long long)N);
-  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED, "%s: spline %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", who,
-             n_ctrl);
-  return vox_check_grid(who, S, 3, grid_radius);
-}
-
-#define NA_DV_DISPATCH(N_CTRL, LAUNCH) \
-  switch (N_CTRL) {                    \
-    case 2: LAUNCH(2); break;          \
-    case 3: LAUNCH(3); break;          \
-    case 4: LAUNCH(4); break;          \
-    case 5: LAUNCH(5); break;          \
-    case 6: LAUNCH(6); break;          \
-    case 7: LAUNCH(7); break;          \
-    case 8: LAUNCH(8); break;          \
-    case 9: LAUNCH(9); break;          \
-    case 10: LAUNCH(10); break;        \
-    default: LAUNCH(11); break;        \
-  }
 
 }  // namespace na
 

@@ -597,6 +597,24 @@ def total_variation(grid, samples: int = 32 ** 3, idxs=None):
     return ops.grid_tv(grid.detach(), idxs, trusted)
 
 
+def arc_len_grid(grid, samples: int = 16 ** 3, idxs=None):
+    """runner.py:793-796 as one launch forward and one backward (autograd.GridSplineLenFn): the mean of arc_len
+    (src/nerf.py:1509-1520) over `samples` voxels of a control-point grid [s0,s1,s2,3 m] drawn by random_sample_grid, each voxel's
+    channels read as its m control points (no zero point in front).  idxs: explicit flat indices as random_sample_grid returns them
+    (range-checked on the host) instead of a draw; x = idx % s0 is the slowest axis in memory, as in total_variation."""
+    trusted = idxs is None
+    s0, s1, s2, _ = grid.shape
+    if trusted:
+        idxs = random_sample_grid(grid, samples)
+    elif bool(((idxs < 0) | (idxs >= s0 * s1 * s2)).any()):
+        raise ValueError(f"idxs outside the grid: flat indices 0 .. {s0 * s1 * s2 - 1}")
+    # the reference decodes the draw as grid[idx % s0, idx // s0 % s1, idx // (s0 s1) % s2]: that voxel's row in memory
+    rows = ((idxs % s0) * s1 + idxs // s0 % s1) * s2 + idxs // (s0 * s1) % s2
+    if ag.needs_grad(grid):
+        return ag.GridSplineLenFn.apply(grid, rows, True)
+    return ops.grid_spline_len(grid.detach(), rows, True)
+
+
 # ------------------------------------------------------------------------------------------------- NeRFVoxel
 class NeRFVoxel(CommonNeRF):
     """src/nerf.py:401-524: a dense grid of densities [S,S,S,1] and per-voxel colour parameters rgb [S,S,S,C], read by the reference's
@@ -1042,6 +1060,22 @@ class DynamicNeRFVoxel(nn.Module):
     def rigid_dp(self):
         """dp * rigidity (src/nerf.py:1585), formed on demand like DynamicNeRF's"""
         return self.dp * self.rigidity
+
+    def spline_len(self, weights=None):
+        """runner.py:784-787: the mean over the samples of the last forward of weights * arc_len(the sample's spline), the n control
+        points interpolated at the unwarped `pts` with zero first (they exist only inside the kernels: autograd.DynVoxelSplineLenFn,
+        DESIGN.md 3n).  weights [T, ...batch] (the canonical's compositing weights, used detached) or None for 1.  The per-sample mean
+        for any batch size; the reference's own expression runs at one view only and equals it there."""
+        if getattr(self, "pts", None) is None:
+            raise RuntimeError("DynamicNeRFVoxel.spline_len reads the sample positions of the last forward: render first")
+        if weights is not None:
+            if weights.numel() != self.pts.numel() // 3:
+                raise ValueError(f"weights {tuple(weights.shape)}: one per sample of the last forward {tuple(self.pts.shape[:-1])} expected")
+            weights = weights.detach().reshape(self.pts.shape[:-1]).contiguous()
+        c = self.canonical
+        if ag.needs_grad(self.ctrl_pts_grid):
+            return ag.DynVoxelSplineLenFn.apply(self.ctrl_pts_grid, self.pts, weights, self.spline, c.grid_radius)
+        return ops.dyn_voxel_spline_len(self.pts, self.ctrl_pts_grid.data, self.spline, c.grid_radius, weights)
 
 
 # ------------------------------------------------------------------------------------------------- registries

@@ -1885,3 +1885,110 @@ def grid_upsample(grid: torch.Tensor, reso: int) -> torch.Tensor:
     out = torch.empty(reso, reso, reso, grid.shape[-1], device=grid.device, dtype=torch.float32)
     check(lib.na_grid_upsample(_ptr(grid), S, _ptr(out), reso, grid.shape[-1], _stream()))
     return out
+
+
+# ------------------------------------------------------------------------------------------------- spline lengths (csrc/spline_len.hip)
+SPLINE_LEN_SAMPLES = 16  # arc_len's samples=16 (src/nerf.py:1509): the only value the Python side uses
+
+
+_spline_len_tables = {}
+
+
+def _spline_len_table(device_str: str) -> torch.Tensor:
+    """torch.linspace(0, 1, 16)'s own fp32 values, formed on the CPU as the reference's operators see them and copied to the device
+    once: the kernels read the table and never form j / 15 themselves"""
+    if device_str not in _spline_len_tables:
+        _spline_len_tables[device_str] = torch.linspace(0, 1, SPLINE_LEN_SAMPLES, dtype=torch.float32).to(device_str)
+    return _spline_len_tables[device_str]
+
+
+def _spline_len_grid(grid: torch.Tensor):
+    """a grid [..., 3 m] of m = 1 .. 10 control points per row as the kernels read it -> (grid, rows, m)"""
+    grid = _f32(grid, "grid")
+    C = grid.shape[-1]
+    if grid.dim() < 2 or C % 3 != 0 or not 1 <= C // 3 <= 10:
+        raise ValueError(f"grid must be [..., 3 m] with m = 1 .. 10 control points per row (spline 2 .. 11), got {tuple(grid.shape)}")
+    return grid, grid.numel() // C, C // 3
+
+
+def _spline_len_idxs(rows: int, idxs: torch.Tensor, device, trusted: bool) -> torch.Tensor:
+    if not idxs.is_cuda or idxs.device != device:
+        raise ValueError("idxs must live on the grid's device")
+    if idxs.dtype != torch.int64:
+        raise ValueError(f"idxs must be int64 (what torch.randint draws), got {idxs.dtype}")
+    idxs = idxs.reshape(-1).contiguous()
+    if idxs.numel() < 1:
+        raise ValueError("idxs is empty: the mean over no rows")
+    if not trusted and bool(((idxs < 0) | (idxs >= rows)).any()):  # (ONE host check; the kernels clamp whatever they are given)
+        raise ValueError(f"idxs outside the grid: flat rows 0 .. {rows - 1}")
+    return idxs
+
+
+def grid_spline_len(grid: torch.Tensor, idxs: torch.Tensor, trusted: bool = False, want_lens: bool = False):
+    """0-dim mean arc length (arc_len, src/nerf.py:1509-1520) of the splines whose m control points are the rows idxs [K] int64 of
+    grid [..., 3 m] (control point 0 is not prepended: runner.py:793-796): one launch.  want_lens: (value, lens [K])."""
+    lib = _lib.load()
+    grid, rows, m = _spline_len_grid(grid)
+    idxs = _spline_len_idxs(rows, idxs, grid.device, trusted)
+    out = torch.zeros(2, device=grid.device, dtype=torch.float32)  # [value | arrival counter]
+    lens = torch.empty(idxs.numel(), device=grid.device, dtype=torch.float32) if want_lens else None
+    check(lib.na_grid_spline_len(_ptr(grid), rows, m, _ptr(idxs), idxs.numel(), _ptr(_spline_len_table(str(grid.device))),
+                                 SPLINE_LEN_SAMPLES, _ptr(lens), _ptr(out), _stream()))
+    return (out[0], lens) if want_lens else out[0]
+
+
+def grid_spline_len_backward(grid: torch.Tensor, idxs: torch.Tensor, g: torch.Tensor, trusted: bool = False) -> torch.Tensor:
+    """gradient of grid_spline_len w.r.t. grid times the device scalar g (read by the kernel: no host synchronisation)"""
+    lib = _lib.load()
+    grid, rows, m = _spline_len_grid(grid)
+    idxs = _spline_len_idxs(rows, idxs, grid.device, trusted)
+    g = _f32(g.reshape(1), "g")
+    config.require_deterministic_workspace(8 * grid.numel())
+    out = torch.zeros_like(grid)
+    check(lib.na_grid_spline_len_backward(_ptr(grid), rows, m, _ptr(idxs), idxs.numel(), _ptr(_spline_len_table(str(grid.device))),
+                                          SPLINE_LEN_SAMPLES, _ptr(g), _ptr(out), _stream()))
+    return out
+
+
+def _spline_len_samples(pts: torch.Tensor, ctrl_pts_grid: torch.Tensor, spline: int, w: Optional[torch.Tensor]):
+    _dyn_voxel_spline(spline)
+    ctrl, pts = _f32(ctrl_pts_grid, "ctrl_pts_grid"), _f32(pts, "pts")
+    S = ctrl.shape[0]
+    if ctrl.dim() != 4 or tuple(ctrl.shape) != (S, S, S, 3 * (spline - 1)):
+        raise ValueError(f"ctrl_pts_grid must be [S,S,S,{3 * (spline - 1)}], got {tuple(ctrl.shape)}")
+    _dyn_voxel_reso(S)
+    if pts.shape[-1] != 3 or pts.numel() < 3:
+        raise ValueError(f"pts must be a non-empty [..., 3], got {tuple(pts.shape)}")
+    N = pts.numel() // 3
+    if w is not None:
+        w = _f32(w, "w")
+        if w.numel() != N:
+            raise ValueError(f"w has {w.numel()} elements, one per sample ({N}) expected")
+    return pts, ctrl, S, N, w
+
+
+def dyn_voxel_spline_len(pts: torch.Tensor, ctrl_pts_grid: torch.Tensor, spline: int, grid_radius: float,
+                         w: Optional[torch.Tensor] = None, want_lens: bool = False):
+    """0-dim mean over the samples pts [..., 3] of w * arc_len(control points of the sample) (runner.py:784-787; w None = 1): the
+    control points 1 .. spline-1 are interpolated from ctrl_pts_grid as dyn_voxel_warp does, behind the zero control point 0, and
+    never leave the registers.  One launch.  want_lens: (value, lens [...])."""
+    lib = _lib.load()
+    pts, ctrl, S, N, w = _spline_len_samples(pts, ctrl_pts_grid, spline, w)
+    out = torch.zeros(2, device=pts.device, dtype=torch.float32)  # [value | arrival counter]
+    lens = torch.empty(pts.shape[:-1], device=pts.device, dtype=torch.float32) if want_lens else None
+    check(lib.na_dyn_voxel_spline_len(_ptr(pts), N, _ptr(ctrl), S, spline, float(grid_radius), _ptr(w), _ptr(_spline_len_table(str(pts.device))),
+                                      SPLINE_LEN_SAMPLES, _ptr(lens), _ptr(out), _stream()))
+    return (out[0], lens) if want_lens else out[0]
+
+
+def dyn_voxel_spline_len_backward(pts: torch.Tensor, ctrl_pts_grid: torch.Tensor, spline: int, grid_radius: float, g: torch.Tensor,
+                                  w: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gradient of dyn_voxel_spline_len w.r.t. ctrl_pts_grid times the device scalar g: one scatter-add launch (pts and w get none)"""
+    lib = _lib.load()
+    pts, ctrl, S, N, w = _spline_len_samples(pts, ctrl_pts_grid, spline, w)
+    g = _f32(g.reshape(1), "g")
+    config.require_deterministic_workspace(8 * ctrl.numel())
+    out = torch.zeros_like(ctrl)
+    check(lib.na_dyn_voxel_spline_len_backward(_ptr(pts), N, _ptr(ctrl), S, spline, float(grid_radius), _ptr(w),
+                                               _ptr(_spline_len_table(str(pts.device))), SPLINE_LEN_SAMPLES, _ptr(g), _ptr(out), _stream()))
+    return out

@@ -42,6 +42,7 @@ DEFAULTS = dict(
     neural_upsample=False, quiet=False,
     encoding_size=32, normalize_latent=False, latent_l2_weight=0.0,  # NeRFAE (runner.py:412-416)
     voxel_tv_sigma=0.0, voxel_tv_rgb=0.0, voxel_tv_bezier=0.0, voxel_tv_rigidity=0.0,  # runner.py:289-301
+    voxel_random_spline_len_decay=0.0, spline_len_decay=0.0,  # runner.py:276-283
     voxel_upsample=[],  # this build's flag: ITER:RESO pairs, NeRFVoxel.upsample(RESO) at the start of iteration ITER
 )
 
@@ -434,6 +435,12 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
     if (voxel_tv or upsample_at) and not isinstance(model.nerf, nerf.NeRFVoxel):
         raise ValueError(f"{'--voxel-upsample' if upsample_at else '--voxel-tv-sigma / --voxel-tv-rgb'} needs --model voxel (fit() unsets the "
                          "total-variation weights of another model with the reference's warning)")
+    for flag in ("spline_len_decay", "voxel_random_spline_len_decay"):
+        # both read DynamicNeRFVoxel's ctrl_pts_grid; --dyn-model plain's own per-sample control points are not kept
+        if getattr(args, flag, 0) > 0 and not dyn_voxel:
+            raise ValueError(f"--{flag.replace('_', '-')} needs --dyn-model voxel (the term reads DynamicNeRFVoxel's ctrl_pts_grid), got "
+                             f"{type(model).__name__}")
+    len_on = getattr(args, "spline_len_decay", 0) > 0 or getattr(args, "voxel_random_spline_len_decay", 0) > 0
     device = next(model.parameters()).device
     loss_fn = load_loss_fn(args)
     times = None
@@ -460,6 +467,8 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
     # ([TV(densities), TV(rgb)] per iteration, + [TV(ctrl_pts_grid), TV(rigidity_grid)] for DynamicNeRFVoxel; device scalars: read after
     # the run, no sync in the loop)
     tv_terms = train.last_tv_terms = []
+    # ([--spline-len-decay term, --voxel-random-spline-len-decay term] per iteration, NaN where a term is off; device scalars)
+    len_terms = train.last_len_terms = []
     model.train()
     opt.zero_grad()
     for i in range(args.epochs):
@@ -549,6 +558,20 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
                 tv = nerf.total_variation(model.rigidity_grid)
                 tv_terms[-1][3] = tv.detach()
                 loss = loss + args.voxel_tv_rigidity * tv
+        if len_on:
+            len_terms.append([float("nan")] * 2)
+            if args.spline_len_decay > 0:
+                # runner.py:784-787: "only apply this to visible points": the samples of this iteration's forward, weighted by the
+                # (detached) compositing weights
+                term = model.spline_len(model.canonical.weights)
+                len_terms[-1][0] = term.detach()
+                loss = loss + args.spline_len_decay * term
+            if args.voxel_random_spline_len_decay > 0:
+                # runner.py:792-796: one draw of 16^3 voxels of ctrl_pts_grid (every data-parallel rank draws the same ones), weighted
+                # by the flag itself -- the reference's line names --random-spline-len-decay
+                term = nerf.arc_len_grid(model.ctrl_pts_grid)
+                len_terms[-1][1] = term.detach()
+                loss = loss + args.voxel_random_spline_len_decay * term
         if args.opt_step != 1:
             loss = loss / args.opt_step
         loss.backward()
@@ -624,5 +647,6 @@ def fit(args, device="cuda", replay_reference_rng=False, init=None, on_iter=None
         model.set_bg("white")
     psnrs, gots = test(model, test_cam, test_labels, args)
     return dict(model=model, losses=losses, reg_terms=list(getattr(train, "last_reg_terms", [])),
-                tv_terms=[[float(v) for v in row] for row in getattr(train, "last_tv_terms", [])],test_psnr=psnrs, test_psnr_mean=float(np.mean(psnrs)), frames=gots,
+                tv_terms=[[float(v) for v in row] for row in getattr(train, "last_tv_terms", [])],
+                len_terms=[[float(v) for v in row] for row in getattr(train, "last_len_terms", [])], test_psnr=psnrs, test_psnr_mean=float(np.mean(psnrs)), frames=gots,
                 test_labels=test_labels, rank=rank, world=world)

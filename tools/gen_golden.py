@@ -1173,9 +1173,86 @@ def g25():
         save(f"g25_dyn_voxel_{name}", **kw)
 
 
+SPLINE_LEN_CASES = {  # name: (S, spline, T, ray batch shape [1, H, W], time, indices of the grid term, act, bg)
+    "s2_n2": (2, 2, 7, (1, 4, 4), 0.0, 63, "thin", "black"),               # grid term: one control point per voxel, every length 0
+    "s4_n4": (4, 4, 16, (1, 4, 4), 0.6, 257, "upshifted", "white"),        # more indices than voxels: duplicates
+    "s16_n5_ragged": (16, 5, 24, (1, 5, 7), 0.25, 1000, "leaky_relu", "black"),
+    "s16_n11": (16, 11, 24, (1, 4, 4), 0.9, 257, "upshifted", "black"),
+}
+
+
+def g26():
+    """g26_spline_len_<case>: the reference's two spline-length terms (runner.py:784-796 over arc_len, src/nerf.py:1509-1520), in fp32
+    AND on `.double()` copies.  Data only.
+      grid term    `g_data` built as runner.py:793-795 from the carried indices `g_idxs` (a seeded torch.randint draw decoded as
+                   random_sample_grid decodes it, checked against that function) on the model's procedural ctrl_pts_grid: arc_len per
+                   voxel `g_lens`, their mean `g_value`, autograd's gradient w.r.t. the grid `g_grad`.  Control point 0 is not
+                   prepended there, so spline 2 is a one-point spline: every length and the gradient are 0.
+      sample term  the reference's DynamicNeRFVoxel over its NeRFVoxel + Positional built as g25 builds them, eval mode, ONE view
+                   (arc_len's .squeeze(dim=1) is a shape error at more), voxel_ref.generic_rays: model.ctrl_pts `s_ctrl_pts`,
+                   arc_len of them `s_lens`, the canonical's weights `s_weights`, (w * arc_lens).mean() `s_value` and the gradient
+                   w.r.t. ctrl_pts_grid `s_grad`.  g23's rule: a seed on which the reference's fp32 and fp64 lengths disagree by more
+                   than 1e-5 (a sample on a cell-membership plane) pins nothing and is skipped."""
+    import copy
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import voxel_ref as V
+    for name, (S, spline, T, shape, time, K, act, bg) in SPLINE_LEN_CASES.items():
+        canon, _, _ = _voxel_build(S, T, act, bg)
+        m = rnerf.DynamicNeRFVoxel(canon, spline=spline)
+        m.eval()
+        names, shapes = fill_procedural(m)
+        m64 = copy.deepcopy(m).double()
+        t = torch.tensor([time], dtype=torch.float32)
+
+        def sample_term(model, dt, rays):
+            with torch.enable_grad():
+                model.ctrl_pts_grid.requires_grad_(True)
+                model.ctrl_pts_grid.grad = None
+                model((rays.to(dt), t.to(dt)))
+                lens = rnerf.arc_len(model.ctrl_pts)
+                w = model.canonical.weights.detach().squeeze(1)
+                value = (w * lens).mean()
+                value.backward()
+            return dict(ctrl_pts=model.ctrl_pts.detach(), lens=lens.detach(), weights=w, value=value.detach(), grad=model.ctrl_pts_grid.grad.clone())
+        for seed in range(4500, 4600, 2):
+            rays = V.generic_rays(shape, seed)
+            r32, r64 = sample_term(m, torch.float32, rays), sample_term(m64, torch.float64, rays)
+            dev = float((r32["lens"].double() - r64["lens"]).abs().max())
+            if dev <= 1e-5:
+                break
+            print(f"g26 {name}: seed {seed} skipped, the reference's fp32 and fp64 lengths disagree by {dev:.2e}")
+        else:
+            raise AssertionError(f"g26 {name}: no seed on which the reference agrees with itself")
+        assert r32["lens"].shape == (T,) + tuple(shape[1:]) and r32["lens"].dtype == torch.float32 and r64["value"].dtype == torch.float64
+        kw = dict(rays=rays, time=t, S=S, spline=spline, steps=T, near=2.0, far=6.0, act=act, bg=bg, grid_radius=canon.grid_radius, seed=seed,
+                  ts=m.ts, **spec(names, shapes))
+        for k in r32:
+            kw["s_" + k], kw["s_" + k + "64"] = r32[k], r64[k]
+        torch.manual_seed(2600 + S + spline)
+        idxs = torch.randint(0, S ** 3, (K,))
+        torch.manual_seed(2600 + S + spline)
+        x, y, z = rnerf.random_sample_grid(m.ctrl_pts_grid, K)
+        assert torch.equal(x, idxs % S) and torch.equal(y, idxs // S % S) and torch.equal(z, idxs // (S * S) % S)
+
+        def grid_term(model):
+            with torch.enable_grad():
+                model.ctrl_pts_grid.grad = None
+                data = torch.stack(model.ctrl_pts_grid[x, y, z].split(3, dim=-1), dim=0)[:, :, None, None, None, :]
+                lens = rnerf.arc_len(data)
+                value = lens.mean()
+                value.backward()
+            return dict(lens=lens.detach().reshape(K), value=value.detach(), grad=model.ctrl_pts_grid.grad.clone())
+        q32, q64 = grid_term(m), grid_term(m64)
+        for k in q32:
+            kw["g_" + k], kw["g_" + k + "64"] = q32[k], q64[k]
+        print(f"g26 {name}: seed {seed}; sample term {float(r64['value']):.9f} (lengths up to {float(r64['lens'].max()):.3f}, fp32 off by {dev:.2e}), "
+              f"grid term {float(q64['value']):.9f} over {len(set(idxs.tolist()))} distinct of {K} indices")
+        save(f"g26_spline_len_{name}", g_idxs=idxs, **kw)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25", "g26"]
     for g in which:
         globals()[g]()
     with open(os.path.join(OUT, "PROVENANCE.txt"), "w") as f:
