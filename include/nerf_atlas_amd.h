@@ -823,6 +823,24 @@ int na_dyn_voxel_warp(const float* pts, const float* t, int64_t N, const float* 
 int na_dyn_voxel_warp_backward(const float* pts, const float* t, int64_t N, const float* dp, const float* rigidity, const float* g_warped,
                                const float* g_dp, const float* g_rigidity, int S, int n_ctrl, double grid_radius, float* g_ctrl_pts_grid,
                                float* g_rigidity_grid, void* stream);
+/* na_dyn_voxel_render         DynamicNeRFVoxel's test-time render as ONE launch (csrc/dyn_voxel_render.hip): per ray r of rays [R,6] at
+ *                             time t_ray [R] (the reference's time is per batch element; the caller expands it), for the steps ts [T] in
+ *                             order: the position o + t d as na_compute_pts forms it, na_dyn_voxel_warp's deformation at it,
+ *                             na_voxel_render's lookup at the warped point, activation and compositing step (NA_SIG_* act_kind,
+ *                             NA_BG_BLACK / NA_BG_WHITE; bg random: composite against black, then na_sky_random), and the maps of
+ *                             runner.py:894-916 summed as na_integrate sums them (acc = acc + w * other, ascending t, from 0):
+ *                               out [R,3]; depth [R] = sum w ts; acc [R] = sum of w[:-1]; flow [R,3] = sum w (dp * rigidity);
+ *                               rigidity_map [R] = sum w rigidity; alpha, weights [T,R].
+ *                             Every output but `out` may be NULL and is then not written; the others' bits do not depend on which are
+ *                             asked for.  The result equals, bit for bit, na_compute_pts -> na_dyn_voxel_warp -> na_voxel_render(pts =
+ *                             warped) -> na_integrate x 4, without their per-sample arrays.  S even, 2 .. 1024; C == 3 and n_ctrl 2 .. 11
+ *                             (else NA_EUNSUPPORTED); T >= 1; R == 0 returns NA_OK without a launch; a NULL required pointer is NA_ENULL
+ *                             and named in na_last_error.  Memory safety as above: every grid read goes through an id clamped as an
+ *                             integer, and a non-finite coordinate makes that ray's outputs NaN and touches nothing else.          */
+int na_dyn_voxel_render(const float* rays, const float* t_ray, int64_t R, const float* ts, int T, const float* densities, const float* rgb,
+                        const float* ctrl_pts_grid, const float* rigidity_grid, int S, int C, int n_ctrl, double grid_radius, int act_kind,
+                        int bg_kind, float* out, float* depth, float* acc, float* flow, float* rigidity_map, float* alpha, float* weights,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Operators on a dense channel-last grid [s0,s1,s2,C], 1 <= C <= 32 (NeRFVoxel's densities and rgb; csrc/grid_ops.hip).

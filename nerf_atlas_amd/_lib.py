@@ -240,6 +240,8 @@ SIGNATURES = {
                                     C.c_void_p]),
     "na_dyn_voxel_warp_backward": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_double,
                                              c_f32p, c_f32p, C.c_void_p]),
+    "na_dyn_voxel_render": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
+                                      C.c_double, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "na_grid_tv": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i64, c_f32p, C.c_void_p]),
     "na_grid_tv_backward": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i64, c_f32p, c_f32p, C.c_void_p]),
     "na_grid_upsample": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_void_p]),

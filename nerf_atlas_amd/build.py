@@ -39,6 +39,7 @@ UNITS = [
     ("composite_rayts.hip", [], ""),
     ("voxel.hip", [], ""),
     ("dyn_voxel.hip", [], ""),
+    ("dyn_voxel_render.hip", [], ""),
     ("spline_len.hip", [], ""),
     ("grid_ops.hip", [], ""),
     ("optim.hip", [], ""),

@@ -1,0 +1,164 @@
+// DynamicNeRFVoxel's test-time render as ONE launch (na_dyn_voxel_render): positions -> deformation -> canonical lookup -> activation ->
+// compositing -> the depth / accumulation / flow / rigidity maps of runner.py:894-916, all inside one kernel.
+// It replaces, for a model without an MLP, the composition
+//   na_compute_pts -> na_dyn_voxel_warp (warped, dp, rigidity per sample) -> na_voxel_render(pts = warped) (alpha, weights per sample)
+//   -> na_integrate x 4 (weights x ts, weights x [1 .. 1 0], weights x dp * rigidity, weights x rigidity)
+// and is bit for bit equal to it: every step calls the device functions those kernels call (voxel_cell.h, dyn_voxel_spline.h, common.h) in
+// their order, the running product is voxel_render_kernel's, and every map is integrate_kernel's `acc = acc + w * other` in ascending t
+// from 0 (this unit is built with -ffp-contract=off like the others).  No per-sample array is written unless alpha / weights are asked for.
+//
+// Decomposition.  Everything in a step but the running product and the sums is independent of the walk, and it is nearly all of the work:
+// two lookups with five correctly rounded divisions per axis each, the spline, four transcendentals.  One thread per ray, as
+// voxel_render_kernel walks, leaves a 64 x 64 test tile with 64 waves for 1024 SIMDs, each issuing 80 steps' arithmetic back to back
+// (measured: 0.36 ms a tile, no faster for a quarter of the rays, and FASTER with less look-ahead -- issue-bound, not latency-bound;
+// DESIGN.md 3o).  So NA_DVR_LANES lanes share a ray: lane j computes steps t0 + j of a chunk of NA_DVR_LANES steps to the point where
+// the walk needs them -- alpha, the three activated colours, dp * rigidity, rigidity -- and parks the eight floats in LDS; then ONE lane
+// per ray walks the chunk in ascending t with voxel_render_kernel's step and integrate_kernel's sums, every operation in their order.
+// The gathers of a whole chunk are in flight ahead of the dependent updates (voxel_render_kernel's habit, NA_DVR_LANES steps deep), a
+// tile is 1024 waves, and the walk itself is 80 x ~20 instructions.  NA_DVR_LANES and NA_DVR_BLOCK are build-time constants; DESIGN.md 3o
+// has the times of the other values.
+#include "dyn_voxel_scatter.h"
+#include "dyn_voxel_spline.h"
+
+namespace na {
+
+#ifndef NA_DVR_LANES
+#define NA_DVR_LANES 16   // lanes (steps of a chunk) per ray; a power of two <= 64
+#endif
+#ifndef NA_DVR_BLOCK
+#define NA_DVR_BLOCK 64   // threads of a workgroup: NA_DVR_BLOCK / NA_DVR_LANES rays (one wave: its barriers cost nothing)
+#endif
+static_assert(NA_DVR_BLOCK % NA_DVR_LANES == 0 && (NA_DVR_LANES & (NA_DVR_LANES - 1)) == 0 && NA_DVR_LANES <= 64, "whole rays per workgroup");
+
+// the optional outputs (NULL: not written)
+struct DvrMaps {
+  float* depth;     // [R]
+  float* acc;       // [R]
+  float* flow;      // [R,3]
+  float* rigidity;  // [R]
+  float* alpha;     // [T,R]
+  float* weights;   // [T,R]
+};
+
+template <int NC>
+__global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const float* __restrict__ rays, const float* __restrict__ t_ray,
+                                                                        const float* __restrict__ ts, int T, int64_t R, VoxGrid g,
+                                                                        const float* __restrict__ den, const float* __restrict__ rgb,
+                                                                        const float* __restrict__ ctrl, const float* __restrict__ rig,
+                                                                        int act_kind, int bg_kind, float* __restrict__ out, DvrMaps m) {
+  constexpr int CH = 3 * (NC - 1), L = NA_DVR_LANES, RPB = NA_DVR_BLOCK / NA_DVR_LANES;
+  // a step as the walk needs it: [alpha | 3 activated colours | 3 of dp * rigidity | rigidity]
+  __shared__ float4 park[RPB][L][2];
+  const int slot = threadIdx.x / L, j = threadIdx.x % L;
+  for (int64_t base = (int64_t)blockIdx.x * RPB; base < R; base += (int64_t)gridDim.x * RPB) {  // (uniform: every thread meets the barriers)
+    const int64_t r = base + slot;
+    const bool live = r < R;
+    const int64_t rr = live ? r : R - 1;  // (a dead slot computes the last ray again and writes nothing)
+    const float* ry = rays + rr * 6 + 3;
+    const float nrm = sqrtf((ry[0] * ry[0] + ry[1] * ry[1]) + ry[2] * ry[2]);
+    const float time = t_ray[rr];
+    float trans = 1.0f, acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, wsum_head = 0.f;
+    float depth = 0.f, accm = 0.f, fl0 = 0.f, fl1 = 0.f, fl2 = 0.f, rigm = 0.f;
+    for (int t0 = 0; t0 < T; t0 += L) {
+      const int t = t0 + j;
+      if (t < T) {
+        // the deformation (na_dyn_voxel_warp's arithmetic) at o + t d ...
+        float px, py, pz;
+        vox_position(nullptr, rays, ts, R, (int64_t)t * R + rr, px, py, pz);
+        const VoxCell c = vox_cell(px, py, pz, g);
+        float cp[CH], rl = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < CH; ++ch) cp[ch] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int64_t row = vox_row(c, k, g.S);
+          const float w = vox_weight(c, k);
+          const float* q = ctrl + row * CH;
+#pragma unroll
+          for (int ch = 0; ch < CH; ++ch) cp[ch] = cp[ch] + w * q[ch];
+          rl = rl + w * rig[row];
+        }
+        float dp[3], rdp[3], raw[4];
+        dv_spline<NC>(cp, time, dp);
+        const float rg = sigmoidf_(rl);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) rdp[a] = dp[a] * rg;  // (rigid_dp: the product formed first, once)
+        // ... the canonical lookup at the warped point, and voxel_render_kernel's step up to the running product
+        vox_gather(px + rdp[0], py + rdp[1], pz + rdp[2], g, den, rgb, raw);
+        const float sigma = fast_softplus(raw[0] - 1.0f);
+        float dist = t < T - 1 ? fmaxf(ts[t + 1] - ts[t], 1e-5f) : 1e10f;
+        dist = dist * nrm;
+        const float a = 1.0f - fast_exp(-sigma * dist);
+        if (live && m.alpha != nullptr) m.alpha[(int64_t)t * R + r] = a;
+        park[slot][j][0] = make_float4(a, apply_sigmoid_kind(raw[1], act_kind), apply_sigmoid_kind(raw[2], act_kind),
+                                       apply_sigmoid_kind(raw[3], act_kind));
+        park[slot][j][1] = make_float4(rdp[0], rdp[1], rdp[2], rg);
+      }
+      __syncthreads();
+      if (j == 0 && live) {
+        // the dependent updates, in ascending t: voxel_render_kernel's, then integrate_kernel's `acc = acc + w * other` for the four maps
+        const int n = T - t0 < L ? T - t0 : L;
+        for (int u = 0; u < n; ++u) {
+          const int tu = t0 + u;
+          const float4 p0 = park[slot][u][0], p1 = park[slot][u][1];
+          const float a = p0.x;
+          const float w = a * trans;
+          trans = trans * ((1.0f - a) + 1e-10f);
+          if (m.weights != nullptr) m.weights[(int64_t)tu * R + r] = w;
+          acc0 = acc0 + w * p0.y;
+          acc1 = acc1 + w * p0.z;
+          acc2 = acc2 + w * p0.w;
+          if (tu < T - 1) wsum_head = wsum_head + w;
+          depth = depth + w * ts[tu];
+          accm = accm + w * (tu < T - 1 ? 1.0f : 0.0f);  // (the product with 0 is kept: a NaN weight stays a NaN map)
+          fl0 = fl0 + w * p1.x;
+          fl1 = fl1 + w * p1.y;
+          fl2 = fl2 + w * p1.z;
+          rigm = rigm + w * p1.w;
+        }
+      }
+      __syncthreads();  // (the next chunk overwrites the parked steps)
+    }
+    if (j == 0 && live) {
+      const float sky = bg_kind == NA_BG_WHITE ? 1.0f - wsum_head : 0.f;
+      out[r * 3] = acc0 + sky; out[r * 3 + 1] = acc1 + sky; out[r * 3 + 2] = acc2 + sky;
+      if (m.depth != nullptr) m.depth[r] = depth;
+      if (m.acc != nullptr) m.acc[r] = accm;
+      if (m.flow != nullptr) { m.flow[r * 3] = fl0; m.flow[r * 3 + 1] = fl1; m.flow[r * 3 + 2] = fl2; }
+      if (m.rigidity != nullptr) m.rigidity[r] = rigm;
+    }
+  }
+}
+
+}  // namespace na
+
+using namespace na;
+
+extern "C" {
+
+int na_dyn_voxel_render(const float* rays, const float* t_ray, int64_t R, const float* ts, int T, const float* densities, const float* rgb,
+                        const float* ctrl_pts_grid, const float* rigidity_grid, int S, int C, int n_ctrl, double grid_radius, int act_kind,
+                        int bg_kind, float* out, float* depth, float* acc, float* flow, float* rigidity_map, float* alpha, float* weights,
+                        void* stream) {
+  NA_REQUIRE(T >= 1 && R >= 0, NA_EINVAL, "na_dyn_voxel_render: bad shape T=%d R=%lld", T, (long long)R);
+  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED,
+             "na_dyn_voxel_render: n_ctrl %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", n_ctrl);
+  if (int rc = vox_check_grid("na_dyn_voxel_render", S, C, grid_radius)) return rc;
+  NA_REQUIRE(act_kind >= NA_SIG_NORMAL && act_kind <= NA_SIG_IDENTITY, NA_EUNSUPPORTED, "na_dyn_voxel_render: activation kind %d", act_kind);
+  NA_REQUIRE(bg_kind == NA_BG_BLACK || bg_kind == NA_BG_WHITE, NA_EUNSUPPORTED, "na_dyn_voxel_render: bg kind %d", bg_kind);
+  if (R == 0) return NA_OK;
+#define NA_DVR_PTR(p) NA_REQUIRE(p != nullptr, NA_ENULL, "na_dyn_voxel_render: null pointer " #p)
+  NA_DVR_PTR(rays); NA_DVR_PTR(t_ray); NA_DVR_PTR(ts); NA_DVR_PTR(densities); NA_DVR_PTR(rgb); NA_DVR_PTR(ctrl_pts_grid);
+  NA_DVR_PTR(rigidity_grid); NA_DVR_PTR(out);
+#undef NA_DVR_PTR
+  const VoxGrid g = vox_grid(S, grid_radius);
+  const DvrMaps m{depth, acc, flow, rigidity_map, alpha, weights};
+#define NA_DVR_LAUNCH(NC)                                                                                                                  \
+  hipLaunchKernelGGL(dyn_voxel_render_kernel<NC>, dim3(grid_for(R, NA_DVR_BLOCK / NA_DVR_LANES)), dim3(NA_DVR_BLOCK), 0, (hipStream_t)stream, rays, t_ray, \
+                     ts, T, R, g, densities, rgb, ctrl_pts_grid, rigidity_grid, act_kind, bg_kind, out, m)
+  NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH)
+#undef NA_DVR_LAUNCH
+  return check_launch("na_dyn_voxel_render");
+}
+
+}  // extern "C"

@@ -16,24 +16,6 @@
 
 namespace na {
 
-// raw[0] = density, raw[1..3] = colour parameters: sum over the 8 corners in corner order (4-byte + 12-byte loads per corner; the
-// S = 64 grid is 4 MiB and stays in the L2 / Infinity Cache)
-__device__ __forceinline__ void vox_gather(float px, float py, float pz, const VoxGrid& g, const float* __restrict__ den,
-                                           const float* __restrict__ rgb, float raw[4]) {
-  const VoxCell c = vox_cell(px, py, pz, g);
-  raw[0] = raw[1] = raw[2] = raw[3] = 0.f;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int64_t row = vox_row(c, u, g.S);
-    const float w = vox_weight(c, u);
-    const float* q = rgb + row * 3;
-    raw[0] = raw[0] + w * den[row];
-    raw[1] = raw[1] + w * q[0];
-    raw[2] = raw[2] + w * q[1];
-    raw[3] = raw[3] + w * q[2];
-  }
-}
-
 // ------------------------------------------------------------------------------------ gather
 // one thread per sample, one 16-byte row store
 __global__ __launch_bounds__(256) void voxel_sample_kernel(const float* __restrict__ pts, const float* __restrict__ rays,

@@ -1,5 +1,5 @@
-// The reference's 8-neighbour grid lookup (grid_coords_trilin_weights, src/nerf.py:493-515) as device functions shared by voxel.hip and
-// dyn_voxel.hip: cell membership and xyz are the reference's fp32 chain, operation for operation (voxel.hip's header comment).
+// The reference's 8-neighbour grid lookup (grid_coords_trilin_weights, src/nerf.py:493-515) as device functions shared by voxel.hip,
+// dyn_voxel.hip and dyn_voxel_render.hip: cell membership and xyz are the reference's fp32 chain, operation for operation (voxel.hip's header comment).
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -79,6 +79,24 @@ __device__ __forceinline__ void vox_position(const float* __restrict__ pts, cons
   const float* ry = rays + (n % R) * 6;
   const float tt = ts[n / R];
   px = ry[0] + tt * ry[3]; py = ry[1] + tt * ry[4]; pz = ry[2] + tt * ry[5];
+}
+
+// raw[0] = density, raw[1..3] = colour parameters: sum over the 8 corners in corner order (4-byte + 12-byte loads per corner; the
+// S = 64 grid is 4 MiB and stays in the L2 / Infinity Cache)
+__device__ __forceinline__ void vox_gather(float px, float py, float pz, const VoxGrid& g, const float* __restrict__ den,
+                                           const float* __restrict__ rgb, float raw[4]) {
+  const VoxCell c = vox_cell(px, py, pz, g);
+  raw[0] = raw[1] = raw[2] = raw[3] = 0.f;
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int64_t row = vox_row(c, u, g.S);
+    const float w = vox_weight(c, u);
+    const float* q = rgb + row * 3;
+    raw[0] = raw[0] + w * den[row];
+    raw[1] = raw[1] + w * q[0];
+    raw[2] = raw[2] + w * q[1];
+    raw[3] = raw[3] + w * q[2];
+  }
 }
 
 static int vox_check_grid(const char* who, int S, int C, double grid_radius) {

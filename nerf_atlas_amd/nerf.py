@@ -1056,6 +1056,41 @@ class DynamicNeRFVoxel(nn.Module):
         self.rigidity = rigidity.unsqueeze(-1)
         return c.from_pts(warped, self.ts, r_o, r_d, rays=rays)
 
+    def forward_maps(self, rays_t, depth: bool = True, flow: bool = True, rigidity: bool = True, acc: bool = False):
+        """The test-time frame and its maps (runner.py:894-916) from ONE launch (ops.dyn_voxel_render): a dict of
+        [B,H,W,.] tensors -- `rgb` [.,3] and, where asked for, `depth` [.,1] = sum w ts, `flow` [.,3] = sum w dp rigidity, `rigidity` [.,1]
+        = sum w rigidity, `acc` [.,1] = sum of w[:-1] -- bit for bit what `forward` followed by render.depth_map / flow_map /
+        rigidity_map / alpha_map gives, without the per-sample tensors.  Eval mode without gradients only.  The attributes of the last
+        `forward` (`alpha`, `weights`, `dp`, `rigidity`, `pts` -- here and on the canonical model) are left untouched: nothing per sample
+        is kept, and a regulariser or map that reads them still sees the last `forward`."""
+        rays, t = rays_t
+        c = self.canonical
+        if self.training or ag.needs_grad(self.ctrl_pts_grid, self.rigidity_grid, c.densities, c.rgb):
+            raise RuntimeError("DynamicNeRFVoxel.forward_maps renders in eval mode without gradients only (model.eval() under "
+                               "torch.no_grad()); training goes through forward")
+        if not c._fusable():
+            raise RuntimeError(f"DynamicNeRFVoxel.forward_maps needs the canonical model's one-launch route: the per-voxel RGB head "
+                               f"with 3 colour parameters and a named activation, got {type(c._head).__name__} / {c.rgb.shape[-1]} / "
+                               f"{c.sigmoid_kind}")
+        if c.resolution != self.rigidity_grid.shape[0]:
+            raise ValueError(f"DynamicNeRFVoxel: the canonical grids are {c.resolution}^3 and the deformation grids "
+                             f"{self.rigidity_grid.shape[0]}^3 (the deformation grids have no resampling)")
+        _, _, ts, _ = compute_ts(rays, c.t_near, c.t_far, c.steps, perturb=0)
+        want = [k for k, on in (("depth", depth), ("acc", acc), ("flow", flow), ("rigidity", rigidity)) if on]
+        if c.bg == "random":
+            want.append("weights")  # (the random sky is added behind the launch from the weights)
+        tt = t[:, None, None].expand(rays.shape[:-1]).contiguous()
+        res = ops.dyn_voxel_render(rays.contiguous(), tt, ts, c.densities.data, c.rgb.data, self.ctrl_pts_grid.data, self.rigidity_grid.data,
+                                   self.spline, c.grid_radius, c._act_kind(), c._kernel_bg(), want=want)
+        weights = res.pop("weights", None)
+        if weights is not None:
+            kept, c.weights = c.weights, weights
+            try:
+                c._finish_sky(res["rgb"])
+            finally:
+                c.weights = kept
+        return res
+
     @property
     def rigid_dp(self):
         """dp * rigidity (src/nerf.py:1585), formed on demand like DynamicNeRF's"""

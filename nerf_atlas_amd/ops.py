@@ -1816,6 +1816,43 @@ def dyn_voxel_warp_backward(pts: torch.Tensor, t: torch.Tensor, dp: torch.Tensor
     return g_ctrl, g_rig
 
 
+DYN_VOXEL_MAPS = ("depth", "acc", "flow", "rigidity", "alpha", "weights")
+
+
+def dyn_voxel_render(rays: torch.Tensor, t: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor,
+                     ctrl_pts_grid: torch.Tensor, rigidity_grid: torch.Tensor, spline: int, grid_radius: float,
+                     sigmoid_kind: str = "upshifted", bg: str = "black", want=("depth", "flow", "rigidity")):
+    """DynamicNeRFVoxel's test-time render as ONE launch (csrc/dyn_voxel_render.hip): rays [..., 6] at times t [...] (one per ray, expanded
+    by the caller) over the steps ts [T] -> dict(rgb [..., 3] + the outputs named in `want`: depth [..., 1], acc [..., 1], flow [..., 3],
+    rigidity [..., 1] -- the maps of runner.py:894-916 -- and alpha, weights [T, ...]).  Bit for bit compute_pts -> dyn_voxel_warp ->
+    voxel_render(pts=warped) -> integrate x 4, without their per-sample tensors.  bg black | white (random: black, then sky_random)."""
+    lib = _lib.load()
+    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
+    ctrl, rig, S2 = _dyn_voxel_grids(ctrl_pts_grid, rigidity_grid, spline)
+    if S2 != S:
+        raise ValueError(f"the canonical grids are {S}^3 and the deformation grids {S2}^3")
+    rays, t, ts = _f32(rays, "rays"), _f32(t, "t"), _f32(ts, "ts")
+    if rays.shape[-1] != 6 or ts.dim() != 1 or tuple(t.shape) != tuple(rays.shape[:-1]):
+        raise ValueError(f"rays must be [..., 6], t [...] (one time per ray, expanded by the caller) and ts [T], got {tuple(rays.shape)}, "
+                         f"{tuple(t.shape)} and {tuple(ts.shape)}")
+    unknown = set(want) - set(DYN_VOXEL_MAPS)
+    if unknown:
+        raise ValueError(f"want {sorted(unknown)}: the optional outputs are {DYN_VOXEL_MAPS}")
+    if bg not in BG:
+        raise NotImplementedError(bg)
+    batch, T, R = tuple(rays.shape[:-1]), ts.shape[0], rays.numel() // 6
+    new = lambda *shape: torch.empty(shape, device=rays.device, dtype=torch.float32)
+    res = {"rgb": new(*batch, 3)}
+    for name, shape in (("depth", batch + (1,)), ("acc", batch + (1,)), ("flow", batch + (3,)), ("rigidity", batch + (1,)),
+                        ("alpha", (T,) + batch), ("weights", (T,) + batch)):
+        if name in want:
+            res[name] = new(*shape)
+    check(lib.na_dyn_voxel_render(_ptr(rays), _ptr(t), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), _ptr(ctrl), _ptr(rig), S, Cn, spline,
+                                  float(grid_radius), SIGMOID[sigmoid_kind], BG[bg], _ptr(res["rgb"]),
+                                  *(_ptr(res.get(name)) for name in DYN_VOXEL_MAPS), _stream()))
+    return res
+
+
 # ------------------------------------------------------------------------------------------------- grid operators (csrc/grid_ops.hip)
 GRID_MAX_C = 32
 

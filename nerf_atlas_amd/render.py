@@ -113,15 +113,91 @@ def rigidity_vis(model):
     return [rigidity_map(model)[0]]
 
 
+def depth_panel(depth: torch.Tensor, near: float, far: float) -> torch.Tensor:
+    """runner.py:940-942: the depth image of a test frame, ((d - near) / (far - near)).clamp(0, 1)"""
+    return ((depth - near) / (far - near)).clamp(min=0, max=1)
+
+
+def flow_panel(flow: torch.Tensor) -> torch.Tensor:
+    """runner.py:943-946: the flow image of a test frame [H,W,3] -- divided by the frame's largest vector norm, signed square root,
+    (x + 1) / 2.  A frame whose flow is zero everywhere divides by zero in the reference (a NaN image); here it is mid-grey, the image
+    of zero flow."""
+    top = flow.norm(dim=-1, keepdim=True).max()
+    flow = flow / torch.where(top > 0, top, torch.ones_like(top))
+    flow = flow.abs().sqrt().copysign(flow)
+    return (flow + 1) / 2
+
+
+def rigidity_panel(rigidity: torch.Tensor) -> torch.Tensor:
+    """runner.py:947: the integrated rigidity as it is"""
+    return rigidity
+
+
+def map_panels(maps: dict, near: float, far: float):
+    """the panels runner.py:940-947 appends behind [label | got] for one view's maps, in the reference's order: depth, flow, rigidity"""
+    items = []
+    if "depth" in maps: items.append(depth_panel(maps["depth"], near, far))
+    if "flow" in maps: items.append(flow_panel(maps["flow"]))
+    if "rigidity" in maps: items.append(rigidity_panel(maps["rigidity"]))
+    return items
+
+
 # runner.py:534-538
 visualizations = {"depth": depth_vis, "flow": flow_vis, "rigidity": rigidity_vis}
 
 
+MAP_CHANNELS = {"depth": 1, "flow": 3, "rigidity": 1, "acc": 1}
+
+
+def _tile_maps(model, cam, crop, size, times, want, generic: bool):
+    """one test tile: {"rgb": [h,w,3], name: [h,w,C] for the names of `want` the model can give}.  DynamicNeRFVoxel renders the tile
+    and its maps in one launch (forward_maps); every other model -- and the voxel D-NeRF with generic=True -- takes render() followed by
+    the map functions above, which read the per-sample tensors of that forward.  A map the model cannot give is omitted, as the
+    reference's hasattr checks omit it (runner.py:908-913)."""
+    from .nerf import DynamicNeRFVoxel
+    if isinstance(model, DynamicNeRFVoxel) and not generic:
+        rays = cam.sample_positions(tuple(crop), size=size, with_noise=False)
+        res = model.forward_maps((rays, times), **{k: k in want for k in MAP_CHANNELS})
+        return {k: v.squeeze(0) for k, v in res.items()}
+    o, _ = render(model, cam, crop, size=size, times=times, with_noise=False)
+    res = {"rgb": o.squeeze(0)}
+    if "depth" in want:
+        res["depth"] = depth_map(model)[0]
+    if "flow" in want and hasattr(model, "rigid_dp"):
+        res["flow"] = flow_map(model)[0]
+    if "rigidity" in want and hasattr(model, "rigidity"):
+        res["rigidity"] = rigidity_map(model)[0]
+    if "acc" in want:
+        res["acc"] = alpha_map(model)[0]
+    return res
+
+
+def render_frame_maps(model, cam, size: int, crop_size: int = 0, times=None, want=("depth", "flow", "rigidity"), generic: bool = False):
+    """test()-style tiled frame WITH its maps (runner.py:879-916): {"rgb": [size,size,3], "depth" / "rigidity" / "acc": [size,size,1],
+    "flow": [size,size,3]}, filled tile by tile in tile_list's order.  `want` names the maps; one the model cannot give (flow and
+    rigidity of a static model) is left out of the result.  generic=True forces render() + the map functions for DynamicNeRFVoxel too
+    (the route its one-launch render is tested against, bit for bit)."""
+    unknown = set(want) - set(MAP_CHANNELS)
+    if unknown:
+        raise ValueError(f"want {sorted(unknown)}: the maps are {tuple(MAP_CHANNELS)}")
+    device = next(model.parameters()).device
+    frame = {}
+    with torch.no_grad():
+        for (c0, c1, h, w) in tile_list(size, crop_size):
+            for k, v in _tile_maps(model, cam, (c0, c1, h, w), size, times, want, generic).items():
+                if k not in frame:
+                    frame[k] = torch.zeros(size, size, v.shape[-1], device=device)
+                frame[k][c0:c0 + h, c1:c1 + w, :] = v
+    return frame
+
+
 def render_over_time(model, cam, size: int, crop_size: int, times, with_alpha: bool = False, rank: int = 0,
-                     world: int = 1):
+                     world: int = 1, generic: bool = False):
     """runner.py:998-1017: one camera, a sweep of times through a dynamic model; frame i is rendered in test()-style
     tiles at times[i].  Frames are independent, so with world > 1 this rank renders frames rank, rank+world, ...
-    (D-NeRF time sweeps shard by frame); returns [(index, frame [size,size,3(+1)])]."""
+    (D-NeRF time sweeps shard by frame); returns [(index, frame [size,size,3(+1)])].  DynamicNeRFVoxel renders a tile
+    and its alpha channel (the kernel's `acc`) in one launch unless generic=True; every other model's frames are render()'s, with
+    alpha_map for the alpha channel."""
     device = next(model.parameters()).device
     frames = []
     with torch.no_grad():
@@ -129,10 +205,10 @@ def render_over_time(model, cam, size: int, crop_size: int, times, with_alpha: b
             t = times[i].reshape(1).to(device)
             got = torch.zeros(size, size, 3 + int(with_alpha), device=device)
             for (c0, c1, h, w) in tile_list(size, crop_size):
-                o, _ = render(model, cam, (c0, c1, h, w), size=size, times=t, with_noise=False)
-                got[c0:c0 + h, c1:c1 + w, :3] = o.squeeze(0)
+                res = _tile_maps(model, cam, (c0, c1, h, w), size, t, ("acc",) if with_alpha else (), generic)
+                got[c0:c0 + h, c1:c1 + w, :3] = res["rgb"]
                 if with_alpha:
-                    got[c0:c0 + h, c1:c1 + w, 3] = alpha_map(model)[0, ..., 0]
+                    got[c0:c0 + h, c1:c1 + w, 3] = res["acc"][..., 0]
             frames.append((i, got))
     return frames
 

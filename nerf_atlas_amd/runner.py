@@ -6,13 +6,15 @@
 
 seeds, loads the dataset (loaders.py), builds the model through the registries, trains (train.py), renders the test set
 with the fused kernels and writes `results.txt` in the reference's format (runner.py:977-995) plus `test_NNN.png`
-(expected | rendered, side by side).  Flags outside the hot path are rejected by argparse rather than ignored."""
+(expected | rendered, side by side; with `--depth-images`, `--flow-map`, `--rigidity-map` the maps' panels behind them) and, with
+`--render-over-time CAM`, `time_NNN.png` for a sweep of times through a dynamic model (RGBA with `--with-alpha`).  Flags outside the hot path are rejected by argparse rather than ignored."""
 import os
 import sys
 
 import numpy as np
 import torch
 
+from . import render
 from . import train as T
 
 
@@ -46,6 +48,24 @@ def load_state(path, allow_pickled_module=False):
     if not isinstance(obj, dict):
         raise ValueError(f"{path}: neither a state_dict nor a module")
     return obj
+
+
+def write_time_sweep(args, res, outdir):
+    """--render-over-time CAM (runner.py:998-1017): test camera CAM fixed, time_{i:03}.png for linspace(0, --render-over-time-end-sec,
+    --render-over-time-steps); RGBA with --with-alpha.  Needs a dynamic model and PIL."""
+    model, cam = res["model"], res["test_cam"]
+    if type(res["test_labels"]) is not tuple:
+        raise ValueError("--render-over-time needs a dynamic model (--data-kind dnerf --dyn-model ...): a static model has no time to sweep")
+    if args.render_over_time >= len(cam):
+        raise ValueError(f"--render-over-time {args.render_over_time}: the test set has {len(cam)} cameras")
+    from PIL import Image
+    device = next(model.parameters()).device
+    times = torch.linspace(0, args.render_over_time_end_sec, steps=args.render_over_time_steps, device=device)
+    model.eval()
+    frames = render.render_over_time(model, cam[args.render_over_time:args.render_over_time + 1], args.render_size, args.test_crop_size,
+                                     times, with_alpha=args.with_alpha)
+    for i, got in frames:
+        Image.fromarray((got.clamp(0, 1).cpu().numpy() * 255).round().astype(np.uint8)).save(os.path.join(outdir, f"time_{i:03}.png"))
 
 
 def main(argv=None):
@@ -88,7 +108,10 @@ def main(argv=None):
         print(lines[-1])
         try:
             from PIL import Image
-            both = torch.cat([labels[i, ..., :3].cpu(), got.clamp(0, 1).cpu()], dim=1)
+            items = [labels[i, ..., :3].cpu(), got.clamp(0, 1).cpu()]
+            if res["maps"]:  # runner.py:940-947: depth | flow | rigidity behind [label | got]
+                items += [m.clamp(0, 1).cpu().expand(-1, -1, 3) for m in render.map_panels(res["maps"][i], args.near, args.far)]
+            both = torch.cat(items, dim=1)
             Image.fromarray((both.numpy() * 255).round().astype(np.uint8)).save(os.path.join(outdir, f"test_{i:03}.png"))
         except ImportError:
             pass
@@ -98,6 +121,8 @@ def main(argv=None):
         f.write(s)
         for l in lines:
             f.write("\n" + l)
+    if args.render_over_time >= 0:
+        write_time_sweep(args, res, outdir)
     if save:
         torch.save(res["model"].state_dict(), save)  # state_dict keys = the reference's
         print(f"Saved to {save}")

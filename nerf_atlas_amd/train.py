@@ -6,6 +6,8 @@ tangents through the MLP), `--smooth-normals` in the reference's default epsilon
 `--smooth-eps-rng`, `--smooth-n-ord`), `--dyn-diverge-decay` (one differentiable direction tangent), `--ffjord-div-decay`
 (forward-mode divergence estimate), `--voxel-tv-sigma` / `--voxel-tv-rgb` (total variation of NeRFVoxel's grids) and this build's
 `--voxel-upsample ITER:RESO`; over `--dyn-model voxel` also `--voxel-tv-bezier` / `--voxel-tv-rigidity`; `--smooth-normals --smooth-eps 0` (double backward) raises.
+The test loop also renders the maps of `--depth-images` / `--flow-map` / `--rigidity-map` (render.render_frame_maps; one launch per tile for
+the voxel D-NeRF); `--render-over-time` and `--with-alpha` are read by runner.main.
 
 Every forward and backward is a HIP kernel (nerf_atlas_amd/autograd.py); the parameter update is the reference's table of torch.optim
 classes (`--opt-kind adam | sgd | adamw | rmsprop`, `--decay`), each with its step as one HIP launch (load_optim below).
@@ -26,7 +28,7 @@ from torch.optim.optimizer import _get_scalar_dtype
 from . import autograd as ag
 from . import dist as na_dist
 from . import config, loaders, nerf, refl, utils
-from .render import render, render_frame
+from .render import render, render_frame, render_frame_maps
 
 # the reference's CLI defaults for the fields used here (runner.py:38-424)
 DEFAULTS = dict(
@@ -44,6 +46,8 @@ DEFAULTS = dict(
     voxel_tv_sigma=0.0, voxel_tv_rgb=0.0, voxel_tv_bezier=0.0, voxel_tv_rigidity=0.0,  # runner.py:289-301
     voxel_random_spline_len_decay=0.0, spline_len_decay=0.0,  # runner.py:276-283
     voxel_upsample=[],  # this build's flag: ITER:RESO pairs, NeRFVoxel.upsample(RESO) at the start of iteration ITER
+    depth_images=False, flow_map=False, rigidity_map=False, with_alpha=False,  # runner.py:360-392: maps next to the test frames
+    render_over_time=-1, render_over_time_steps=100, render_over_time_end_sec=1.0,  # runner.py:252-261: a time sweep of one test camera
 )
 
 loss_map = {
@@ -590,7 +594,8 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
 
 
 def test(model, cam, labels, args):
-    """runner.py:855-995: every view rendered in test_crop_size tiles without jitter; per-image PSNR."""
+    """runner.py:855-995: every view rendered in test_crop_size tiles without jitter; per-image PSNR.  Returns (psnrs, frames); the
+    per-view maps of the map flags are left in test.last_maps."""
     device = next(model.parameters()).device
     times = None
     if type(labels) is tuple:
@@ -599,11 +604,20 @@ def test(model, cam, labels, args):
     if args.test_crop_size <= 0:
         args.test_crop_size = args.render_size
     psnrs, gots = [], []
+    # runner.py:894-916: with --depth-images / --flow-map / --rigidity-map every view's maps are rendered with it (one launch per tile for
+    # the voxel D-NeRF) and kept per view, {name: [size,size,C]}, next to the frames; [] when no flag is set
+    want = [k for k, flag in (("depth", "depth_images"), ("flow", "flow_map"), ("rigidity", "rigidity_map")) if getattr(args, flag, False)]
+    maps = test.last_maps = []
     model.eval()
     for i in range(labels.shape[0]):
         ts = None if times is None else times[i:i + 1]
         exp = labels[i, ..., :3].to(device)
-        got = render_frame(model, cam[i:i + 1], args.render_size, args.test_crop_size, times=ts)
+        if want:
+            frame = render_frame_maps(model, cam[i:i + 1], args.render_size, args.test_crop_size, times=ts, want=want)
+            got = frame.pop("rgb")
+            maps.append(frame)
+        else:
+            got = render_frame(model, cam[i:i + 1], args.render_size, args.test_crop_size, times=ts)
         gots.append(got)
         psnrs.append(float(utils.mse2psnr(F.mse_loss(got, exp))))
     return psnrs, gots
@@ -649,4 +663,4 @@ def fit(args, device="cuda", replay_reference_rng=False, init=None, on_iter=None
     return dict(model=model, losses=losses, reg_terms=list(getattr(train, "last_reg_terms", [])),
                 tv_terms=[[float(v) for v in row] for row in getattr(train, "last_tv_terms", [])],
                 len_terms=[[float(v) for v in row] for row in getattr(train, "last_len_terms", [])], test_psnr=psnrs, test_psnr_mean=float(np.mean(psnrs)), frames=gots,
-                test_labels=test_labels, rank=rank, world=world)
+                maps=list(getattr(test, "last_maps", [])), test_labels=test_labels, test_cam=test_cam, rank=rank, world=world)
