@@ -804,6 +804,44 @@ int na_voxel_sample_backward_pts(const float* pts, int64_t N, const float* densi
                                  double grid_radius, float* g_pts, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * NeRFVoxel with the per-voxel pos-linear-view head (PosLinearView.to_voxel, src/refl.py:265-280; csrc/voxel_plv.hip): rgb is
+ * [S,S,S,C] with C = 3 + (order+1)^2, a row [raw rgb (3) | (order+1)^2 coefficients of one real spherical-harmonic channel], order 0..4
+ * (else NA_EINVAL; 4 is the reference's).  Per sample s = sum_k Y_k(d / max(|d|, 1e-12)) c_k with c_k the interpolated coefficient
+ * and d = rays[n % R, 3:6] (un-normalised; rays is required in both position forms), and the colour is
+ * act(raw rgb) * (sigmoid(s) / 2 + 0.5).  The lookup, its positions (explicit pts [T*R,3], or rays x ts) and its memory-safety rule are
+ * those of na_voxel_sample above; every corner's coefficients are contracted with the ray's basis as the row arrives (d_u = sum_k in
+ * k order by fma, then s = sum_u w_u d_u in corner order), so no [N, (order+1)^2] array exists in either direction.  With C % 4 == 0
+ * (order 0, 2, 4) rows are read with 16-byte loads and rgb must be 16-byte aligned (else NA_EINVAL); raw and g_raw always.
+ * na_voxel_plv_sample               raw [T*R,4] = [density | 3 colour parameters] (na_voxel_sample's layout and arithmetic) and
+ *                                   sh [T*R] = s, before any activation.
+ * na_voxel_plv_sample_backward      g_densities [S^3] += , g_rgb [S^3,C] += (zeroed by the caller): corner u of sample n receives
+ *                                   w_u [g_raw[n,0] | g_raw[n,1..3] | g_sh[n] Y_k].  fp32 atomics by default; under
+ *                                   na_set_deterministic every contribution goes to 2^-40 fixed point on its own (bitwise
+ *                                   independent of the order of the samples; workspace >= 8 (1 + C) S^3 bytes = 60.8 MB at S = 64,
+ *                                   C = 28, else NA_EWORKSPACE before anything is written).  ..._variant runs scatter variant 1
+ *                                   (whole rows in the LDS table) or 2 (the four leading sums in the table, the coefficient block
+ *                                   straight to memory) for measurements; the plain entry point runs the shipped one.
+ * na_voxel_plv_sample_backward_pts  g_pts [N,3] for explicit pts [N,3] (N a multiple of R): na_voxel_sample_backward_pts with the
+ *                                   per-corner value g_raw[n,0] densities[row] + sum_c g_raw[n,1+c] rgb[row,c] + g_sh[n] sum_k Y_k
+ *                                   rgb[row,3+k].  A gather, no atomics; a non-finite coordinate gives a NaN row.
+ * na_voxel_plv_render               the eval route as one launch: the basis once per ray, then per step the lookup, NA_SIG_* act_kind
+ *                                   on the colour parameters, the linear scale and na_composite's arithmetic against NA_BG_BLACK /
+ *                                   NA_BG_WHITE; alpha / weights NULL or [T,R]; out [R,3].  bg random: black, then na_sky_random. */
+int na_voxel_plv_sample(const float* pts, const float* rays, int64_t R, const float* ts, int T, const float* densities, const float* rgb,
+                        int S, int order, double grid_radius, float* raw, float* sh, void* stream);
+int na_voxel_plv_sample_backward(const float* pts, const float* rays, int64_t R, const float* ts, int T, const float* g_raw,
+                                 const float* g_sh, int S, int order, double grid_radius, float* g_densities, float* g_rgb, void* stream);
+int na_voxel_plv_sample_backward_variant(const float* pts, const float* rays, int64_t R, const float* ts, int T, const float* g_raw,
+                                         const float* g_sh, int S, int order, double grid_radius, float* g_densities, float* g_rgb,
+                                         int variant, void* stream);
+int na_voxel_plv_sample_backward_pts(const float* pts, const float* rays, int64_t R, int64_t N, const float* densities, const float* rgb,
+                                     const float* g_raw, const float* g_sh, int S, int order, double grid_radius, float* g_pts,
+                                     void* stream);
+int na_voxel_plv_render(const float* rays, const float* pts, int64_t R, const float* ts, int T, const float* densities, const float* rgb,
+                        int S, int order, double grid_radius, int act_kind, int bg_kind, float* alpha, float* weights, float* out,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * DynamicNeRFVoxel (src/nerf.py:1526-1586; csrc/dyn_voxel.hip): the deformation of a voxel D-NeRF.  ctrl_pts_grid [S,S,S,3(n-1)] holds
  * control points 1 .. n-1 of a Bezier spline per voxel (control point 0 is zero), rigidity_grid [S,S,S,1] a rigidity logit; both are
  * read by NeRFVoxel's lookup above at the UNWARPED pts [N,3] (same cells, same weights, same memory-safety rule), t [N] is the time of
@@ -841,6 +879,15 @@ int na_dyn_voxel_render(const float* rays, const float* t_ray, int64_t R, const 
                         const float* ctrl_pts_grid, const float* rigidity_grid, int S, int C, int n_ctrl, double grid_radius, int act_kind,
                         int bg_kind, float* out, float* depth, float* acc, float* flow, float* rigidity_map, float* alpha, float* weights,
                         void* stream);
+/* na_dyn_voxel_plv_render     na_dyn_voxel_render over a canonical model with the pos-linear-view head of `order` 0 .. 4 (else NA_EINVAL;
+ *                             rgb [S^3, 3 + (order+1)^2], 16-byte aligned where the rows are): same contract and outputs, the canonical
+ *                             step being na_voxel_plv_render's (the ray's basis once per thread, the lookup with the coefficients
+ *                             contracted in registers, the linear scale).  The result equals, bit for bit, na_compute_pts ->
+ *                             na_dyn_voxel_warp -> na_voxel_plv_render(pts = warped) -> na_integrate x 4.                          */
+int na_dyn_voxel_plv_render(const float* rays, const float* t_ray, int64_t R, const float* ts, int T, const float* densities,
+                            const float* rgb, const float* ctrl_pts_grid, const float* rigidity_grid, int S, int order, int n_ctrl,
+                            double grid_radius, int act_kind, int bg_kind, float* out, float* depth, float* acc, float* flow,
+                            float* rigidity_map, float* alpha, float* weights, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Operators on a dense channel-last grid [s0,s1,s2,C], 1 <= C <= 32 (NeRFVoxel's densities and rgb; csrc/grid_ops.hip).

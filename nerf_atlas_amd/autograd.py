@@ -561,6 +561,37 @@ class VoxelSampleFn(Function):
         return g_den, g_rgb, None, g_pts, None, None
 
 
+class VoxelPlvSampleFn(Function):
+    """(raw [..., 4], sh [...]) of NeRFVoxel's lookup with the pos-linear-view head (ops.voxel_plv_sample); backward scatters into the
+    two grids (ops.voxel_plv_sample_backward).  Like VoxelSampleFn only the positions are saved -- the rays (their directions are the
+    head's view) and explicit pts or ts -- and the cells are recomputed; explicit pts that require a gradient get one
+    (ops.voxel_plv_sample_backward_pts, the grids are saved for it), the rays x ts form has no position gradient."""
+
+    @staticmethod
+    def forward(ctx, densities, rgb, grid_radius, rays, pts, ts):
+        ctx.grid_radius, ctx.S, ctx.order = grid_radius, densities.shape[0], ops.PLV_CHANNELS.get(rgb.shape[-1])
+        ctx.explicit = pts is not None
+        ctx.pts_grad = ctx.explicit and ctx.needs_input_grad[4]
+        ctx.save_for_backward(rays, pts if ctx.explicit else ts, *((densities, rgb) if ctx.pts_grad else ()))
+        ctx.set_materialize_grads(False)
+        return ops.voxel_plv_sample(densities, rgb, grid_radius, rays, pts=pts, ts=ts)
+
+    @staticmethod
+    def backward(ctx, g_raw, g_sh):
+        saved = ctx.saved_tensors
+        rays, pos = saved[0], saved[1]
+        kw = {"pts": pos} if ctx.explicit else {"ts": pos}
+        batch = tuple(pos.shape[:-1]) if ctx.explicit else (pos.shape[0],) + tuple(rays.shape[:-1])
+        g_raw = g_raw.contiguous() if g_raw is not None else rays.new_zeros(batch + (4,))
+        g_sh = g_sh.contiguous() if g_sh is not None else rays.new_zeros(batch)
+        g_den = g_rgb = g_pts = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            g_den, g_rgb = ops.voxel_plv_sample_backward(g_raw, g_sh, ctx.S, ctx.order, ctx.grid_radius, rays, **kw)
+        if ctx.pts_grad:
+            g_pts = ops.voxel_plv_sample_backward_pts(g_raw, g_sh, pos, rays, saved[2], saved[3], ctx.grid_radius)
+        return g_den, g_rgb, None, None, g_pts, None
+
+
 class DynVoxelWarpFn(Function):
     """(warped, dp, rigidity) of DynamicNeRFVoxel's deformation (ops.dyn_voxel_warp, one launch); all three are differentiable --
     `warped` feeds the canonical lookup, `dp` and `rigidity` the offset regularisers -- and backward is one scatter-add into the two

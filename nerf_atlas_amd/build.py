@@ -38,6 +38,7 @@ UNITS = [
     ("fourier_grad.hip", [], ""),
     ("composite_rayts.hip", [], ""),
     ("voxel.hip", [], ""),
+    ("voxel_plv.hip", [], ""),
     ("dyn_voxel.hip", [], ""),
     ("dyn_voxel_render.hip", [], ""),
     ("spline_len.hip", [], ""),

@@ -17,8 +17,14 @@
 // The gathers of a whole chunk are in flight ahead of the dependent updates (voxel_render_kernel's habit, NA_DVR_LANES steps deep), a
 // tile is 1024 waves, and the walk itself is 80 x ~20 instructions.  NA_DVR_LANES and NA_DVR_BLOCK are build-time constants; DESIGN.md 3o
 // has the times of the other values.
+//
+// The canonical model's head is a template parameter (K): -1 the per-voxel RGB head (na_dyn_voxel_render, C = 3: vox_gather), 0 .. 4 the
+// pos-linear-view head of that order (na_dyn_voxel_plv_render, C = 3 + (K+1)^2: the ray's basis once per thread, vox_plv_gather and the
+// linear scale -- plv_render_kernel's step, so the result equals the composition over na_voxel_plv_render bit for bit).  The K = -1
+// instantiations compile the code they compiled before the parameter existed.
 #include "dyn_voxel_scatter.h"
 #include "dyn_voxel_spline.h"
+#include "voxel_plv.h"
 
 namespace na {
 
@@ -40,7 +46,7 @@ struct DvrMaps {
   float* weights;   // [T,R]
 };
 
-template <int NC>
+template <int NC, int K>
 __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const float* __restrict__ rays, const float* __restrict__ t_ray,
                                                                         const float* __restrict__ ts, int T, int64_t R, VoxGrid g,
                                                                         const float* __restrict__ den, const float* __restrict__ rgb,
@@ -57,6 +63,8 @@ __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const fl
     const float* ry = rays + rr * 6 + 3;
     const float nrm = sqrtf((ry[0] * ry[0] + ry[1] * ry[1]) + ry[2] * ry[2]);
     const float time = t_ray[rr];
+    float Y[SH_MAX_K];
+    if constexpr (K >= 0) plv_ray_basis<K>(rays, rr, Y);
     float trans = 1.0f, acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, wsum_head = 0.f;
     float depth = 0.f, accm = 0.f, fl0 = 0.f, fl1 = 0.f, fl2 = 0.f, rigm = 0.f;
     for (int t0 = 0; t0 < T; t0 += L) {
@@ -78,20 +86,26 @@ __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const fl
           for (int ch = 0; ch < CH; ++ch) cp[ch] = cp[ch] + w * q[ch];
           rl = rl + w * rig[row];
         }
-        float dp[3], rdp[3], raw[4];
+        float dp[3], rdp[3], raw[5], lin = 1.0f;
         dv_spline<NC>(cp, time, dp);
         const float rg = sigmoidf_(rl);
 #pragma unroll
         for (int a = 0; a < 3; ++a) rdp[a] = dp[a] * rg;  // (rigid_dp: the product formed first, once)
         // ... the canonical lookup at the warped point, and voxel_render_kernel's step up to the running product
-        vox_gather(px + rdp[0], py + rdp[1], pz + rdp[2], g, den, rgb, raw);
+        if constexpr (K >= 0) {
+          vox_plv_gather<K>(px + rdp[0], py + rdp[1], pz + rdp[2], g, den, rgb, Y, raw);
+          lin = plv_scale(raw[4]);
+        } else {
+          vox_gather(px + rdp[0], py + rdp[1], pz + rdp[2], g, den, rgb, raw);
+        }
         const float sigma = fast_softplus(raw[0] - 1.0f);
         float dist = t < T - 1 ? fmaxf(ts[t + 1] - ts[t], 1e-5f) : 1e10f;
         dist = dist * nrm;
         const float a = 1.0f - fast_exp(-sigma * dist);
         if (live && m.alpha != nullptr) m.alpha[(int64_t)t * R + r] = a;
-        park[slot][j][0] = make_float4(a, apply_sigmoid_kind(raw[1], act_kind), apply_sigmoid_kind(raw[2], act_kind),
-                                       apply_sigmoid_kind(raw[3], act_kind));
+        float c0 = apply_sigmoid_kind(raw[1], act_kind), c1 = apply_sigmoid_kind(raw[2], act_kind), c2 = apply_sigmoid_kind(raw[3], act_kind);
+        if constexpr (K >= 0) { c0 = lin * c0; c1 = lin * c1; c2 = lin * c2; }
+        park[slot][j][0] = make_float4(a, c0, c1, c2);
         park[slot][j][1] = make_float4(rdp[0], rdp[1], rdp[2], rg);
       }
       __syncthreads();
@@ -134,6 +148,42 @@ __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const fl
 
 using namespace na;
 
+// `order` -1: the per-voxel RGB head (C = 3); 0 .. 4: the pos-linear-view head
+static int dyn_voxel_render_any(const char* who, int order, const float* rays, const float* t_ray, int64_t R, const float* ts, int T,
+                                const float* densities, const float* rgb, const float* ctrl_pts_grid, const float* rigidity_grid, int S,
+                                int n_ctrl, double grid_radius, int act_kind, int bg_kind, float* out, float* depth, float* acc,
+                                float* flow, float* rigidity_map, float* alpha, float* weights, void* stream) {
+  NA_REQUIRE(act_kind >= NA_SIG_NORMAL && act_kind <= NA_SIG_IDENTITY, NA_EUNSUPPORTED, "%s: activation kind %d", who, act_kind);
+  NA_REQUIRE(bg_kind == NA_BG_BLACK || bg_kind == NA_BG_WHITE, NA_EUNSUPPORTED, "%s: bg kind %d", who, bg_kind);
+  if (R == 0) return NA_OK;
+#define NA_DVR_PTR(p) NA_REQUIRE(p != nullptr, NA_ENULL, "%s: null pointer " #p, who)
+  NA_DVR_PTR(rays); NA_DVR_PTR(t_ray); NA_DVR_PTR(ts); NA_DVR_PTR(densities); NA_DVR_PTR(rgb); NA_DVR_PTR(ctrl_pts_grid);
+  NA_DVR_PTR(rigidity_grid); NA_DVR_PTR(out);
+#undef NA_DVR_PTR
+  NA_REQUIRE(order < 0 || ((order + 1) * (order + 1) + 3) % 4 != 0 || ((uintptr_t)rgb & 15) == 0, NA_EINVAL,
+             "%s: rgb must be 16-byte aligned at order %d", who, order);
+  const VoxGrid g = vox_grid(S, grid_radius);
+  const DvrMaps m{depth, acc, flow, rigidity_map, alpha, weights};
+#define NA_DVR_LAUNCH_K(NC, K)                                                                                                             \
+  hipLaunchKernelGGL((dyn_voxel_render_kernel<NC, K>), dim3(grid_for(R, NA_DVR_BLOCK / NA_DVR_LANES)), dim3(NA_DVR_BLOCK), 0, (hipStream_t)stream, \
+                     rays, t_ray, ts, T, R, g, densities, rgb, ctrl_pts_grid, rigidity_grid, act_kind, bg_kind, out, m)
+#define NA_DVR_LAUNCH_M1(NC) NA_DVR_LAUNCH_K(NC, -1)
+#define NA_DVR_LAUNCH_0(NC) NA_DVR_LAUNCH_K(NC, 0)
+#define NA_DVR_LAUNCH_1(NC) NA_DVR_LAUNCH_K(NC, 1)
+#define NA_DVR_LAUNCH_2(NC) NA_DVR_LAUNCH_K(NC, 2)
+#define NA_DVR_LAUNCH_3(NC) NA_DVR_LAUNCH_K(NC, 3)
+#define NA_DVR_LAUNCH_4(NC) NA_DVR_LAUNCH_K(NC, 4)
+  switch (order) {
+    case 0: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_0) break;
+    case 1: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_1) break;
+    case 2: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_2) break;
+    case 3: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_3) break;
+    case 4: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_4) break;
+    default: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_M1) break;
+  }
+  return check_launch(who);
+}
+
 extern "C" {
 
 int na_dyn_voxel_render(const float* rays, const float* t_ray, int64_t R, const float* ts, int T, const float* densities, const float* rgb,
@@ -144,21 +194,20 @@ int na_dyn_voxel_render(const float* rays, const float* t_ray, int64_t R, const 
   NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED,
              "na_dyn_voxel_render: n_ctrl %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", n_ctrl);
   if (int rc = vox_check_grid("na_dyn_voxel_render", S, C, grid_radius)) return rc;
-  NA_REQUIRE(act_kind >= NA_SIG_NORMAL && act_kind <= NA_SIG_IDENTITY, NA_EUNSUPPORTED, "na_dyn_voxel_render: activation kind %d", act_kind);
-  NA_REQUIRE(bg_kind == NA_BG_BLACK || bg_kind == NA_BG_WHITE, NA_EUNSUPPORTED, "na_dyn_voxel_render: bg kind %d", bg_kind);
-  if (R == 0) return NA_OK;
-#define NA_DVR_PTR(p) NA_REQUIRE(p != nullptr, NA_ENULL, "na_dyn_voxel_render: null pointer " #p)
-  NA_DVR_PTR(rays); NA_DVR_PTR(t_ray); NA_DVR_PTR(ts); NA_DVR_PTR(densities); NA_DVR_PTR(rgb); NA_DVR_PTR(ctrl_pts_grid);
-  NA_DVR_PTR(rigidity_grid); NA_DVR_PTR(out);
-#undef NA_DVR_PTR
-  const VoxGrid g = vox_grid(S, grid_radius);
-  const DvrMaps m{depth, acc, flow, rigidity_map, alpha, weights};
-#define NA_DVR_LAUNCH(NC)                                                                                                                  \
-  hipLaunchKernelGGL(dyn_voxel_render_kernel<NC>, dim3(grid_for(R, NA_DVR_BLOCK / NA_DVR_LANES)), dim3(NA_DVR_BLOCK), 0, (hipStream_t)stream, rays, t_ray, \
-                     ts, T, R, g, densities, rgb, ctrl_pts_grid, rigidity_grid, act_kind, bg_kind, out, m)
-  NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH)
-#undef NA_DVR_LAUNCH
-  return check_launch("na_dyn_voxel_render");
+  return dyn_voxel_render_any("na_dyn_voxel_render", -1, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid, S, n_ctrl,
+                              grid_radius, act_kind, bg_kind, out, depth, acc, flow, rigidity_map, alpha, weights, stream);
+}
+
+int na_dyn_voxel_plv_render(const float* rays, const float* t_ray, int64_t R, const float* ts, int T, const float* densities,
+                            const float* rgb, const float* ctrl_pts_grid, const float* rigidity_grid, int S, int order, int n_ctrl,
+                            double grid_radius, int act_kind, int bg_kind, float* out, float* depth, float* acc, float* flow,
+                            float* rigidity_map, float* alpha, float* weights, void* stream) {
+  NA_REQUIRE(T >= 1 && R >= 0, NA_EINVAL, "na_dyn_voxel_plv_render: bad shape T=%d R=%lld", T, (long long)R);
+  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED,
+             "na_dyn_voxel_plv_render: n_ctrl %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", n_ctrl);
+  if (int rc = vox_plv_check_grid("na_dyn_voxel_plv_render", S, order, grid_radius)) return rc;
+  return dyn_voxel_render_any("na_dyn_voxel_plv_render", order, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid, S,
+                              n_ctrl, grid_radius, act_kind, bg_kind, out, depth, acc, flow, rigidity_map, alpha, weights, stream);
 }
 
 }  // extern "C"

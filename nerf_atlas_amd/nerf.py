@@ -619,7 +619,10 @@ def arc_len_grid(grid, samples: int = 16 ** 3, idxs=None):
 class NeRFVoxel(CommonNeRF):
     """src/nerf.py:401-524: a dense grid of densities [S,S,S,1] and per-voxel colour parameters rgb [S,S,S,C], read by the reference's
     8-neighbour lookup (csrc/voxel.hip) -- no MLP anywhere.  The static model with the per-voxel RGB head
-    (`--refl-kind pos`, refl.Positional.to_voxel); the parameters keep the reference's names, so its state_dict loads.
+    (`--refl-kind pos`, refl.Positional.to_voxel) or the view-dependent one (`--refl-kind pos-linear-view --voxel-refl-order K`,
+    refl.PosLinearView.to_voxel: rgb rows [raw rgb | (K+1)^2 spherical-harmonic coefficients], csrc/voxel_plv.hip, DESIGN.md 3p --
+    both routes below then run the ops.voxel_plv_* / autograd.VoxelPlvSampleFn operators); the parameters keep the reference's names,
+    so its state_dict loads.
 
     Routes of `forward` / `from_pts`:
       eval, no gradients  ops.voxel_render: positions, lookup, activation and compositing as ONE launch (two with bg "random")
@@ -707,16 +710,32 @@ class NeRFVoxel(CommonNeRF):
         kind = self.sigmoid_kind if self._head is None else getattr(self._head, "act_kind", None)
         return kind if kind in ops.SIGMOID else None
 
+    def _plv(self):
+        """the pos-linear-view head is installed: rgb rows are [raw rgb | (order + 1)^2 coefficients] (csrc/voxel_plv.hip)"""
+        return type(self._head) is refl.PosLinearView
+
     def _fusable(self, pts=None):
+        if not self.training and not ag.needs_grad(pts, self.densities, self.rgb) and self._act_kind() is not None and self._plv():
+            return self.rgb.shape[-1] == 3 + self._head.num_sh_coeffs
         return (not self.training and not ag.needs_grad(pts, self.densities, self.rgb) and self.rgb.shape[-1] == 3
                 and self._act_kind() is not None and (self._head is None or type(self._head) is refl.Positional))
 
     def _render(self, rays, ts, pts=None):
-        out, self.alpha, self.weights = ops.voxel_render(rays.contiguous(), ts, self.densities.data, self.rgb.data, self.grid_radius,
-                                                         self._act_kind(), self._kernel_bg(), True, pts=pts)
+        render = ops.voxel_plv_render if self._plv() else ops.voxel_render
+        out, self.alpha, self.weights = render(rays.contiguous(), ts, self.densities.data, self.rgb.data, self.grid_radius,
+                                               self._act_kind(), self._kernel_bg(), True, pts=pts)
         return self._finish_sky(out)
 
     def _operators(self, rays, ts, r_d, pts=None):
+        if self._plv():
+            # lookup with the coefficients contracted in the kernel -> split -> activation -> linear scale -> compositing
+            raw, sh = ag.VoxelPlvSampleFn.apply(self.densities, self.rgb, self.grid_radius, rays.contiguous(),
+                                                None if pts is None else pts.contiguous(), None if pts is not None else ts)
+            if ag.needs_grad(raw):
+                density, params = ag.SplitHeadFn.apply(raw)
+            else:
+                density, params = raw[..., 0].contiguous(), raw[..., 1:]
+            return self._composite(density, self.brdf(params=params.contiguous(), view=r_d, sh=sh), ts, rays)
         if pts is None:
             raw = ag.VoxelSampleFn.apply(self.densities, self.rgb, self.grid_radius, None, rays.contiguous(), ts)
         else:
@@ -1001,7 +1020,8 @@ class DynamicNeRFVoxel(nn.Module):
     parameters keep the reference's names, so its state_dict loads.
 
     Routes of `forward((rays, t))`:
-      eval, no gradients  ops.dyn_voxel_warp, then the canonical's one-launch render at the warped points (ops.voxel_render)
+      eval, no gradients  ops.dyn_voxel_warp, then the canonical's one-launch render at the warped points (ops.voxel_render /
+                          ops.voxel_plv_render by the head)
       otherwise           autograd.DynVoxelWarpFn, then the canonical's operator route, whose lookup returns the position gradient
     The reference marks `pts` as requiring a gradient in training for regularisers that are not built here; pts stays a
     plain tensor and no gradient is formed for it."""
@@ -1070,7 +1090,7 @@ class DynamicNeRFVoxel(nn.Module):
                                "torch.no_grad()); training goes through forward")
         if not c._fusable():
             raise RuntimeError(f"DynamicNeRFVoxel.forward_maps needs the canonical model's one-launch route: the per-voxel RGB head "
-                               f"with 3 colour parameters and a named activation, got {type(c._head).__name__} / {c.rgb.shape[-1]} / "
+                               f"with 3 colour parameters (or the pos-linear-view head) and a named activation, got {type(c._head).__name__} / {c.rgb.shape[-1]} / "
                                f"{c.sigmoid_kind}")
         if c.resolution != self.rigidity_grid.shape[0]:
             raise ValueError(f"DynamicNeRFVoxel: the canonical grids are {c.resolution}^3 and the deformation grids "
@@ -1081,7 +1101,7 @@ class DynamicNeRFVoxel(nn.Module):
             want.append("weights")  # (the random sky is added behind the launch from the weights)
         tt = t[:, None, None].expand(rays.shape[:-1]).contiguous()
         res = ops.dyn_voxel_render(rays.contiguous(), tt, ts, c.densities.data, c.rgb.data, self.ctrl_pts_grid.data, self.rigidity_grid.data,
-                                   self.spline, c.grid_radius, c._act_kind(), c._kernel_bg(), want=want)
+                                   self.spline, c.grid_radius, c._act_kind(), c._kernel_bg(), want=want, plv=c._plv())
         weights = res.pop("weights", None)
         if weights is not None:
             kept, c.weights = c.weights, weights

@@ -1744,6 +1744,109 @@ def voxel_sample_backward_pts(g_raw: torch.Tensor, pts: torch.Tensor, densities:
     return g_pts
 
 
+# ------------------------------------------------------------------------------------------------- NeRFVoxel, pos-linear-view head (csrc/voxel_plv.hip)
+PLV_CHANNELS = {3 + (k + 1) ** 2: k for k in range(5)}  # C = 3 + (order + 1)^2 -> order
+
+
+def _voxel_plv_grid(densities: torch.Tensor, rgb: torch.Tensor):
+    """(densities, rgb, S, order) of the pos-linear-view voxel head: rgb [S,S,S, 3 + (order+1)^2], a 16-byte aligned grid"""
+    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
+    if Cn not in PLV_CHANNELS:
+        raise ValueError(f"rgb has {Cn} channels: the pos-linear-view voxel head holds 3 + (order + 1)^2 = {sorted(PLV_CHANNELS)}")
+    return densities, _aligned16(rgb), S, PLV_CHANNELS[Cn]
+
+
+def _voxel_plv_positions(rays, pts, ts):
+    """(pts or None, rays [R,6], ts or None, R, T, batch of one row of samples): explicit pts [T, *rays.shape[:-1], 3] (any T), or rays x ts;
+    the ray of sample n is n % R either way"""
+    rays = _f32(rays, "rays")
+    if rays.shape[-1] != 6:
+        raise ValueError(f"rays must be [..., 6], got {tuple(rays.shape)}")
+    R = rays.numel() // 6
+    if pts is not None:
+        pts = _f32(pts, "pts")
+        if pts.shape[-1] != 3 or R == 0 or (pts.numel() // 3) % R != 0:
+            raise ValueError(f"pts must be [T, ..., 3] over the {R} rays, got {tuple(pts.shape)}")
+        return pts, rays, None, R, pts.numel() // 3 // R, tuple(pts.shape[:-1])
+    if ts is None:
+        raise ValueError("voxel lookup needs explicit pts, or ts")
+    ts = _f32(ts, "ts")
+    if ts.dim() != 1:
+        raise ValueError(f"ts must be [T], got {tuple(ts.shape)}")
+    return None, rays, ts, R, ts.shape[0], (ts.shape[0],) + tuple(rays.shape[:-1])
+
+
+def voxel_plv_sample(densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float, rays: torch.Tensor,
+                     pts: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None):
+    """(raw [..., 4] = [density | 3 colour parameters], sh [...] = sum_k Y_k(normalize(rays[..., 3:])) c_k) of NeRFVoxel's lookup with
+    the pos-linear-view head, at explicit pts [T, *rays.shape[:-1], 3] or at o + t d of rays x ts [T]."""
+    lib = _lib.load()
+    densities, rgb, S, order = _voxel_plv_grid(densities, rgb)
+    pts, rays, ts, R, T, batch = _voxel_plv_positions(rays, pts, ts)
+    raw = torch.empty(batch + (4,), device=densities.device, dtype=torch.float32)
+    sh = torch.empty(batch, device=densities.device, dtype=torch.float32)
+    check(lib.na_voxel_plv_sample(_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, order, float(grid_radius),
+                                  _ptr(raw), _ptr(sh), _stream()))
+    return raw, sh
+
+
+def voxel_plv_sample_backward(g_raw: torch.Tensor, g_sh: torch.Tensor, S: int, order: int, grid_radius: float, rays: torch.Tensor,
+                              pts: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None, variant: Optional[int] = None):
+    """(g_densities [S,S,S,1], g_rgb [S,S,S, 3 + (order+1)^2]) of voxel_plv_sample given g_raw [..., 4], g_sh [...] and the same
+    positions.  variant: scatter variant 1 or 2 (measurements); None runs the shipped one."""
+    lib = _lib.load()
+    g_raw, g_sh = _f32(g_raw, "g_raw"), _f32(g_sh, "g_sh")
+    if S % 2 != 0 or S < 2:
+        raise ValueError(f"voxel resolution {S}: even resolutions only")
+    if order not in range(5):
+        raise ValueError(f"order {order!r} outside 0..4")
+    pts, rays, ts, R, T, _ = _voxel_plv_positions(rays, pts, ts)
+    if g_raw.numel() != T * R * 4 or g_sh.numel() != T * R:
+        raise ValueError(f"g_raw must be [..., 4] and g_sh [...] with one row per sample ({T * R}), got {tuple(g_raw.shape)} and {tuple(g_sh.shape)}")
+    g_raw = _aligned16(g_raw)
+    Cn = 3 + (order + 1) ** 2
+    config.require_deterministic_workspace(8 * S ** 3 * (1 + Cn))  # (a no-op outside config.set_deterministic's mode)
+    g_den = torch.zeros(S, S, S, 1, device=g_raw.device, dtype=torch.float32)
+    g_rgb = torch.zeros(S, S, S, Cn, device=g_raw.device, dtype=torch.float32)
+    args = (_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(g_raw), _ptr(g_sh), S, order, float(grid_radius), _ptr(g_den), _ptr(g_rgb))
+    if variant is None:
+        check(lib.na_voxel_plv_sample_backward(*args, _stream()))
+    else:
+        check(lib.na_voxel_plv_sample_backward_variant(*args, int(variant), _stream()))
+    return g_den, g_rgb
+
+
+def voxel_plv_sample_backward_pts(g_raw: torch.Tensor, g_sh: torch.Tensor, pts: torch.Tensor, rays: torch.Tensor, densities: torch.Tensor,
+                                  rgb: torch.Tensor, grid_radius: float) -> torch.Tensor:
+    """g_pts [..., 3]: the gradient of voxel_plv_sample w.r.t. explicit pts given g_raw [..., 4] and g_sh [...] (a gather, no atomics)"""
+    lib = _lib.load()
+    densities, rgb, S, order = _voxel_plv_grid(densities, rgb)
+    pts, rays, _, R, T, _ = _voxel_plv_positions(rays, pts, None)
+    g_raw, g_sh = _f32(g_raw, "g_raw"), _f32(g_sh, "g_sh")
+    if g_raw.numel() != T * R * 4 or g_sh.numel() != T * R:
+        raise ValueError(f"g_raw must be [..., 4] and g_sh [...] with one row per sample ({T * R}), got {tuple(g_raw.shape)} and {tuple(g_sh.shape)}")
+    g_raw = _aligned16(g_raw)
+    g_pts = torch.empty(pts.shape, device=pts.device, dtype=torch.float32)
+    check(lib.na_voxel_plv_sample_backward_pts(_ptr(pts), _ptr(rays), R, T * R, _ptr(densities), _ptr(rgb), _ptr(g_raw), _ptr(g_sh), S, order,
+                                               float(grid_radius), _ptr(g_pts), _stream()))
+    return g_pts
+
+
+def voxel_plv_render(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float,
+                     sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True, pts: Optional[torch.Tensor] = None):
+    """NeRFVoxel's eval route with the pos-linear-view head as ONE launch: basis per ray, positions (o + t d, or explicit pts
+    [T, ..., 3]) -> lookup -> activation x linear scale -> compositing.  Outputs and backgrounds of voxel_render."""
+    lib = _lib.load()
+    densities, rgb, S, order = _voxel_plv_grid(densities, rgb)
+    rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
+    T = ts.shape[0]
+    R, pts = _ls_batch(rays, T, pts)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
+    check(lib.na_voxel_plv_render(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, order, float(grid_radius),
+                                  SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
+    return out, alpha, weights
+
+
 # ------------------------------------------------------------------------------------------------- DynamicNeRFVoxel (csrc/dyn_voxel.hip)
 def _dyn_voxel_grids(ctrl_pts_grid: torch.Tensor, rigidity_grid: torch.Tensor, spline: int):
     """S of ctrl_pts_grid [S,S,S,3(spline-1)] and rigidity_grid [S,S,S,1]"""
@@ -1821,13 +1924,18 @@ DYN_VOXEL_MAPS = ("depth", "acc", "flow", "rigidity", "alpha", "weights")
 
 def dyn_voxel_render(rays: torch.Tensor, t: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor,
                      ctrl_pts_grid: torch.Tensor, rigidity_grid: torch.Tensor, spline: int, grid_radius: float,
-                     sigmoid_kind: str = "upshifted", bg: str = "black", want=("depth", "flow", "rigidity")):
+                     sigmoid_kind: str = "upshifted", bg: str = "black", want=("depth", "flow", "rigidity"), plv: bool = False):
     """DynamicNeRFVoxel's test-time render as ONE launch (csrc/dyn_voxel_render.hip): rays [..., 6] at times t [...] (one per ray, expanded
     by the caller) over the steps ts [T] -> dict(rgb [..., 3] + the outputs named in `want`: depth [..., 1], acc [..., 1], flow [..., 3],
     rigidity [..., 1] -- the maps of runner.py:894-916 -- and alpha, weights [T, ...]).  Bit for bit compute_pts -> dyn_voxel_warp ->
-    voxel_render(pts=warped) -> integrate x 4, without their per-sample tensors.  bg black | white (random: black, then sky_random)."""
+    voxel_render(pts=warped) -> integrate x 4, without their per-sample tensors.  bg black | white (random: black, then sky_random).
+    plv: the canonical model carries the pos-linear-view head (rgb [S,S,S, 3 + (order+1)^2]; na_dyn_voxel_plv_render, the composition
+    then being over voxel_plv_render)."""
     lib = _lib.load()
-    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
+    if plv:
+        densities, rgb, S, Cn = _voxel_plv_grid(densities, rgb)  # (Cn: the order)
+    else:
+        densities, rgb, S, Cn = _voxel_grid(densities, rgb)
     ctrl, rig, S2 = _dyn_voxel_grids(ctrl_pts_grid, rigidity_grid, spline)
     if S2 != S:
         raise ValueError(f"the canonical grids are {S}^3 and the deformation grids {S2}^3")
@@ -1847,9 +1955,9 @@ def dyn_voxel_render(rays: torch.Tensor, t: torch.Tensor, ts: torch.Tensor, dens
                         ("alpha", (T,) + batch), ("weights", (T,) + batch)):
         if name in want:
             res[name] = new(*shape)
-    check(lib.na_dyn_voxel_render(_ptr(rays), _ptr(t), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), _ptr(ctrl), _ptr(rig), S, Cn, spline,
-                                  float(grid_radius), SIGMOID[sigmoid_kind], BG[bg], _ptr(res["rgb"]),
-                                  *(_ptr(res.get(name)) for name in DYN_VOXEL_MAPS), _stream()))
+    entry = lib.na_dyn_voxel_plv_render if plv else lib.na_dyn_voxel_render
+    check(entry(_ptr(rays), _ptr(t), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), _ptr(ctrl), _ptr(rig), S, Cn, spline, float(grid_radius),
+                SIGMOID[sigmoid_kind], BG[bg], _ptr(res["rgb"]), *(_ptr(res.get(name)) for name in DYN_VOXEL_MAPS), _stream()))
     return res
 
 

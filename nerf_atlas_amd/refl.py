@@ -100,18 +100,44 @@ class Positional(Reflectance):
 class PosLinearView(Reflectance):
     """src/refl.py:248-290 (view='raw')."""
 
-    def __init__(self, space=None, view="raw", intermediate_size=64, **kwargs):
+    def __init__(self, space=None, view="raw", intermediate_size=64, voxel_order=None, **kwargs):
         super().__init__(**kwargs)
         assert view == "raw"
+        if voxel_order is not None and not (isinstance(voxel_order, int) and 0 <= voxel_order <= 4):
+            raise ValueError(f"--voxel-refl-order must be an integer in 0..4, got {voxel_order!r}")
+        self.voxel_order = voxel_order  # order of the per-voxel expansion `to_voxel` installs (None: no voxel form)
         self.im = intermediate_size
         self.pos = SkipConnMLP(in_size=3, out=self.out_features + self.im, latent_size=self.latent_size,
                                enc=HashEncoder(input_dims=3), num_layers=2, hidden_size=256)
         self.view = SkipConnMLP(in_size=6, out=1, latent_size=self.latent_size + self.im, num_layers=2,
                                 hidden_size=128, init="siren", activation=torch.sin)
 
+    def pos_linear_voxel_forward(self, params, view, sh=None):
+        """src/refl.py:265-272: act(raw rgb) * (sigmoid(eval_sh(order, coefficients, normalize(view))) / 2 + 0.5).  NeRFVoxel's lookup
+        contracts the coefficients with the ray's basis itself (csrc/voxel_plv.hip), so `params` are the 3 interpolated colour
+        parameters and `sh` the expansion in front of the sigmoid; the combination is pos_linear_combine's kernel."""
+        if sh is None:
+            raise ValueError("the pos-linear-view voxel head is evaluated by NeRFVoxel's lookup (ops.voxel_plv_sample): pass its `sh`")
+        pos, lin = self.act(params), sh.unsqueeze(-1)
+        if ag.needs_grad(lin, pos):
+            return ag.PosLinearCombineFn.apply(lin, pos, self.out_features)
+        return ops.pos_linear_combine(lin, pos, self.out_features)
+
     def to_voxel(self):
-        raise NotImplementedError("refl kind 'pos-linear-view' as a voxel head (src/refl.py:265-280: rgb | 25 spherical-harmonic "
-                                  "coefficients per voxel) is not built: --model voxel takes --refl-kind pos")
+        """src/refl.py:273-280: both MLPs are deleted and the grid holds out_features + (order + 1)^2 parameters per voxel.  The
+        reference hard-codes order 4 ("TODO where to pass this into this function?"); here --voxel-refl-order is that place, and
+        without it the head has no voxel form."""
+        if self.voxel_order is None:
+            raise NotImplementedError("refl kind 'pos-linear-view' as a voxel head (src/refl.py:265-280: rgb | (order + 1)^2 spherical-"
+                                      "harmonic coefficients per voxel) needs --voxel-refl-order K, K in 0..4 (the reference's is 4); "
+                                      "without it --model voxel takes --refl-kind pos")
+        if self.out_features != 3:
+            raise NotImplementedError(f"the pos-linear-view voxel head with {self.out_features} colour parameters (3 have a kernel)")
+        del self.pos
+        del self.view
+        self.order = order = self.voxel_order
+        self.num_sh_coeffs = (order + 1) * (order + 1)
+        return self.out_features + self.num_sh_coeffs, self.pos_linear_voxel_forward
 
     def forward(self, x, view, normal=None, light=None, latent=None):
         if hasattr(latent, "tensor") and not torch.is_tensor(latent):
@@ -242,5 +268,7 @@ def load(args, refl_kind: str, space_kind: str, latent_size: int):
     kwargs = {}
     if refl_kind == "sph-har":
         kwargs["order"] = getattr(args, "refl_order", 2)  # src/refl.py:33
+    if refl_kind == "pos-linear-view":
+        kwargs["voxel_order"] = getattr(args, "voxel_refl_order", None)  # this build's flag
     return cons(latent_size=latent_size, act=args.sigmoid_kind, out_features=args.feature_space,
                 normal=getattr(args, "normal_kind", None), bidirectional=getattr(args, "refl_bidirectional", True), **kwargs)

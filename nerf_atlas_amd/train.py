@@ -46,6 +46,7 @@ DEFAULTS = dict(
     voxel_tv_sigma=0.0, voxel_tv_rgb=0.0, voxel_tv_bezier=0.0, voxel_tv_rigidity=0.0,  # runner.py:289-301
     voxel_random_spline_len_decay=0.0, spline_len_decay=0.0,  # runner.py:276-283
     voxel_upsample=[],  # this build's flag: ITER:RESO pairs, NeRFVoxel.upsample(RESO) at the start of iteration ITER
+    voxel_refl_order=None,  # this build's flag: order K (0..4) of the per-voxel pos-linear-view head, the reference's hard-coded 4
     depth_images=False, flow_map=False, rigidity_map=False, with_alpha=False,  # runner.py:360-392: maps next to the test frames
     render_over_time=-1, render_over_time_steps=100, render_over_time_end_sec=1.0,  # runner.py:252-261: a time sweep of one test camera
 )
@@ -107,7 +108,7 @@ def args_from_argv(argv) -> SimpleNamespace:
         elif isinstance(v, list):
             p.add_argument(flag, nargs="+", default=v, type=type(v[0]) if v else str)
         elif v is None:
-            p.add_argument(flag, default=None, type=(int if k == "spline" else str))
+            p.add_argument(flag, default=None, type=(int if k in ("spline", "voxel_refl_order") else str))
         else:
             p.add_argument(flag, type=type(v), default=v)
     p.add_argument("--nosave", action="store_true")
@@ -116,6 +117,20 @@ def args_from_argv(argv) -> SimpleNamespace:
     p.add_argument("--outdir", default="outputs/")
     ns = vars(p.parse_args(argv))
     return make_args(**{k: ns[k] for k in DEFAULTS if k in ns})
+
+
+def check_voxel_refl_order(args):
+    """--voxel-refl-order K: the order of the spherical-harmonic expansion PosLinearView.to_voxel installs per voxel (the reference
+    hard-codes 4, src/refl.py:278).  Only meaningful for --model voxel --refl-kind pos-linear-view; anything else raises by name."""
+    k = getattr(args, "voxel_refl_order", None)
+    if k is None:
+        return
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= 4:
+        raise ValueError(f"--voxel-refl-order {k!r}: an integer in 0..4 (the reference's head is order 4)")
+    if args.model != "voxel":
+        raise ValueError(f"--voxel-refl-order {k} over --model {args.model}: the flag sets the per-voxel head of --model voxel")
+    if args.refl_kind != "pos-linear-view":
+        raise ValueError(f"--voxel-refl-order {k} with --refl-kind {args.refl_kind}: the flag belongs to --refl-kind pos-linear-view")
 
 
 def seed(s):
@@ -142,6 +157,7 @@ def load_model(args, is_dyn=False, device="cuda"):
         if why is not None:
             raise ValueError(f"--steps-fine {steps_fine} (coarse -> fine training) needs --model plain --refl-kind view without --mip "
                              f"and without a --dyn-model; got {why}")
+    check_voxel_refl_order(args)
     model = nerf.load_nerf(args)
     if is_dyn:
         model = nerf.load_dyn(args, model, device)

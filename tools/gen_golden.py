@@ -1016,17 +1016,18 @@ VOXEL_CASES = {  # name: (S, T, ray batch shape, act, bg)
 }
 
 
-def _voxel_build(S, T, act, bg):
-    """the reference's NeRFVoxel + Positional constructed directly (its runner wiring is dead: DESIGN.md 7), procedural grids"""
+def _voxel_build(S, T, act, bg, head=None):
+    """the reference's NeRFVoxel + Positional (or the head class given) constructed directly (its runner wiring is dead: DESIGN.md 7),
+    procedural grids"""
     m = rnerf.NeRFVoxel(resolution=S, t_near=2.0, t_far=6.0, steps=T)
-    m.set_refl(rrefl.Positional(act=act, latent_size=0, out_features=3))
+    m.set_refl((head or rrefl.Positional)(act=act, latent_size=0, out_features=3))
     m.set_bg(bg)
     m.eval()
     names, shapes = fill_procedural(m)
     return m, names, shapes
 
 
-def g23():
+def g23(prefix="g23_voxel_", head=None, cases=None):
     """g23_voxel_<case>: the reference's NeRFVoxel (src/nerf.py:401-524) with the per-voxel Positional head, eval mode, near 2 / far 6,
     generic rays (tests/voxel_ref.py generic_rays: origins on the radius-4 sphere, so the first samples of every ray are extrapolated),
     in fp32 AND fp64: out, alpha, weights and the reference's own fp32 - fp64 deviation.  A case whose two precisions disagree by more
@@ -1036,8 +1037,11 @@ def g23():
     import copy
     sys.path.insert(0, os.path.join(REPO, "tests"))
     import voxel_ref as V
+    tag = prefix.split("_")[0]
     for name, (S, T, shape, act, bg) in VOXEL_CASES.items():
-        m, names, shapes = _voxel_build(S, T, act, bg)
+        if cases is not None and name not in cases:
+            continue
+        m, names, shapes = _voxel_build(S, T, act, bg, head)
         m64 = copy.deepcopy(m).double()
         for seed in range(4500, 4600, 2):
             rays = V.generic_rays(shape, seed)
@@ -1046,11 +1050,11 @@ def g23():
             dev = {k: float((a.double() - b).abs().max()) for k, a, b in (("out", out, out64), ("alpha", alpha, alpha64), ("weights", weights, weights64))}
             if max(dev.values()) <= 1e-5:
                 break
-            print(f"g23 {name}: seed {seed} skipped, the reference's fp32 and fp64 disagree by {max(dev.values()):.2e}")
+            print(f"{tag} {name}: seed {seed} skipped, the reference's fp32 and fp64 disagree by {max(dev.values()):.2e}")
         else:
-            raise AssertionError(f"g23 {name}: no seed on which the reference agrees with itself")
+            raise AssertionError(f"{tag} {name}: no seed on which the reference agrees with itself")
         opac = weights64[:-1].sum(0)
-        print(f"g23 {name}: seed {seed}, opacity before the last sample {float(opac.min()):.2f}..{float(opac.max()):.2f}; fp32 vs fp64: "
+        print(f"{tag} {name}: seed {seed}, opacity before the last sample {float(opac.min()):.2f}..{float(opac.max()):.2f}; fp32 vs fp64: "
               + " ".join(f"{k} {v:.2e}" for k, v in dev.items()))
         kw = dict(rays=rays, S=S, steps=T, near=2.0, far=6.0, act=act, bg=bg, grid_radius=m.grid_radius, seed=seed, ts=ts,
                   out=out, out64=out64, alpha=alpha, alpha64=alpha64, weights=weights, weights64=weights64,
@@ -1063,7 +1067,7 @@ def g23():
                 for p_ in m.parameters(): p_.requires_grad_(True)
                 m(rays).square().sum().backward()
             g_dev = [float((a.grad.double() - b.grad).abs().max() / b.grad.abs().max()) for a, b in ((m.densities, m64.densities), (m.rgb, m64.rgb))]
-            print(f"g23 {name}: the reference's fp32 gradients are {g_dev[0]:.2e} (densities) / {g_dev[1]:.2e} (rgb) of the largest entry off its fp64 ones")
+            print(f"{tag} {name}: the reference's fp32 gradients are {g_dev[0]:.2e} (densities) / {g_dev[1]:.2e} (rgb) of the largest entry off its fp64 ones")
             kw.update(g_densities64=m64.densities.grad, g_rgb64=m64.rgb.grad, g_dev=np.array(g_dev))
             lat = V.lattice_points(S, m.grid_radius)
             seen, orig = [], rnerf.trilinear_weights
@@ -1074,7 +1078,7 @@ def g23():
                 rnerf.trilinear_weights = orig
             assert ids.dtype == torch.int64 and seen[0].dtype == torch.float32
             kw.update(lat_pts=lat, lat_ids=ids, lat_xyz=seen[0])
-        save(f"g23_voxel_{name}", **kw)
+        save(f"{prefix}{name}", **kw)
 
 
 GRID_TV_CASES = {
@@ -1120,7 +1124,7 @@ DYN_VOXEL_CASES = {  # name: (S, spline, T, ray batch shape [B, H, W], times [B]
 DYN_VOXEL_GRADS = ("canonical.densities", "canonical.rgb", "ctrl_pts_grid", "rigidity_grid")
 
 
-def g25():
+def g25(prefix="g25_dyn_voxel_", head=None, cases=None):
     """g25_dyn_voxel_<case>: the reference's DynamicNeRFVoxel (src/nerf.py:1526-1586) over its NeRFVoxel + Positional, all three built
     directly (load_dyn's own call is a TypeError: DESIGN.md 7), eval mode, near 2 / far 6, procedural grids (stored as specs; proc_param
     fills rigidity_grid too, so the rigidity is not the constant 1/2 of the zero init), voxel_ref.generic_rays and 2-3 times per batch,
@@ -1131,8 +1135,9 @@ def g25():
     import copy
     sys.path.insert(0, os.path.join(REPO, "tests"))
     import voxel_ref as V
-    for name, (S, spline, T, shape, times, act, bg) in DYN_VOXEL_CASES.items():
-        canon, _, _ = _voxel_build(S, T, act, bg)
+    tag = prefix.split("_")[0]
+    for name, (S, spline, T, shape, times, act, bg) in (cases or DYN_VOXEL_CASES).items():
+        canon, _, _ = _voxel_build(S, T, act, bg, head)
         m = rnerf.DynamicNeRFVoxel(canon, spline=spline)
         m.eval()
         names, shapes = fill_procedural(m)
@@ -1149,11 +1154,11 @@ def g25():
             dev = {k: float((r32[k].double() - r64[k]).abs().max()) for k in keys}
             if max(dev.values()) <= 1e-5:
                 break
-            print(f"g25 {name}: seed {seed} skipped, the reference's fp32 and fp64 disagree by {max(dev.values()):.2e}")
+            print(f"{tag} {name}: seed {seed} skipped, the reference's fp32 and fp64 disagree by {max(dev.values()):.2e}")
         else:
-            raise AssertionError(f"g25 {name}: no seed on which the reference agrees with itself")
+            raise AssertionError(f"{tag} {name}: no seed on which the reference agrees with itself")
         opac = r64["weights"][:-1].sum(0)
-        print(f"g25 {name}: seed {seed}, opacity before the last sample {float(opac.min()):.2f}..{float(opac.max()):.2f}, |dp| up to "
+        print(f"{tag} {name}: seed {seed}, opacity before the last sample {float(opac.min()):.2f}..{float(opac.max()):.2f}, |dp| up to "
               f"{float(r64['dp'].abs().max()):.2f}, rigidity {float(r64['rigidity'].min()):.2f}..{float(r64['rigidity'].max()):.2f}; "
               "fp32 vs fp64: " + " ".join(f"{k} {v:.2e}" for k, v in dev.items()))
         kw = dict(rays=rays, times=t, S=S, spline=spline, steps=T, near=2.0, far=6.0, act=act, bg=bg, grid_radius=canon.grid_radius, seed=seed,
@@ -1167,10 +1172,10 @@ def g25():
                     model((rays.to(dt), t.to(dt))).square().sum().backward()
             g32, g64 = dict(m.named_parameters()), dict(m64.named_parameters())
             g_dev = [float((g32[k].grad.double() - g64[k].grad).abs().max() / g64[k].grad.abs().max()) for k in DYN_VOXEL_GRADS]
-            print(f"g25 {name}: the reference's fp32 gradients are " + " / ".join(f"{v:.2e}" for v in g_dev)
+            print(f"{tag} {name}: the reference's fp32 gradients are " + " / ".join(f"{v:.2e}" for v in g_dev)
                   + " of the largest entry off its fp64 ones (densities, rgb, ctrl_pts_grid, rigidity_grid)")
             kw.update(g_dev=np.array(g_dev), **{"grad64." + k: g64[k].grad for k in DYN_VOXEL_GRADS})
-        save(f"g25_dyn_voxel_{name}", **kw)
+        save(f"{prefix}{name}", **kw)
 
 
 SPLINE_LEN_CASES = {  # name: (S, spline, T, ray batch shape [1, H, W], time, indices of the grid term, act, bg)
@@ -1250,9 +1255,26 @@ def g26():
         save(f"g26_spline_len_{name}", g_idxs=idxs, **kw)
 
 
+def g27():
+    """g27_voxel_plv_<case>: g23 with the reference's PosLinearView head in its voxel form (src/refl.py:265-280: rgb [S,S,S, 3 + 25],
+    order 4) -- same cases, same seed rule, same outputs and fp64 gradients; the lattice ids and xyz are g23's and are carried again."""
+    g23("g27_voxel_plv_", rrefl.PosLinearView, ("s2", "s4", "s16_ragged", "s64_black"))
+
+
+DYN_VOXEL_PLV_CASES = {  # (the layout of DYN_VOXEL_CASES)
+    "s4_n4": (4, 4, 16, (3, 4, 4), (0.0, 0.6, 1.0), "upshifted", "white"),
+    "s16_n2": (16, 2, 24, (2, 5, 7), (0.25, 0.8), "leaky_relu", "black"),
+}
+
+
+def g28():
+    """g28_dyn_voxel_plv_<case>: g25's builder over the canonical model of g27 (NeRFVoxel + PosLinearView, order 4)"""
+    g25("g28_dyn_voxel_plv_", rrefl.PosLinearView, DYN_VOXEL_PLV_CASES)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25", "g26"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25", "g26", "g27", "g28"]
     for g in which:
         globals()[g]()
     with open(os.path.join(OUT, "PROVENANCE.txt"), "w") as f:

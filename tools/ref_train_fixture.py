@@ -69,7 +69,7 @@ RECIPES = {
     "voxel_adamw": (False, ["--model", "voxel", "--refl-kind", "pos", "--loss-fns", "l2", "--opt-kind", "adamw", "-lr", "5e-2"]),
     "voxel_sgd": (False, ["--model", "voxel", "--refl-kind", "pos", "--loss-fns", "l2", "--opt-kind", "sgd", "-lr", "5000"]),
     # `make dyn_voxel` (reference makefile: --model voxel --dyn-model voxel) with the head that has a voxel form here (`pos`; the shipped
-    # recipe's pos-linear-view head is not built), both deformation-grid total-variation terms (runner.py:774-775: two more draws of 32^3
+    # recipe's pos-linear-view head is the `dyn_voxel_plv` recipe below), both deformation-grid total-variation terms (runner.py:774-775: two more draws of 32^3
     # voxel indices per iteration, after the sigma / rgb terms' place in the stream) and the NR-NeRF offset term through model.dp /
     # model.rigidity.  The rate is the `voxel` recipe's 5e-2, for that recipe's reason (the shipped 1e-2 barely leaves the start in 200
     # iterations on this scene).  The reference's load_dyn cannot build the class as shipped (src/nerf.py:1688-1696 passes refl_latent=
@@ -79,6 +79,12 @@ RECIPES = {
     "dyn_voxel": (True, ["--model", "voxel", "--refl-kind", "pos", "--loss-fns", "l2", "-lr", "5e-2", "--data-kind", "dnerf",
                          "--dyn-model", "voxel", "--spline", "4", "--voxel-tv-bezier", "0.02", "--voxel-tv-rigidity", "0.02",
                          "--offset-decay", "1"]),
+    # `make dyn_voxel` with its shipped head: the `dyn_voxel` recipe with --refl-kind pos-linear-view (PosLinearView.to_voxel,
+    # src/refl.py:273-280: 3 + 25 parameters per voxel, order 4).  Same rate, same recording flags; this build is given the argv plus
+    # its own --voxel-refl-order 4
+    "dyn_voxel_plv": (True, ["--model", "voxel", "--refl-kind", "pos-linear-view", "--loss-fns", "l2", "-lr", "5e-2", "--data-kind", "dnerf",
+                             "--dyn-model", "voxel", "--spline", "4", "--voxel-tv-bezier", "0.02", "--voxel-tv-rigidity", "0.02",
+                             "--offset-decay", "1"]),
     "dnerf": (True, ["--model", "plain", "--refl-kind", "view", "--data-kind", "dnerf", "--dyn-model", "plain",
                      "--spline", "4"]),
     # `make dnerf`'s regularisers (reference makefile:106-114) on the small scene: NR-NeRF offset decay + the FFJORD
@@ -260,7 +266,7 @@ def main():
         test_psnr=psnrs, test_psnr_mean=mean, reg_terms=captured.get("reg_terms", []),
         torch=torch.__version__, threads=cfg.threads, wall_s=round(dt, 1),
     )
-    if cfg.name == "dyn_voxel":
+    if cfg.name in ("dyn_voxel", "dyn_voxel_plv"):
         tv = captured["tv_terms"]
         fixture["tv_terms"] = [tv[i:i + 2] for i in range(0, len(tv), 2)]  # (ctrl_pts_grid, rigidity_grid) per iteration
     if cfg.name == "voxel_tv":
