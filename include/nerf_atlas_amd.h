@@ -945,6 +945,31 @@ int na_dyn_voxel_spline_len(const float* pts, int64_t N, const float* ctrl_pts_g
 int na_dyn_voxel_spline_len_backward(const float* pts, int64_t N, const float* ctrl_pts_grid, int S, int n_ctrl, double grid_radius,
                                      const float* w, const float* t, int M, const float* g_up, float* g_ctrl_pts_grid, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Divergence regularisers of DynamicNeRFVoxel (runner.py:694-700, src/utils.py:461-478; csrc/dyn_voxel_div.hip): quadratic forms of the
+ * Jacobian of the deformation w.r.t. the unwarped position.  Only xyzs = (pts - centre) / voxel_len carries a gradient in the
+ * reference's lookup, so with w_u the trilinear weights, (sx, sy, sz) = +1 / -1 by the bits of corner u and vl = voxel_len
+ *   grad w_u = (sx wy wz, wx sy wz, wx wy sz) / vl,       J_dp v = spline_t(sum_u (v . grad w_u) c_{u,k}),
+ *   J_rigid v = s (J_dp v) + dp s (1 - s) sum_u (v . grad w_u) r_u,   s = sigmoid(sum_u w_u r_u),  dp = spline_t(sum_u w_u c_{u,k}).
+ * pts [N,3], t [N], the grids, S, n_ctrl (2 .. 11, else NA_EUNSUPPORTED) and grid_radius are na_dyn_voxel_warp's, with its cells,
+ * weights, id clamping and memory-safety rule.
+ * na_dyn_voxel_jac_quad           one launch: out [N] = v . (J v), J = J_dp if rigidity_grid is NULL (--dyn-diverge-decay: v = ones gives
+ *                                 the sum of the nine entries of J_dp, utils.divergence) else J_rigid (--ffjord-div-decay: v the
+ *                                 normal draw, utils.div_approx).  v is [N,3] or NULL (= ones, bit for bit).  One thread per sample;
+ *                                 the eight rows are read once, nothing per sample but out is written.  A non-finite coordinate
+ *                                 gives NaN for that sample only.  N == 0 returns NA_OK without a launch; a NULL required pointer is
+ *                                 NA_ENULL and named in na_last_error.
+ * na_dyn_voxel_jac_quad_backward  g_ctrl_pts_grid += (zeroed by the caller) the gradient of sum_n g[n] out[n] of the J_dp form:
+ *                                 channel 3(k-1) + a of row u of a sample gets g[n] (v . grad w_u) B_k(t) v_a.  The J_rigid form has
+ *                                 no gradient in the reference and none here.  No gradient w.r.t. pts, t or v.  Accumulation modes
+ *                                 as na_dyn_voxel_warp_backward: fp32 atomics by default; under na_set_deterministic every
+ *                                 contribution goes to 2^-40 fixed point on its own (workspace >= 8 S^3 3(n-1) bytes, else
+ *                                 NA_EWORKSPACE) and the result is bitwise independent of the order of the samples.             */
+int na_dyn_voxel_jac_quad(const float* pts, const float* t, int64_t N, const float* ctrl_pts_grid, const float* rigidity_grid, int S, int n_ctrl,
+                          double grid_radius, const float* v, float* out, void* stream);
+int na_dyn_voxel_jac_quad_backward(const float* pts, const float* t, int64_t N, int S, int n_ctrl, double grid_radius, const float* v,
+                                   const float* g, float* g_ctrl_pts_grid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

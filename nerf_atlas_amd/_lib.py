@@ -263,6 +263,8 @@ SIGNATURES = {
                                           C.c_void_p]),
     "na_dyn_voxel_spline_len_backward": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_int, C.c_int, C.c_double, c_f32p, c_f32p, C.c_int, c_f32p,
                                                    c_f32p, C.c_void_p]),
+    "na_dyn_voxel_jac_quad": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, c_f32p, C.c_int, C.c_int, C.c_double, c_f32p, c_f32p, C.c_void_p]),
+    "na_dyn_voxel_jac_quad_backward": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_double, c_f32p, c_f32p, c_f32p, C.c_void_p]),
 }
 
 _lib = None

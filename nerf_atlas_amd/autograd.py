@@ -643,3 +643,22 @@ class DynVoxelSplineLenFn(Function):
         ctrl, pts, *w = ctx.saved_tensors
         g_ctrl = ops.dyn_voxel_spline_len_backward(pts, ctrl, ctx.spline, ctx.grid_radius, g.contiguous(), w[0] if w else None)
         return g_ctrl, None, None, None, None
+
+
+class DynVoxelJacQuadFn(Function):
+    """v . (J_dp v) per sample (ops.dyn_voxel_jac_quad without a rigidity grid: one launch), J_dp the Jacobian of DynamicNeRFVoxel's dp
+    w.r.t. the unwarped position; differentiable w.r.t. ctrl_pts_grid, in which it is linear: backward is one scatter-add
+    (ops.dyn_voxel_jac_quad_backward) that needs neither the grid nor the forward's output.  pts, t and v carry no gradient.  The
+    dp * rigidity form has no graph in the reference (src/utils.py:471-477) and is evaluated by the operator directly."""
+
+    @staticmethod
+    def forward(ctx, ctrl_pts_grid, pts, t, v, spline, grid_radius):
+        ctx.save_for_backward(pts, t, *(() if v is None else (v,)))
+        ctx.S, ctx.spline, ctx.grid_radius = ctrl_pts_grid.shape[0], spline, grid_radius
+        return ops.dyn_voxel_jac_quad(pts, t, ctrl_pts_grid, None, spline, grid_radius, v)
+
+    @staticmethod
+    def backward(ctx, g):
+        pts, t, *v = ctx.saved_tensors
+        g_ctrl = ops.dyn_voxel_jac_quad_backward(pts, t, ctx.S, ctx.spline, ctx.grid_radius, g.contiguous(), v[0] if v else None)
+        return g_ctrl, None, None, None, None, None

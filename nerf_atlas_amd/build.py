@@ -42,6 +42,7 @@ UNITS = [
     ("dyn_voxel.hip", [], ""),
     ("dyn_voxel_render.hip", [], ""),
     ("spline_len.hip", [], ""),
+    ("dyn_voxel_div.hip", [], ""),
     ("grid_ops.hip", [], ""),
     ("optim.hip", [], ""),
     ("backward.hip", [], ""),

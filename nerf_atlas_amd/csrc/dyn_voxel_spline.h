@@ -37,4 +37,25 @@ __device__ __forceinline__ void dv_spline(const float* cp, float t, float dp[3])
   for (int a = 0; a < 3; ++a) dp[a] = b[0][a];
 }
 
+// d dp / d control point k, k = 0 .. NC-1: the cubic form's own coefficients, else the Bernstein polynomials by the de Casteljau
+// recurrence on the weights (every step a convex combination for t in [0, 1])
+template <int NC>
+__device__ __forceinline__ void dv_bernstein(float t, float B[NC]) {
+  const float m1t = 1.f - t;
+  if (NC == 4) {
+    const float m1t_sq = m1t * m1t, t_sq = t * t;
+    B[0] = m1t_sq * m1t; B[1] = (3.f * m1t_sq) * t; B[2] = (3.f * t_sq) * m1t; B[3] = t_sq * t;
+    return;
+  }
+  B[0] = 1.f;
+#pragma unroll
+  for (int k = 1; k < NC; ++k) B[k] = 0.f;
+#pragma unroll
+  for (int i = 1; i < NC; ++i) {
+#pragma unroll
+    for (int j = i; j >= 1; --j) B[j] = B[j] * m1t + B[j - 1] * t;
+    B[0] = B[0] * m1t;
+  }
+}
+
 }  // namespace na

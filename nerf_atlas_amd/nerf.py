@@ -1023,8 +1023,8 @@ class DynamicNeRFVoxel(nn.Module):
       eval, no gradients  ops.dyn_voxel_warp, then the canonical's one-launch render at the warped points (ops.voxel_render /
                           ops.voxel_plv_render by the head)
       otherwise           autograd.DynVoxelWarpFn, then the canonical's operator route, whose lookup returns the position gradient
-    The reference marks `pts` as requiring a gradient in training for regularisers that are not built here; pts stays a
-    plain tensor and no gradient is formed for it."""
+    The reference marks `pts` as requiring a gradient in training for its two divergence regularisers; here pts stays a plain tensor and
+    the Jacobian's quadratic forms come from a kernel of their own (`ffjord_div`, `sum_jacobian_div`: csrc/dyn_voxel_div.hip)."""
 
     def __init__(self, canonical=None, spline: int = 4):
         if not isinstance(canonical, NeRFVoxel):
@@ -1066,7 +1066,7 @@ class DynamicNeRFVoxel(nn.Module):
                              f"{self.rigidity_grid.shape[0]}^3 (the deformation grids have no resampling)")
         self.pts, self.ts, r_o, r_d, _ = compute_pts_ts(rays, c.t_near, c.t_far, c.steps, perturb=1 if self.training else 0)
         c.ts = self.ts
-        tt = t[None, :, None, None].expand(*self.pts.shape[:-1]).contiguous()
+        tt = self._tt = t[None, :, None, None].expand(*self.pts.shape[:-1]).contiguous()
         if ag.needs_grad(self.ctrl_pts_grid, self.rigidity_grid):
             warped, self.dp, rigidity = ag.DynVoxelWarpFn.apply(self.ctrl_pts_grid, self.rigidity_grid, self.pts, tt, self.spline,
                                                                  c.grid_radius)
@@ -1115,6 +1115,33 @@ class DynamicNeRFVoxel(nn.Module):
     def rigid_dp(self):
         """dp * rigidity (src/nerf.py:1585), formed on demand like DynamicNeRF's"""
         return self.dp * self.rigidity
+
+    def _last_samples(self, who):
+        if getattr(self, "pts", None) is None or getattr(self, "_tt", None) is None:
+            raise RuntimeError(f"DynamicNeRFVoxel.{who} reads the sample positions and times of the last forward: render first")
+        return self.pts, self._tt
+
+    def ffjord_div(self, e):
+        """utils.div_approx(model.pts, model.rigid_dp) of runner.py:698-699 (src/utils.py:467-478) at the samples of the last forward:
+        <e, d(rigid_dp)/d(pts) . e> per sample [T,B,H,W], e [T,B,H,W,3] the caller's randn draw -- DynamicNeRF.ffjord_div's name, shape
+        and meaning.  The Jacobian of the grid lookup is formed in closed form by one launch (ops.dyn_voxel_jac_quad, DESIGN.md 3q);
+        like the reference's, the estimate has no graph."""
+        pts, tt = self._last_samples("ffjord_div")
+        with torch.no_grad():
+            return ops.dyn_voxel_jac_quad(pts, tt, self.ctrl_pts_grid.data, self.rigidity_grid.data, self.spline,
+                                          self.canonical.grid_radius, e.detach().reshape(pts.shape))
+
+    def sum_jacobian_div(self):
+        """`utils.divergence(model.pts, model.dp)` of runner.py:694-696 at the samples of the last forward, with its graph: the sum of
+        all nine entries of d dp / d pts (DynamicNeRF.sum_jacobian_div's docstring says why it is not the trace), [T,B,H,W,1].  One
+        launch, linear in ctrl_pts_grid, which is the only parameter its gradient reaches (autograd.DynVoxelJacQuadFn)."""
+        pts, tt = self._last_samples("sum_jacobian_div")
+        c = self.canonical
+        if ag.needs_grad(self.ctrl_pts_grid):
+            div = ag.DynVoxelJacQuadFn.apply(self.ctrl_pts_grid, pts, tt, None, self.spline, c.grid_radius)
+        else:
+            div = ops.dyn_voxel_jac_quad(pts, tt, self.ctrl_pts_grid.data, None, self.spline, c.grid_radius)
+        return div.unsqueeze(-1)
 
     def spline_len(self, weights=None):
         """runner.py:784-787: the mean over the samples of the last forward of weights * arc_len(the sample's spline), the n control

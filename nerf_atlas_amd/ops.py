@@ -1919,6 +1919,54 @@ def dyn_voxel_warp_backward(pts: torch.Tensor, t: torch.Tensor, dp: torch.Tensor
     return g_ctrl, g_rig
 
 
+def _dyn_voxel_direction(v: Optional[torch.Tensor], pts: torch.Tensor):
+    if v is not None:
+        v = _f32(v, "v")
+        if v.shape != pts.shape:
+            raise ValueError(f"v must be {tuple(pts.shape)} (one direction per sample) or None for ones, got {tuple(v.shape)}")
+    return v
+
+
+def dyn_voxel_jac_quad(pts: torch.Tensor, t: torch.Tensor, ctrl_pts_grid: torch.Tensor, rigidity_grid: Optional[torch.Tensor], spline: int,
+                       grid_radius: float, v: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """v . (J v) per sample [...] of pts [..., 3] at times t [...] as ONE launch (csrc/dyn_voxel_div.hip), J the Jacobian w.r.t. the
+    unwarped position of dyn_voxel_warp's dp (rigidity_grid None: utils.divergence with v = None, i.e. ones) or of dp * rigidity
+    (rigidity_grid given: utils.div_approx with v the normal draw).  Nothing per sample but the result is written."""
+    lib = _lib.load()
+    if rigidity_grid is None:
+        _dyn_voxel_spline(spline)
+        ctrl, rig = _f32(ctrl_pts_grid, "ctrl_pts_grid"), None
+        S = ctrl.shape[0]
+        if ctrl.dim() != 4 or tuple(ctrl.shape) != (S, S, S, 3 * (spline - 1)):
+            raise ValueError(f"ctrl_pts_grid must be [S,S,S,{3 * (spline - 1)}], got {tuple(ctrl.shape)}")
+        _dyn_voxel_reso(S)
+    else:
+        ctrl, rig, S = _dyn_voxel_grids(ctrl_pts_grid, rigidity_grid, spline)
+    pts, t, N = _dyn_voxel_samples(pts, t)
+    v = _dyn_voxel_direction(v, pts)
+    out = torch.empty(pts.shape[:-1], device=pts.device, dtype=torch.float32)
+    check(lib.na_dyn_voxel_jac_quad(_ptr(pts), _ptr(t), N, _ptr(ctrl), _ptr(rig), S, spline, float(grid_radius), _ptr(v), _ptr(out), _stream()))
+    return out
+
+
+def dyn_voxel_jac_quad_backward(pts: torch.Tensor, t: torch.Tensor, S: int, spline: int, grid_radius: float, g: torch.Tensor,
+                                v: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """g_ctrl_pts_grid [S,S,S,3(spline-1)] of dyn_voxel_jac_quad's dp form given g [...] (one value per sample): one scatter-add launch.
+    The dp * rigidity form has no gradient (the reference's estimate has no graph); pts, t and v get none."""
+    lib = _lib.load()
+    _dyn_voxel_spline(spline)
+    _dyn_voxel_reso(S)
+    pts, t, N = _dyn_voxel_samples(pts, t)
+    v = _dyn_voxel_direction(v, pts)
+    g = _f32(g, "g")
+    if g.numel() != N:
+        raise ValueError(f"g has {g.numel()} elements, one per sample ({N}) expected")
+    config.require_deterministic_workspace(8 * S ** 3 * 3 * (spline - 1))
+    out = torch.zeros(S, S, S, 3 * (spline - 1), device=pts.device, dtype=torch.float32)
+    check(lib.na_dyn_voxel_jac_quad_backward(_ptr(pts), _ptr(t), N, S, spline, float(grid_radius), _ptr(v), _ptr(g), _ptr(out), _stream()))
+    return out
+
+
 DYN_VOXEL_MAPS = ("depth", "acc", "flow", "rigidity", "alpha", "weights")
 
 

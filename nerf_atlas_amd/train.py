@@ -423,12 +423,14 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
     if args.epochs == 0:
         return []
     dyn_voxel = isinstance(model, nerf.DynamicNeRFVoxel)
-    if dyn_voxel:
-        # both terms differentiate rigid_dp / dp w.r.t. the sample positions (runner.py:694-699), which the deformation's node does not form
+    if dyn_voxel and not model.ctrl_pts_grid.is_cuda:
+        # both terms contract d(rigid_dp)/d(pts) / d(dp)/d(pts) of the grid lookup (runner.py:694-699), which only csrc/dyn_voxel_div.hip
+        # forms (NeRFVoxel.upsample's rule: no CPU implementation); raised before cam / labels are touched
         for flag in ("ffjord_div_decay", "dyn_diverge_decay"):
             if getattr(args, flag, 0):
-                raise NotImplementedError(f"--{flag.replace('_', '-')} over --dyn-model voxel needs d(dp)/d(pts) of the grid lookup, "
-                                          "which is not built (DESIGN.md 8)")
+                raise NotImplementedError(f"--{flag.replace('_', '-')} over --dyn-model voxel runs on the GPU only: d(dp)/d(pts) of the "
+                                          "grid lookup is a HIP kernel (DESIGN.md 3q) and the model's grids are on "
+                                          f"{model.ctrl_pts_grid.device}")
     if getattr(args, "dyn_diverge_decay", 0) > 0 and not hasattr(model, "sum_jacobian_div"):
         raise ValueError("--dyn-diverge-decay needs a dynamic model (--data-kind dnerf --dyn-model plain --spline N): the "
                          "reference reads model.pts / model.dp (runner.py:694-696)")
@@ -489,6 +491,8 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
     tv_terms = train.last_tv_terms = []
     # ([--spline-len-decay term, --voxel-random-spline-len-decay term] per iteration, NaN where a term is off; device scalars)
     len_terms = train.last_len_terms = []
+    # (mean(alpha * div_approx^2) of --ffjord-div-decay per iteration, NaN where the flag is off; device scalars)
+    ffjord_terms = train.last_ffjord_terms = []
     model.train()
     opt.zero_grad()
     for i in range(args.epochs):
@@ -542,7 +546,11 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
             e = utils.randn(tuple(model.pts.shape), device)
             exp_ratio = (1 / 100) ** (1 - i / args.epochs)
             div = model.ffjord_div(e).abs().square()
-            loss = loss + exp_ratio * args.ffjord_div_decay * (model.canonical.alpha.detach() * div).mean()
+            ffjord_term = (model.canonical.alpha.detach() * div).mean()
+            ffjord_terms.append(ffjord_term.detach())
+            loss = loss + exp_ratio * args.ffjord_div_decay * ffjord_term
+        else:
+            ffjord_terms.append(float("nan"))
         if args.smooth_normals > 0:
             # runner.py:711-727, the epsilon-perturbation form "from unisurf": normals at the points and at points a random
             # direction of length eps away should agree.  Draw order of the reference: random.random() (with
@@ -678,5 +686,6 @@ def fit(args, device="cuda", replay_reference_rng=False, init=None, on_iter=None
     psnrs, gots = test(model, test_cam, test_labels, args)
     return dict(model=model, losses=losses, reg_terms=list(getattr(train, "last_reg_terms", [])),
                 tv_terms=[[float(v) for v in row] for row in getattr(train, "last_tv_terms", [])],
+                ffjord_terms=[float(v) for v in getattr(train, "last_ffjord_terms", [])],
                 len_terms=[[float(v) for v in row] for row in getattr(train, "last_len_terms", [])], test_psnr=psnrs, test_psnr_mean=float(np.mean(psnrs)), frames=gots,
                 maps=list(getattr(test, "last_maps", [])), test_labels=test_labels, test_cam=test_cam, rank=rank, world=world)

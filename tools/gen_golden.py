@@ -1272,9 +1272,96 @@ def g28():
     g25("g28_dyn_voxel_plv_", rrefl.PosLinearView, DYN_VOXEL_PLV_CASES)
 
 
+DYN_VOXEL_DIV_CASES = {  # name: (S, spline, T, ray batch shape [B, H, W], times [B])
+    "s2_n2": (2, 2, 6, (1, 3, 3), (0.7,)),
+    "s4_n4": (4, 4, 6, (2, 2, 3), (0.35, 1.0)),
+    "s4_n5": (4, 5, 6, (1, 3, 3), (0.6,)),
+    "s16_n11_ragged": (16, 11, 7, (1, 3, 5), (0.45,)),   # 105 samples
+}
+
+
+def g29():
+    """g29_dyn_voxel_div_<case>: the reference's two divergence regularisers over its DynamicNeRFVoxel (runner.py:694-700:
+    utils.div_approx(model.pts, model.rigid_dp) and utils.divergence(model.pts, model.dp)), TRAINING mode (perturbed samples,
+    pts.requires_grad_()), evaluated in fp64.  Data only.
+      positions   the fp32 training-mode forward under the carried torch seed gives `pts` (fp32); the fp64 model is then run AT those
+                  positions (compute_pts_ts wrapped to hand back their double images), so every input of the fp64 run is an fp32 number.
+      membership  g24 / g28's convention, made strict: every coordinate of every sample is at least 1e-3 voxel lengths from a plane on which
+                  the cell pair changes (asserted; the next seed is taken otherwise), and the ids of the fp64 run equal those of the
+                  fp32 chain (tests/voxel_ref.cells) -- no sample ever has to be excluded from a comparison.
+      coverage    at least a third of the samples inside the grid and a third outside (asserted).
+      e           captured as g17 captures it (the seed replayed); the draw is made in fp32 and widened (randn_like wrapped for the
+                  call), so the kernels can be fed the very same numbers.
+      contents    pts, t (one per sample), both grids (procedural values, stored), e, div_approx, divergence,
+                  g_ctrl = d(mean divergence)/d ctrl_pts_grid, and the reference's own fp32 - fp64 deviations `dev`."""
+    import copy
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import voxel_ref as V
+    import dyn_voxel_div_ref as R
+    for name, (S, spline, T, shape, times) in DYN_VOXEL_DIV_CASES.items():
+        canon, _, _ = _voxel_build(S, T, "upshifted", "black")
+        m = rnerf.DynamicNeRFVoxel(canon, spline=spline)
+        fill_procedural(m)
+        m.train()
+        canon.train()
+        m64 = copy.deepcopy(m).double()
+        t = torch.tensor(times, dtype=torch.float32)
+        gr = canon.grid_radius
+        for seed in range(4500, 4700, 2):
+            rays = V.generic_rays(shape, seed)
+            torch.manual_seed(seed)
+            with torch.enable_grad():
+                m((rays, t))
+            pts = m.pts.detach().clone()
+            flat = pts.reshape(-1, 3)
+            inside = (flat.abs() <= gr).all(dim=-1).float().mean()
+            if float(R.face_distance(flat, S, gr).min()) >= 1e-3 and 1 / 3 <= float(inside) <= 2 / 3:
+                break
+        else:
+            raise AssertionError(f"g29 {name}: no seed keeps every sample 1e-3 voxel lengths off the cell faces with a third inside / outside")
+        orig_pts, orig_randn = rnerf.compute_pts_ts, torch.randn_like
+
+        def run(model, dt):
+            def at_pts(*a, **k):
+                _, ts, r_o, r_d, mids = orig_pts(*a, **k)
+                return pts.to(dt), ts, r_o, r_d, mids
+            rnerf.compute_pts_ts = at_pts
+            torch.randn_like = lambda x, **k: orig_randn(x.float(), **k).to(x.dtype)
+            try:
+                with torch.enable_grad():
+                    model.ctrl_pts_grid.requires_grad_(True)
+                    model.ctrl_pts_grid.grad = None
+                    torch.manual_seed(seed)
+                    model((rays.to(dt), t.to(dt)))
+                    assert torch.equal(model.pts.detach(), pts.to(dt)) and model.pts.requires_grad
+                    torch.manual_seed(seed + 1)
+                    div_approx = rutils.div_approx(model.pts, model.rigid_dp)
+                    torch.manual_seed(seed + 1)
+                    e = torch.randn_like(model.rigid_dp)
+                    divergence = rutils.divergence(model.pts, model.dp)
+                    divergence.mean().backward()
+                    ids, _ = model.canonical.grid_coords_trilin_weights(model.pts)
+            finally:
+                rnerf.compute_pts_ts, torch.randn_like = orig_pts, orig_randn
+            assert not div_approx.requires_grad and divergence.requires_grad
+            return dict(e=e.detach(), div_approx=div_approx.detach(), divergence=divergence.detach(), dp=model.dp.detach(),
+                        g_ctrl=model.ctrl_pts_grid.grad.clone(), ids=ids)
+        r32, r64 = run(m, torch.float32), run(m64, torch.float64)
+        assert r64["div_approx"].dtype == torch.float64 and torch.equal(r32["e"].double(), r64["e"]) and float(r64["g_ctrl"].abs().max()) > 0
+        assert torch.equal(r64["ids"].reshape(-1, 8, 3), V.cells(flat, S, gr)[0]), "the fp64 run and the fp32 chain read different cells"
+        dev = {k: float((r32[k].double() - r64[k]).abs().max()) for k in ("div_approx", "divergence", "g_ctrl", "dp")}
+        tt = t[None, :, None, None].expand(pts.shape[:-1]).contiguous()
+        print(f"g29 {name}: seed {seed}, {flat.shape[0]} samples, {float(inside):.0%} inside, nearest face {float(R.face_distance(flat, S, gr).min()):.2e} vl; "
+              f"|div_approx| up to {float(r64['div_approx'].abs().max()):.3g}, |divergence| up to {float(r64['divergence'].abs().max()):.3g}; "
+              "fp32 vs fp64: " + " ".join(f"{k} {v:.2e}" for k, v in dev.items()))
+        save(f"g29_dyn_voxel_div_{name}", pts=pts, t=tt, S=S, spline=spline, grid_radius=gr, seed=seed, rays=rays, times=t,
+             ctrl_pts_grid=m.ctrl_pts_grid.detach(), rigidity_grid=m.rigidity_grid.detach(), e=r32["e"], div_approx=r64["div_approx"],
+             divergence=r64["divergence"], g_ctrl=r64["g_ctrl"], dev=np.array([dev[k] for k in ("div_approx", "divergence", "g_ctrl", "dp")]))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25", "g26", "g27", "g28"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25", "g26", "g27", "g28", "g29"]
     for g in which:
         globals()[g]()
     with open(os.path.join(OUT, "PROVENANCE.txt"), "w") as f:

@@ -35,6 +35,12 @@ from tools.make_scene import make_scene  # noqa: E402
 
 REF = "/root/reference"
 
+DYN_VOXEL_MAKE = ["--data-kind", "dnerf", "--near", "2", "--far", "6", "--model", "voxel", "--dyn-model", "voxel", "-lr", "1e-2", "--loss-fns", "l2",
+                  "--spline", "4", "--voxel-tv-sigma", "1e-3", "--voxel-tv-rgb", "1e-4", "--voxel-tv-bezier", "1e-4", "--voxel-tv-rigidity", "1e-4",
+                  "--higher-end-chance", "1", "--offset-decay", "30"]
+DYN_VOXEL_MAKE_TAIL = ["--sigmoid-kind", "upshifted", "--voxel-random-spline-len-decay", "1e-5", "--refl-kind", "pos-linear-view"]
+DYN_VOXEL_DIV_WEIGHT = os.environ.get("NA_DYN_VOXEL_DIV_WEIGHT", "0.1")   # (the committed fixture records the weight used in its argv)
+
 RECIPES = {
     # name: (dynamic scene?, reference argv after the data flags)
     "plain": (False, ["--model", "plain", "--refl-kind", "view"]),
@@ -85,6 +91,19 @@ RECIPES = {
     "dyn_voxel_plv": (True, ["--model", "voxel", "--refl-kind", "pos-linear-view", "--loss-fns", "l2", "-lr", "5e-2", "--data-kind", "dnerf",
                              "--dyn-model", "voxel", "--spline", "4", "--voxel-tv-bezier", "0.02", "--voxel-tv-rigidity", "0.02",
                              "--offset-decay", "1"]),
+    # `make dyn_voxel` AS SHIPPED (reference makefile:36-45), --ffjord-div-decay 0.3 included: every flag of its command line that bears
+    # on training, in its order, with its values (the rate too: 1e-2).  Left out are the flags of the run's surroundings (-d, --size,
+    # --epochs, --crop-size, --batch-size, --steps, --test-crop-size, --seed: this tool's; --save / --load / --save-freq / --loss-window /
+    # --replace: checkpoints; --depth-images / --flow-map / --rigidity-map: panels of the test frames).  The reference adds 0 x the
+    # --voxel-random-spline-len-decay term but draws its indices.  Recorded with the voxel fixtures' sizes and --epochs 60;
+    # the fixture carries mean(alpha * div_approx^2) of every iteration (`ffjord_terms`) and, for the first five, the same number from an
+    # fp64 copy of the model at the same positions with the same draw (`ffjord_terms64`)
+    "dyn_voxel_make": (True, DYN_VOXEL_MAKE + ["--ffjord-div-decay", "0.3"] + DYN_VOXEL_MAKE_TAIL),
+    # the same recipe with --dyn-diverge-decay in --ffjord-div-decay's place (`reg_terms`: the term of every iteration; `reg_terms64`: the
+    # fp64 copy's, first five), and the loss curve of the recipe with neither flag (`losses_without_flag`, recorded with --out and folded in
+    # with --base).  The weight is the smallest of 0.1, 1, 10, ... at which the last 10 losses of the two curves differ by more than 2e-3
+    "dyn_voxel_div": (True, DYN_VOXEL_MAKE + ["--dyn-diverge-decay", DYN_VOXEL_DIV_WEIGHT] + DYN_VOXEL_MAKE_TAIL),
+    "dyn_voxel_nodiv": (True, DYN_VOXEL_MAKE + DYN_VOXEL_MAKE_TAIL),   # (never committed: --out, then --base)
     "dnerf": (True, ["--model", "plain", "--refl-kind", "view", "--data-kind", "dnerf", "--dyn-model", "plain",
                      "--spline", "4"]),
     # `make dnerf`'s regularisers (reference makefile:106-114) on the small scene: NR-NeRF offset decay + the FFJORD
@@ -168,6 +187,8 @@ def main():
     a.add_argument("--threads", type=int, default=8)
     a.add_argument("--out", default=None, help="write the fixture here instead of tests/golden/train_parity_<name>.json "
                    "(sensitivity runs: the same recipe under another thread count = another summation order)")
+    a.add_argument("--base", default=None, metavar="JSON", help="dyn_voxel_div: the dyn_voxel_nodiv run (made with --out JSON) whose losses are "
+                   "recorded as `losses_without_flag`")
     a.add_argument("--add-run", default=None, metavar="JSON", help="no training: record another run of the same recipe (made with --threads N "
                    "--out JSON) in the committed fixture as `other_runs` -- the reference's own spread under another summation order")
     cfg = a.parse_args()
@@ -211,6 +232,63 @@ def main():
         captured.setdefault("reg_terms", []).append(float(v.mean().detach()))
         return v
     rutils.divergence = divergence
+    real_div_approx = rutils.div_approx
+    is_dyn_voxel_div = cfg.name in ("dyn_voxel_make", "dyn_voxel_div")
+
+    def term64(kind, e=None):
+        """the regulariser's term from an fp64 copy of the model run at the fp32 run's positions (and with its draw): the reference's own
+        arithmetic in double at the same state.  The global random stream is left where it was."""
+        m, m64, (rays, t) = captured["model"], captured["model64"], captured["rays_t"]
+        state = torch.get_rng_state()
+        m64.load_state_dict({k: v.detach().double() for k, v in m.state_dict().items()})
+        m64.train(m.training)
+        for k in ("steps", "t_near", "t_far"):  # (runner.set_per_run writes them after load_model)
+            setattr(m64.canonical, k, getattr(m.canonical, k))
+        pts = m.pts.detach().double()
+        orig_pts, orig_randn = rnerf.compute_pts_ts, torch.randn_like
+
+        def at_pts(*a_, **k_):  # (the fp32 run's perturbed steps too: alpha depends on them)
+            _, _, r_o, r_d, mids = orig_pts(*a_, **k_)
+            return pts.clone(), m.ts.detach().double(), r_o, r_d, mids
+        rnerf.compute_pts_ts = at_pts
+        try:
+            with torch.enable_grad():
+                m64((rays.double(), t.double()))
+                if kind == "ffjord":
+                    torch.randn_like = lambda x, **k_: e.double()
+                    v = real_div_approx(m64.pts, m64.rigid_dp)
+                    out = float((m64.canonical.alpha.detach() * v.abs().square()).mean())
+                else:
+                    out = float(real_div(m64.pts, m64.dp).mean())
+        finally:
+            rnerf.compute_pts_ts, torch.randn_like = orig_pts, orig_randn
+            torch.set_rng_state(state)
+        return out
+
+    def div_approx(x, fn_x):  # (mean(alpha * div_approx^2) per iteration: what --ffjord-div-decay weights)
+        state = torch.get_rng_state()
+        v = real_div_approx(x, fn_x)
+        if is_dyn_voxel_div:
+            after = torch.get_rng_state()
+            torch.set_rng_state(state)
+            e = torch.randn_like(fn_x)
+            assert torch.equal(torch.get_rng_state(), after)
+            m = captured["model"]
+            terms = captured.setdefault("ffjord_terms", [])
+            terms.append(float((m.canonical.alpha.detach() * v.detach().abs().square()).mean()))
+            if len(terms) <= 5:
+                captured.setdefault("ffjord_terms64", []).append(term64("ffjord", e))
+        return v
+    rutils.div_approx = div_approx
+    if is_dyn_voxel_div:
+        def divergence(x, field):
+            v = real_div(x, field)
+            terms = captured.setdefault("reg_terms", [])
+            terms.append(float(v.mean().detach()))
+            if len(terms) <= 5:
+                captured.setdefault("reg_terms64", []).append(term64("divergence"))
+            return v
+        rutils.divergence = divergence
     real_tv = rnerf.total_variation
 
     def total_variation(grid, samples=32 ** 3):  # (the two --voxel-tv-* terms per iteration, densities then rgb)
@@ -236,6 +314,11 @@ def main():
             import src.refl as rrefl
             m.set_refl(rrefl.load(args, args.refl_kind, args.space_kind, args.encoding_size + m.intermediate_size))
         fill_procedural(m)
+        if is_dyn_voxel_div:  # (term64 replays the iteration's forward)
+            import copy
+            captured["model"], captured["model64"] = m, copy.deepcopy(m).double()
+            forward = m.forward
+            m.forward = lambda rays_t: (captured.__setitem__("rays_t", rays_t), forward(rays_t))[1]
         torch.manual_seed(cfg.seed + 1)
         return m
     runner.load_model = load_model
@@ -266,6 +349,22 @@ def main():
         test_psnr=psnrs, test_psnr_mean=mean, reg_terms=captured.get("reg_terms", []),
         torch=torch.__version__, threads=cfg.threads, wall_s=round(dt, 1),
     )
+    if cfg.name in ("dyn_voxel_make", "dyn_voxel_div", "dyn_voxel_nodiv"):
+        tv = captured["tv_terms"]
+        fixture["tv_terms"] = [tv[i:i + 4] for i in range(0, len(tv), 4)]  # (densities, rgb, ctrl_pts_grid, rigidity_grid) per iteration
+        for k in ("ffjord_terms", "ffjord_terms64", "reg_terms64"):
+            if k in captured:
+                fixture[k] = captured[k]
+    if cfg.name == "dyn_voxel_div":
+        base = json.load(open(cfg.base))
+        drop = lambda av: [x for i, x in enumerate(av) if not (x == "--dyn-diverge-decay" or (i and av[i - 1] == "--dyn-diverge-decay"))]
+        assert drop(fixture["argv"]) == base["argv"] and base["seed"] == cfg.seed, "record dyn_voxel_nodiv with the same flags"
+        fixture["losses_without_flag"] = base["losses"]
+        fixture["diverge_weight"] = float(DYN_VOXEL_DIV_WEIGHT)
+        sep = float(np.abs(np.array(fixture["losses"][-10:]) - np.array(base["losses"][-10:])).max())
+        fixture["separation_last10"] = sep
+        print(f"dyn_voxel_div: weight {DYN_VOXEL_DIV_WEIGHT}: the curves with and without the term differ by {sep:.2e} in the last 10 losses")
+        assert sep > 10 * 2e-4, "raise the weight (NA_DYN_VOXEL_DIV_WEIGHT) until the two reference curves separate"
     if cfg.name in ("dyn_voxel", "dyn_voxel_plv"):
         tv = captured["tv_terms"]
         fixture["tv_terms"] = [tv[i:i + 2] for i in range(0, len(tv), 2)]  # (ctrl_pts_grid, rigidity_grid) per iteration
