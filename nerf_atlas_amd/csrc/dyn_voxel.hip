@@ -6,9 +6,9 @@
 //   rigidity = sigmoid(interpolated rigidity_grid)                 (the plain sigmoid, not na_bezier_warp's x / 2 form)
 //   warped   = pts + dp * rigidity
 // Two operators: the deformation as one launch (na_dyn_voxel_warp: a gather of 8 rows of 1 + 3(n-1) floats, the spline) and its
-// backward (na_dyn_voxel_warp_backward: a scatter-add into the two grids on voxel_backward_kernel's scheme).  There is no gradient
+// backward (na_dyn_voxel_warp_backward: a scatter-add into the two grids on voxel_scatter.h's scheme).  There is no gradient
 // w.r.t. pts: they are a leaf in the reference.  Kernels are instantiated per n = 2 .. 11 so that the control points stay in registers.
-#include "dyn_voxel_scatter.h"
+#include "voxel_scatter.h"
 #include "dyn_voxel_spline.h"
 
 namespace na {
@@ -24,19 +24,8 @@ __global__ __launch_bounds__(256) void dyn_voxel_warp_kernel(const float* __rest
   for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
     const float px = pts[n * 3], py = pts[n * 3 + 1], pz = pts[n * 3 + 2];
     const VoxCell c = vox_cell(px, py, pz, g);
-    float cp[CH], rl = 0.f;
-#pragma unroll
-    for (int ch = 0; ch < CH; ++ch) cp[ch] = 0.f;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int64_t row = vox_row(c, u, g.S);
-      const float w = vox_weight(c, u);
-      const float* q = ctrl + row * CH;
-#pragma unroll
-      for (int ch = 0; ch < CH; ++ch) cp[ch] = cp[ch] + w * q[ch];
-      rl = rl + w * rig[row];
-    }
-    float dp[3];
+    float cp[CH], rl, dp[3];
+    dv_gather<NC, true, false, true>(c, g, ctrl, rig, nullptr, cp, &rl, nullptr, nullptr);
     dv_spline<NC>(cp, t[n], dp);
     const float r = sigmoidf_(rl);
     warped[n * 3] = px + dp[0] * r; warped[n * 3 + 1] = py + dp[1] * r; warped[n * 3 + 2] = pz + dp[2] * r;
@@ -48,10 +37,10 @@ __global__ __launch_bounds__(256) void dyn_voxel_warp_kernel(const float* __rest
 // ------------------------------------------------------------------------------------ scatter-add into the two grids
 // With r the rigidity, G = g_warped, D = G r + g_dp and q = (G . dp + g_rigidity) r (1 - r), corner u of a sample adds
 //   w_u B_k(t) D  to channels 3(k-1) .. 3k-1 of ctrl row_u  (k = 1 .. n-1)      and      w_u q  to rigidity row_u:
-// one "wide row" of W = 1 + 3(n-1) sums per grid row, [rigidity | control channels], summed by the scheme of dyn_voxel_scatter.h (a
+// one "wide row" of W = 1 + 3(n-1) sums per grid row, [rigidity | control channels], summed by the scheme of voxel_scatter.h (a
 // contiguous run of samples per workgroup, a hashed LDS table, one flush).  dp and rigidity are the forward's outputs (16 bytes per
 // sample instead of gathering the 8 rows again).  Deterministic mode: every contribution to 2^-40 fixed point on its own, as
-// voxel_backward_kernel.
+// every scatter on that table.
 template <int NC>
 __global__ __launch_bounds__(256) void dyn_voxel_warp_backward_kernel(const float* __restrict__ pts, const float* __restrict__ t, int64_t N,
                                                                       VoxGrid g, const float* __restrict__ dp, const float* __restrict__ rigidity,
@@ -96,9 +85,7 @@ __global__ __launch_bounds__(256) void dyn_voxel_warp_backward_kernel(const floa
     for (int u = 0; u < 8; ++u) table.add_row((uint32_t)vox_row(c, u, g.S), vox_weight(c, u), sv, add_global);
   }
   table.flush([&](uint32_t id, int e, unsigned long long v) {
-    const int64_t at = e == 0 ? (int64_t)id : (int64_t)id * CH + (e - 1);
-    if (fix == nullptr) atomicAdd((e == 0 ? g_rig : g_ctrl) + at, __uint_as_float((uint32_t)v));
-    else atomicAdd((unsigned long long*)((e == 0 ? fix_rig : fix) + at), v);
+    table.put(e == 0 ? g_rig : g_ctrl, e == 0 ? fix_rig : fix, e == 0 ? (int64_t)id : (int64_t)id * CH + (e - 1), v);
   });
 }
 

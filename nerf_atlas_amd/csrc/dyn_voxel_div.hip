@@ -12,23 +12,16 @@
 //                                   eight rows are read once and the tangent control points sum_u (v . grad w_u) c_{u,k} (and, for
 //                                   J_rigid, the control points themselves) stay in registers.
 //   na_dyn_voxel_jac_quad_backward  the J_dp form's gradient w.r.t. ctrl_pts_grid: row u, block k, axis a gets
-//                                   g[n] (v . grad w_u) B_k(t) v_a, summed by dyn_voxel_scatter.h's table.  The J_rigid form has no
+//                                   g[n] (v . grad w_u) B_k(t) v_a, summed by voxel_scatter.h's table.  The J_rigid form has no
 //                                   graph in the reference and gets no backward.  There is no gradient w.r.t. pts, t or v.
 // ORDER OF THE OPERATIONS (tests/dyn_voxel_div_ref.py derives its bound from it; the unit is built with -ffp-contract=off):
-//   d_u = ((v_x gx_u + v_y gy_u) + v_z gz_u) / vl with gx_u = +-(wy wz), gy_u = +-(wx wz), gz_u = +-(wx wy); sums over the corners in
-//   corner order, acc <- acc + d_u q; dv_spline; out = (v_x j_x + v_y j_y) + v_z j_z.
-#include "dyn_voxel_scatter.h"
+//   d_u = ((v_x gx_u + v_y gy_u) + v_z gz_u) / vl with gx_u = +-(wy wz), gy_u = +-(wx wz), gz_u = +-(wx wy) (dv_tangent over
+//   vox_dweight); sums over the corners in corner order, acc <- acc + d_u q (dv_gather's tangent sums, dyn_voxel_spline.h); dv_spline;
+//   out = (v_x j_x + v_y j_y) + v_z j_z.
+#include "voxel_scatter.h"
 #include "dyn_voxel_spline.h"
 
 namespace na {
-
-// v . grad w_u of corner u
-__device__ __forceinline__ float jq_dweight(const VoxCell& c, int u, const float v[3], float vl) {
-  const float wx = (u & 1) ? c.x : 1.f - c.x, wy = (u & 2) ? c.y : 1.f - c.y, wz = (u & 4) ? c.z : 1.f - c.z;
-  const float yz = wy * wz, xz = wx * wz, xy = wx * wy;
-  const float gx = (u & 1) ? yz : -yz, gy = (u & 2) ? xz : -xz, gz = (u & 4) ? xy : -xy;
-  return ((v[0] * gx + v[1] * gy) + v[2] * gz) / vl;
-}
 
 __device__ __forceinline__ void jq_direction(const float* __restrict__ v, int64_t n, float e[3]) {
   e[0] = e[1] = e[2] = 1.f;
@@ -46,31 +39,7 @@ __global__ __launch_bounds__(256) void dyn_voxel_jac_quad_kernel(const float* __
     float e[3];
     jq_direction(v, n, e);
     float tcp[CH], cp[RIGID ? CH : 1], rl = 0.f, trl = 0.f;
-#pragma unroll
-    for (int ch = 0; ch < CH; ++ch) {
-      tcp[ch] = 0.f;
-      if (RIGID) cp[ch] = 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int64_t row = vox_row(c, u, g.S);
-      const float d = jq_dweight(c, u, e, g.vl);
-      const float* q = ctrl + row * CH;
-      if (RIGID) {
-        const float w = vox_weight(c, u), r = rig[row];
-#pragma unroll
-        for (int ch = 0; ch < CH; ++ch) {
-          const float qv = q[ch];
-          cp[ch] = cp[ch] + w * qv;
-          tcp[ch] = tcp[ch] + d * qv;
-        }
-        rl = rl + w * r;
-        trl = trl + d * r;
-      } else {
-#pragma unroll
-        for (int ch = 0; ch < CH; ++ch) tcp[ch] = tcp[ch] + d * q[ch];
-      }
-    }
+    dv_gather<NC, RIGID, true, RIGID>(c, g, ctrl, rig, e, cp, &rl, tcp, &trl);
     const float tn = t[n];
     float j[3];
     dv_spline<NC>(tcp, tn, j);
@@ -87,7 +56,7 @@ __global__ __launch_bounds__(256) void dyn_voxel_jac_quad_kernel(const float* __
 }
 
 // corner u of a sample adds (v . grad w_u) g[n] B_k(t) v_a to channel 3(k-1) + a of ctrl row_u: one wide row of W = 3(NC-1) sums per
-// grid row on dyn_voxel_scatter.h's table (add_row's weight is v . grad w_u)
+// grid row on voxel_scatter.h's table (add_row's weight is v . grad w_u)
 template <int NC>
 __global__ __launch_bounds__(256) void dyn_voxel_jac_quad_backward_kernel(const float* __restrict__ pts, const float* __restrict__ t, int64_t N,
                                                                           VoxGrid g, const float* __restrict__ v, const float* __restrict__ g_up,
@@ -115,13 +84,9 @@ __global__ __launch_bounds__(256) void dyn_voxel_jac_quad_backward_kernel(const 
       for (int a = 0; a < 3; ++a) sv[3 * (k - 1) + a] = gb * e[a];
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) table.add_row((uint32_t)vox_row(c, u, g.S), jq_dweight(c, u, e, g.vl), sv, add_global);
+    for (int u = 0; u < 8; ++u) table.add_row((uint32_t)vox_row(c, u, g.S), dv_tangent(c, u, e, g.vl), sv, add_global);
   }
-  table.flush([&](uint32_t id, int e, unsigned long long x) {
-    const int64_t at = (int64_t)id * W + e;
-    if (fix == nullptr) atomicAdd(g_ctrl + at, __uint_as_float((uint32_t)x));
-    else atomicAdd((unsigned long long*)(fix + at), x);
-  });
+  table.flush([&](uint32_t id, int e, unsigned long long x) { table.put(g_ctrl, fix, (int64_t)id * W + e, x); });
 }
 
 }  // namespace na

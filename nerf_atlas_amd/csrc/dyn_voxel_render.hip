@@ -3,26 +3,26 @@
 // It replaces, for a model without an MLP, the composition
 //   na_compute_pts -> na_dyn_voxel_warp (warped, dp, rigidity per sample) -> na_voxel_render(pts = warped) (alpha, weights per sample)
 //   -> na_integrate x 4 (weights x ts, weights x [1 .. 1 0], weights x dp * rigidity, weights x rigidity)
-// and is bit for bit equal to it: every step calls the device functions those kernels call (voxel_cell.h, dyn_voxel_spline.h, common.h) in
-// their order, the running product is voxel_render_kernel's, and every map is integrate_kernel's `acc = acc + w * other` in ascending t
+// and is bit for bit equal to it: every step calls the device functions those kernels call (voxel_cell.h, dyn_voxel_spline.h, voxel_plv.h, common.h) in
+// their order, the running product is plv_render_kernel's, and every map is integrate_kernel's `acc = acc + w * other` in ascending t
 // from 0 (this unit is built with -ffp-contract=off like the others).  No per-sample array is written unless alpha / weights are asked for.
 //
 // Decomposition.  Everything in a step but the running product and the sums is independent of the walk, and it is nearly all of the work:
 // two lookups with five correctly rounded divisions per axis each, the spline, four transcendentals.  One thread per ray, as
-// voxel_render_kernel walks, leaves a 64 x 64 test tile with 64 waves for 1024 SIMDs, each issuing 80 steps' arithmetic back to back
+// plv_render_kernel walks, leaves a 64 x 64 test tile with 64 waves for 1024 SIMDs, each issuing 80 steps' arithmetic back to back
 // (measured: 0.36 ms a tile, no faster for a quarter of the rays, and FASTER with less look-ahead -- issue-bound, not latency-bound;
 // DESIGN.md 3o).  So NA_DVR_LANES lanes share a ray: lane j computes steps t0 + j of a chunk of NA_DVR_LANES steps to the point where
 // the walk needs them -- alpha, the three activated colours, dp * rigidity, rigidity -- and parks the eight floats in LDS; then ONE lane
-// per ray walks the chunk in ascending t with voxel_render_kernel's step and integrate_kernel's sums, every operation in their order.
-// The gathers of a whole chunk are in flight ahead of the dependent updates (voxel_render_kernel's habit, NA_DVR_LANES steps deep), a
+// per ray walks the chunk in ascending t with plv_render_kernel's step and integrate_kernel's sums, every operation in their order.
+// The gathers of a whole chunk are in flight ahead of the dependent updates (plv_render_kernel's habit, NA_DVR_LANES steps deep), a
 // tile is 1024 waves, and the walk itself is 80 x ~20 instructions.  NA_DVR_LANES and NA_DVR_BLOCK are build-time constants; DESIGN.md 3o
 // has the times of the other values.
 //
-// The canonical model's head is a template parameter (K): -1 the per-voxel RGB head (na_dyn_voxel_render, C = 3: vox_gather), 0 .. 4 the
-// pos-linear-view head of that order (na_dyn_voxel_plv_render, C = 3 + (K+1)^2: the ray's basis once per thread, vox_plv_gather and the
-// linear scale -- plv_render_kernel's step, so the result equals the composition over na_voxel_plv_render bit for bit).  The K = -1
-// instantiations compile the code they compiled before the parameter existed.
-#include "dyn_voxel_scatter.h"
+// The canonical model's head is a template parameter (K), as in voxel_plv.h's kernels: -1 the per-voxel RGB head (na_dyn_voxel_render,
+// C = 3), 0 .. 4 the pos-linear-view head of that order (na_dyn_voxel_plv_render, C = 3 + (K+1)^2: the ray's basis once per thread and
+// the linear scale).  Lookup, alpha and the walk are plv_render_kernel<K>'s own functions (vox_gather<K>, vox_alpha, VoxWalk), so the
+// result equals the composition over na_voxel_render / na_voxel_plv_render bit for bit; the deformation is na_dyn_voxel_warp's
+// (dv_gather, dv_spline).
 #include "dyn_voxel_spline.h"
 #include "voxel_plv.h"
 
@@ -64,8 +64,8 @@ __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const fl
     const float nrm = sqrtf((ry[0] * ry[0] + ry[1] * ry[1]) + ry[2] * ry[2]);
     const float time = t_ray[rr];
     float Y[SH_MAX_K];
-    if constexpr (K >= 0) plv_ray_basis<K>(rays, rr, Y);
-    float trans = 1.0f, acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, wsum_head = 0.f;
+    plv_ray_basis<K>(rays, rr, Y);
+    VoxWalk walk;
     float depth = 0.f, accm = 0.f, fl0 = 0.f, fl1 = 0.f, fl2 = 0.f, rigm = 0.f;
     for (int t0 = 0; t0 < T; t0 += L) {
       const int t = t0 + j;
@@ -74,55 +74,33 @@ __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const fl
         float px, py, pz;
         vox_position(nullptr, rays, ts, R, (int64_t)t * R + rr, px, py, pz);
         const VoxCell c = vox_cell(px, py, pz, g);
-        float cp[CH], rl = 0.f;
-#pragma unroll
-        for (int ch = 0; ch < CH; ++ch) cp[ch] = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int64_t row = vox_row(c, k, g.S);
-          const float w = vox_weight(c, k);
-          const float* q = ctrl + row * CH;
-#pragma unroll
-          for (int ch = 0; ch < CH; ++ch) cp[ch] = cp[ch] + w * q[ch];
-          rl = rl + w * rig[row];
-        }
-        float dp[3], rdp[3], raw[5], lin = 1.0f;
+        float cp[CH], rl, dp[3], rdp[3], raw[5];
+        dv_gather<NC, true, false, true>(c, g, ctrl, rig, nullptr, cp, &rl, nullptr, nullptr);
         dv_spline<NC>(cp, time, dp);
         const float rg = sigmoidf_(rl);
 #pragma unroll
         for (int a = 0; a < 3; ++a) rdp[a] = dp[a] * rg;  // (rigid_dp: the product formed first, once)
-        // ... the canonical lookup at the warped point, and voxel_render_kernel's step up to the running product
-        if constexpr (K >= 0) {
-          vox_plv_gather<K>(px + rdp[0], py + rdp[1], pz + rdp[2], g, den, rgb, Y, raw);
-          lin = plv_scale(raw[4]);
-        } else {
-          vox_gather(px + rdp[0], py + rdp[1], pz + rdp[2], g, den, rgb, raw);
-        }
-        const float sigma = fast_softplus(raw[0] - 1.0f);
-        float dist = t < T - 1 ? fmaxf(ts[t + 1] - ts[t], 1e-5f) : 1e10f;
-        dist = dist * nrm;
-        const float a = 1.0f - fast_exp(-sigma * dist);
+        // ... the canonical lookup at the warped point, and plv_render_kernel's step up to the running product
+        vox_gather<K>(px + rdp[0], py + rdp[1], pz + rdp[2], g, den, rgb, Y, raw);
+        const float a = vox_alpha(raw[0], ts, t, T, nrm);
         if (live && m.alpha != nullptr) m.alpha[(int64_t)t * R + r] = a;
         float c0 = apply_sigmoid_kind(raw[1], act_kind), c1 = apply_sigmoid_kind(raw[2], act_kind), c2 = apply_sigmoid_kind(raw[3], act_kind);
-        if constexpr (K >= 0) { c0 = lin * c0; c1 = lin * c1; c2 = lin * c2; }
+        if constexpr (K >= 0) {
+          const float lin = plv_scale(raw[4]);
+          c0 = lin * c0; c1 = lin * c1; c2 = lin * c2;
+        }
         park[slot][j][0] = make_float4(a, c0, c1, c2);
         park[slot][j][1] = make_float4(rdp[0], rdp[1], rdp[2], rg);
       }
       __syncthreads();
       if (j == 0 && live) {
-        // the dependent updates, in ascending t: voxel_render_kernel's, then integrate_kernel's `acc = acc + w * other` for the four maps
+        // the dependent updates, in ascending t: plv_render_kernel's, then integrate_kernel's `acc = acc + w * other` for the four maps
         const int n = T - t0 < L ? T - t0 : L;
         for (int u = 0; u < n; ++u) {
           const int tu = t0 + u;
           const float4 p0 = park[slot][u][0], p1 = park[slot][u][1];
-          const float a = p0.x;
-          const float w = a * trans;
-          trans = trans * ((1.0f - a) + 1e-10f);
+          const float w = walk.step(p0.x, p0.y, p0.z, p0.w, tu == T - 1);
           if (m.weights != nullptr) m.weights[(int64_t)tu * R + r] = w;
-          acc0 = acc0 + w * p0.y;
-          acc1 = acc1 + w * p0.z;
-          acc2 = acc2 + w * p0.w;
-          if (tu < T - 1) wsum_head = wsum_head + w;
           depth = depth + w * ts[tu];
           accm = accm + w * (tu < T - 1 ? 1.0f : 0.0f);  // (the product with 0 is kept: a NaN weight stays a NaN map)
           fl0 = fl0 + w * p1.x;
@@ -134,8 +112,7 @@ __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const fl
       __syncthreads();  // (the next chunk overwrites the parked steps)
     }
     if (j == 0 && live) {
-      const float sky = bg_kind == NA_BG_WHITE ? 1.0f - wsum_head : 0.f;
-      out[r * 3] = acc0 + sky; out[r * 3 + 1] = acc1 + sky; out[r * 3 + 2] = acc2 + sky;
+      walk.finish(bg_kind, out + r * 3);
       if (m.depth != nullptr) m.depth[r] = depth;
       if (m.acc != nullptr) m.acc[r] = accm;
       if (m.flow != nullptr) { m.flow[r * 3] = fl0; m.flow[r * 3 + 1] = fl1; m.flow[r * 3 + 2] = fl2; }

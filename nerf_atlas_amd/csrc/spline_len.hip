@@ -9,6 +9,8 @@
 //                                        mean over the samples of w[n] len[n] (--spline-len-decay)
 // Every operation is fp32 in the reference's order (this unit is built with -ffp-contract=off): 1 - t, the n - 1 levels
 // b_j <- b_j (1 - t) + b_{j+1} t, the difference, (dx^2 + dy^2) + dz^2, sqrtf, the sum over the segments in segment order.
+// The levels and the Bernstein recurrence are dyn_voxel_spline.h's (dv_casteljau, dv_bernstein_levels), called directly: the length
+// is de_casteljau at n == 4 as well, never dv_spline's cubic form.
 //
 // GRADIENT.  d len / d control point k = sum_j dir_j (B_k(t_{j+1}) - B_k(t_j)) with dir_j = (p_{j+1} - p_j) / |p_{j+1} - p_j|, and
 // dir_j = 0 for a segment of length 0 (torch.linalg.vector_norm's gradient there: 0, not NaN); the points are recomputed by the same
@@ -20,57 +22,21 @@
 // LDS, and the workgroups' partials are combined by one atomic each: fp32 atomics by default, 2^-40 fixed point under
 // na_set_deterministic (bitwise reproducible).  The workgroup that arrives last divides by the count in double and stores the value
 // with one rounding (na_grid_tv's protocol: out[1] counts arriving waves).
-#include "dyn_voxel_scatter.h"
+#include "voxel_scatter.h"
+#include "dyn_voxel_spline.h"
 
 namespace na {
 
 constexpr int kSlMaxM = 32;               // points on the spline at most (Python uses 16)
 constexpr int64_t kSlMaxBlocks = 1 << 18;  // beyond 2^26 samples a thread takes a second sample
 
-// de Casteljau on P[0 .. NP-1][3] at t
-template <int NP>
-__device__ __forceinline__ void sl_point(const float (&P)[NP][3], float t, float p[3]) {
-  const float m1t = 1.f - t;
-  float b[NP][3];
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) b[k][a] = P[k][a];
-  }
-#pragma unroll
-  for (int i = 1; i < NP; ++i) {
-#pragma unroll
-    for (int j = 0; j < NP - i; ++j) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) b[j][a] = b[j][a] * m1t + b[j + 1][a] * t;
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) p[a] = b[0][a];
-}
-
-// the Bernstein polynomials of degree NP - 1 at t by the de Casteljau recurrence on the weights
-template <int NP>
-__device__ __forceinline__ void sl_bernstein(float t, float (&B)[NP]) {
-  const float m1t = 1.f - t;
-  B[0] = 1.f;
-#pragma unroll
-  for (int k = 1; k < NP; ++k) B[k] = 0.f;
-#pragma unroll
-  for (int i = 1; i < NP; ++i) {
-#pragma unroll
-    for (int j = i; j >= 1; --j) B[j] = B[j] * m1t + B[j - 1] * t;
-    B[0] = B[0] * m1t;
-  }
-}
-
 // dB[j * NP + k] = B_k(t_{j+1}) - B_k(t_j), j = 0 .. M-2, once per workgroup (ends with a barrier)
 template <int NP>
 __device__ __forceinline__ void sl_bernstein_steps(const float* __restrict__ t, int M, float* dB) {
   for (int j = threadIdx.x; j < M - 1; j += blockDim.x) {
     float B0[NP], B1[NP];
-    sl_bernstein<NP>(t[j], B0);
-    sl_bernstein<NP>(t[j + 1], B1);
+    dv_bernstein_levels<NP>(t[j], B0);
+    dv_bernstein_levels<NP>(t[j + 1], B1);
 #pragma unroll
     for (int k = 0; k < NP; ++k) dB[j * NP + k] = B1[k] - B0[k];
   }
@@ -81,7 +47,7 @@ __device__ __forceinline__ void sl_bernstein_steps(const float* __restrict__ t, 
 template <int NP, bool GRAD>
 __device__ __forceinline__ float sl_arc(const float (&P)[NP][3], const float* __restrict__ t, int M, const float* dB, float (&G)[NP][3]) {
   float prev[3], len = 0.f;
-  sl_point<NP>(P, t[0], prev);
+  dv_casteljau<NP>(P, t[0], prev);
   if (GRAD) {
 #pragma unroll
     for (int k = 0; k < NP; ++k) G[k][0] = G[k][1] = G[k][2] = 0.f;
@@ -89,7 +55,7 @@ __device__ __forceinline__ float sl_arc(const float (&P)[NP][3], const float* __
 #pragma unroll 1
   for (int j = 1; j < M; ++j) {
     float cur[3], d[3];
-    sl_point<NP>(P, t[j], cur);
+    dv_casteljau<NP>(P, t[j], cur);
 #pragma unroll
     for (int a = 0; a < 3; ++a) d[a] = cur[a] - prev[a];
     const float l = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
@@ -190,19 +156,11 @@ __global__ __launch_bounds__(256) void grid_spline_len_backward_kernel(const flo
 }
 
 // ------------------------------------------------------------------------------------ the per-sample term
-// control points 1 .. NC-1 of a sample: na_dyn_voxel_warp's gather (8 rows of 3(NC-1) floats, corner order, cp <- cp + w_u v_u)
+// the control points of a sample: zero, then 1 .. NC-1 by na_dyn_voxel_warp's gather (dv_gather; P[1 ..] is 3(NC-1) floats in a row)
 template <int NC>
-__device__ __forceinline__ void sl_gather(const float* __restrict__ ctrl, const VoxCell& c, int S, float (&P)[NC][3]) {
-  constexpr int CH = 3 * (NC - 1);
-#pragma unroll
-  for (int k = 0; k < NC; ++k) P[k][0] = P[k][1] = P[k][2] = 0.f;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const float* q = ctrl + vox_row(c, u, S) * CH;
-    const float w = vox_weight(c, u);
-#pragma unroll
-    for (int ch = 0; ch < CH; ++ch) P[1 + ch / 3][ch % 3] = P[1 + ch / 3][ch % 3] + w * q[ch];
-  }
+__device__ __forceinline__ void sl_gather(const float* __restrict__ ctrl, const VoxCell& c, const VoxGrid& g, float (&P)[NC][3]) {
+  P[0][0] = P[0][1] = P[0][2] = 0.f;
+  dv_gather<NC, true, false, false>(c, g, ctrl, nullptr, nullptr, &P[1][0], nullptr, nullptr, nullptr);
 }
 
 // one thread per sample (S = 64, n = 4: 9.4 MiB of control points, L2 / Infinity Cache resident; the work is the VALU stream)
@@ -217,7 +175,7 @@ __global__ __launch_bounds__(256) void dyn_voxel_spline_len_kernel(const float* 
     if (n < N) {
       const VoxCell c = vox_cell(pts[n * 3], pts[n * 3 + 1], pts[n * 3 + 2], g);
       float P[NC][3], G[NC][3];
-      sl_gather<NC>(ctrl, c, g.S, P);
+      sl_gather<NC>(ctrl, c, g, P);
       const float len = sl_arc<NC, false>(P, t, M, nullptr, G);
       if (lens != nullptr) lens[n] = len;
       acc = acc + (w != nullptr ? w[n] * len : len);
@@ -227,7 +185,7 @@ __global__ __launch_bounds__(256) void dyn_voxel_spline_len_kernel(const float* 
 }
 
 // corner u of a sample adds w_u (g_up w[n] / N) d len / d control point k to channels 3(k-1) .. 3k-1 of ctrl row_u: one wide row of
-// W = 3(NC-1) sums per grid row on dyn_voxel_scatter.h's table
+// W = 3(NC-1) sums per grid row on voxel_scatter.h's table
 template <int NC>
 __global__ __launch_bounds__(256) void dyn_voxel_spline_len_backward_kernel(const float* __restrict__ pts, int64_t N, VoxGrid g,
                                                                             const float* __restrict__ ctrl, const float* __restrict__ w,
@@ -250,7 +208,7 @@ __global__ __launch_bounds__(256) void dyn_voxel_spline_len_backward_kernel(cons
     if (n >= n_hi) continue;  // (no barrier inside the loop)
     const VoxCell c = vox_cell(pts[n * 3], pts[n * 3 + 1], pts[n * 3 + 2], g);
     float P[NC][3], G[NC][3], sv[W];
-    sl_gather<NC>(ctrl, c, g.S, P);
+    sl_gather<NC>(ctrl, c, g, P);
     sl_arc<NC, true>(P, t, M, dB, G);
     const float s = w != nullptr ? s0 * w[n] : s0;
 #pragma unroll
@@ -261,11 +219,7 @@ __global__ __launch_bounds__(256) void dyn_voxel_spline_len_backward_kernel(cons
 #pragma unroll
     for (int u = 0; u < 8; ++u) table.add_row((uint32_t)vox_row(c, u, g.S), vox_weight(c, u), sv, add_global);
   }
-  table.flush([&](uint32_t id, int e, unsigned long long v) {
-    const int64_t at = (int64_t)id * W + e;
-    if (fix == nullptr) atomicAdd(g_ctrl + at, __uint_as_float((uint32_t)v));
-    else atomicAdd((unsigned long long*)(fix + at), v);
-  });
+  table.flush([&](uint32_t id, int e, unsigned long long v) { table.put(g_ctrl, fix, (int64_t)id * W + e, v); });
 }
 
 static int sl_check_table(const char* who, const float* t, int M) {

@@ -1,5 +1,6 @@
-// The reference's 8-neighbour grid lookup (grid_coords_trilin_weights, src/nerf.py:493-515) as device functions shared by voxel.hip,
-// dyn_voxel.hip and dyn_voxel_render.hip: cell membership and xyz are the reference's fp32 chain, operation for operation (voxel.hip's header comment).
+// The reference's 8-neighbour grid lookup (grid_coords_trilin_weights, src/nerf.py:493-515) as device functions shared by every voxel unit:
+// cell membership and xyz are the reference's fp32 chain, operation for operation (voxel.hip's header comment).  The lookup itself
+// (vox_gather) and the kernels of a voxel model are voxel_plv.h's, the scatter table is voxel_scatter.h's.
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -65,6 +66,14 @@ __device__ __forceinline__ float vox_weight(const VoxCell& c, int u) {
   return (wx * wy) * wz;
 }
 
+// d w_u / d xyz: (+-(wy wz), +-(wx wz), +-(wx wy)), + when corner u takes the upper cell on that axis.  One product each, then the
+// sign; what the callers form from it (g += d * v in the position gradients, ((v0 gx + v1 gy) + v2 gz) / vl in dv_tangent) is theirs.
+__device__ __forceinline__ void vox_dweight(const VoxCell& c, int u, float& gx, float& gy, float& gz) {
+  const float wx = (u & 1) ? c.x : 1.f - c.x, wy = (u & 2) ? c.y : 1.f - c.y, wz = (u & 4) ? c.z : 1.f - c.z;
+  const float yz = wy * wz, xz = wx * wz, xy = wx * wy;
+  gx = (u & 1) ? yz : -yz; gy = (u & 2) ? xz : -xz; gz = (u & 4) ? xy : -xy;
+}
+
 __device__ __forceinline__ int64_t vox_row(const VoxCell& c, int u, int S) {
   return ((int64_t)c.ix[u & 1] * S + c.iy[(u >> 1) & 1]) * S + c.iz[(u >> 2) & 1];
 }
@@ -79,24 +88,6 @@ __device__ __forceinline__ void vox_position(const float* __restrict__ pts, cons
   const float* ry = rays + (n % R) * 6;
   const float tt = ts[n / R];
   px = ry[0] + tt * ry[3]; py = ry[1] + tt * ry[4]; pz = ry[2] + tt * ry[5];
-}
-
-// raw[0] = density, raw[1..3] = colour parameters: sum over the 8 corners in corner order (4-byte + 12-byte loads per corner; the
-// S = 64 grid is 4 MiB and stays in the L2 / Infinity Cache)
-__device__ __forceinline__ void vox_gather(float px, float py, float pz, const VoxGrid& g, const float* __restrict__ den,
-                                           const float* __restrict__ rgb, float raw[4]) {
-  const VoxCell c = vox_cell(px, py, pz, g);
-  raw[0] = raw[1] = raw[2] = raw[3] = 0.f;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int64_t row = vox_row(c, u, g.S);
-    const float w = vox_weight(c, u);
-    const float* q = rgb + row * 3;
-    raw[0] = raw[0] + w * den[row];
-    raw[1] = raw[1] + w * q[0];
-    raw[2] = raw[2] + w * q[1];
-    raw[3] = raw[3] + w * q[2];
-  }
 }
 
 static int vox_check_grid(const char* who, int S, int C, double grid_radius) {

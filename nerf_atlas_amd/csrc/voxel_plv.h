@@ -1,26 +1,31 @@
-// NeRFVoxel's view-dependent head (PosLinearView.to_voxel, src/refl.py:265-280) as device functions shared by voxel_plv.hip: the grid
-// row is [raw rgb (3) | (K+1)^2 coefficients of ONE spherical-harmonic channel], C = 3 + (K+1)^2 floats, and
+// The kernels of a voxel model (NeRFVoxel, src/nerf.py:401-524) for both of its heads, as templates over K:
+//   K = -1      the per-voxel RGB head: grid rows of C = 3 colour parameters (voxel.hip has the entry points)
+//   K = 0 .. 4  the view-dependent head (PosLinearView.to_voxel, src/refl.py:265-280; entry points in voxel_plv.hip): the grid row is
+//               [raw rgb (3) | (K+1)^2 coefficients of ONE spherical-harmonic channel], C = 3 + (K+1)^2 floats, and
 //     rgb = act(raw_rgb) * (sigmoid(s) / 2 + 0.5),   s = sum_k Y_k(normalize(view)) c_k,   c_k = the interpolated coefficient k.
 // Interpolation and expansion are both linear in the grid, and Y depends on the ray only, so the lookup contracts every corner's
-// coefficients with the ray's basis as the row arrives: the (K+1)^2 interpolated coefficients never exist.
+// coefficients with the ray's basis as the row arrives: the (K+1)^2 interpolated coefficients never exist.  At K = -1 there is no
+// basis, no sh output and no linear scale: `if constexpr (K >= 0)` leaves the RGB head's own code.  The ray of sample n is n % R.
+// Also here, for dyn_voxel_render.hip as well: the lookup (vox_gather) and one compositing step (vox_alpha, VoxWalk).
 //
 // ASSOCIATION (one function for every route; tests/voxel_plv_ref.py derives the bound from these counts):
 //     d_u = fma(Y_k, row_u[3 + k], d_u) for k = 1 .. NK-1 in k order, from d_u = Y_0 * row_u[3]      (coefficients first: NK roundings)
 //     s   = s + w_u * d_u for the corners u = 0 .. 7 in corner order, from s = 0                     (a product and a sum per corner)
-// Density and the three colour parameters are vox_gather's arithmetic, operation for operation: with all coefficients zero the four
-// leading outputs are na_voxel_sample's bits.
+// Density and the three colour parameters are v_i = v_i + w_u * row_u[i] in corner order from 0, the same for every K: with all
+// coefficients zero the four leading outputs are na_voxel_sample's bits.
 // Cells, weights and rows are voxel_cell.h's (the operator's definition and its memory-safety rule): the ids are
 // integer-clamped whatever the coordinate is, and a non-finite coordinate makes xyz -- hence every weight and every output of that
 // sample -- NaN.
 #pragma once
 #include "sh_basis.h"
-#include "voxel_cell.h"
+#include "voxel_scatter.h"
+#include <type_traits>
 
 namespace na {
 
 template <int K> struct Plv {
-  static constexpr int NK = (K + 1) * (K + 1);  // coefficients per voxel
-  static constexpr int C = 3 + NK;              // floats per grid row: 4, 7, 12, 19, 28
+  static constexpr int NK = (K + 1) * (K + 1);  // coefficients per voxel (none at K = -1)
+  static constexpr int C = 3 + NK;              // floats per grid row: 3 | 4, 7, 12, 19, 28
   static constexpr bool ALIGNED = C % 4 == 0;   // rows of 4 C bytes are 16-byte aligned for K = 0, 2, 4 only
 };
 
@@ -39,24 +44,31 @@ template <int K> __device__ __forceinline__ void plv_load_row(const float* __res
   }
 }
 
-// d = sum_k Y_k row[3 + k], the association of the header comment
+// d = sum_k Y_k row[3 + k], the association of the header comment (0 at K = -1: nothing reads it)
 template <int K> __device__ __forceinline__ float plv_contract(const float (&r)[Plv<K>::C], const float (&Y)[SH_MAX_K]) {
-  float d = Y[0] * r[3];
+  if constexpr (K < 0) {
+    return 0.f;
+  } else {
+    float d = Y[0] * r[3];
 #pragma unroll
-  for (int k = 1; k < Plv<K>::NK; ++k) d = fmaf(Y[k], r[3 + k], d);
-  return d;
+    for (int k = 1; k < Plv<K>::NK; ++k) d = fmaf(Y[k], r[3 + k], d);
+    return d;
+  }
 }
 
 // the basis of ray r (dirs = rays[:, 3:6], un-normalised: sh_basis normalises with F.normalize's eps like na_sh_shade)
 template <int K> __device__ __forceinline__ void plv_ray_basis(const float* __restrict__ rays, int64_t r, float (&Y)[SH_MAX_K]) {
-  const float* d = rays + r * 6 + 3;
-  sh_basis(K, d[0], d[1], d[2], Y);
+  if constexpr (K >= 0) {
+    const float* d = rays + r * 6 + 3;
+    sh_basis(K, d[0], d[1], d[2], Y);
+  }
 }
 
-// v[0] = density, v[1..3] = colour parameters, v[4] = s: the per-sample lookup of every kernel of the head
+// v[0] = density, v[1..3] = colour parameters, v[4] = s (K >= 0): the per-sample lookup of every kernel.  Sums over the 8 corners
+// in corner order (the S = 64 grid of the RGB head is 4 MiB and stays in the L2 / Infinity Cache).
 template <int K>
-__device__ __forceinline__ void vox_plv_gather(float px, float py, float pz, const VoxGrid& g, const float* __restrict__ den,
-                                               const float* __restrict__ rgb, const float (&Y)[SH_MAX_K], float v[5]) {
+__device__ __forceinline__ void vox_gather(float px, float py, float pz, const VoxGrid& g, const float* __restrict__ den,
+                                           const float* __restrict__ rgb, const float (&Y)[SH_MAX_K], float v[5]) {
   const VoxCell c = vox_cell(px, py, pz, g);
   v[0] = v[1] = v[2] = v[3] = v[4] = 0.f;
 #pragma unroll
@@ -70,7 +82,7 @@ __device__ __forceinline__ void vox_plv_gather(float px, float py, float pz, con
     v[1] = v[1] + w * r[0];
     v[2] = v[2] + w * r[1];
     v[3] = v[3] + w * r[2];
-    v[4] = v[4] + w * d;
+    if constexpr (K >= 0) v[4] = v[4] + w * d;
   }
 }
 
@@ -82,6 +94,236 @@ static int vox_plv_check_grid(const char* who, int S, int order, double grid_rad
   NA_REQUIRE(S >= 2 && S <= 1024 && S % 2 == 0, NA_EINVAL, "%s: resolution %d (even, 2 .. 1024)", who, S);
   NA_REQUIRE(grid_radius > 0 && grid_radius < 1e30, NA_EINVAL, "%s: grid_radius %g", who, grid_radius);
   return NA_OK;
+}
+
+// ------------------------------------------------------------------------------------ one compositing step
+// composite_kernel's (basic_ops.hip) per-step arithmetic on the same device functions, for the three one-launch renderers.
+// The per-sample part, independent of the walk: sigma = fast_softplus(raw0 - 1); dist = max(ts[t + 1] - ts[t], 1e-5), 1e10 at the
+// last step, times nrm; alpha = 1 - fast_exp(-sigma dist).
+__device__ __forceinline__ float vox_alpha(float raw0, const float* __restrict__ ts, int t, int T, float nrm) {
+  const float sigma = fast_softplus(raw0 - 1.0f);
+  float dist = t < T - 1 ? fmaxf(ts[t + 1] - ts[t], 1e-5f) : 1e10f;
+  dist = dist * nrm;
+  return 1.0f - fast_exp(-sigma * dist);
+}
+
+// The walk, in ascending t: w = a trans; trans <- trans ((1 - a) + 1e-10) (the reference's cumprod association);
+// acc_i <- acc_i + w c_i; wsum_head <- wsum_head + w except at the last step.  finish: the sky is 1 - wsum_head on white, 0 on black.
+struct VoxWalk {
+  float trans = 1.0f, acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, wsum_head = 0.f;
+  // the two halves of a step, for a kernel that stores a and w in between
+  __device__ __forceinline__ float weight(float a) {
+    const float w = a * trans;
+    trans = trans * ((1.0f - a) + 1e-10f);
+    return w;
+  }
+  __device__ __forceinline__ void add(float w, float c0, float c1, float c2, bool last) {
+    acc0 = acc0 + w * c0;
+    acc1 = acc1 + w * c1;
+    acc2 = acc2 + w * c2;
+    if (!last) wsum_head = wsum_head + w;
+  }
+  __device__ __forceinline__ float step(float a, float c0, float c1, float c2, bool last) {
+    const float w = weight(a);
+    add(w, c0, c1, c2, last);
+    return w;
+  }
+  __device__ __forceinline__ void finish(int bg_kind, float* __restrict__ out) const {
+    const float sky = bg_kind == NA_BG_WHITE ? 1.0f - wsum_head : 0.f;
+    out[0] = acc0 + sky; out[1] = acc1 + sky; out[2] = acc2 + sky;
+  }
+};
+
+// ------------------------------------------------------------------------------------ gather
+// one thread per sample, one 16-byte row store (+ sh [N] = s with the view-dependent head).  The RGB head's instantiation is pinned to
+// the 6 waves per SIMD it had as a kernel of its own (72 VGPRs; left alone the allocator takes 91 for the same instructions).
+template <int K>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K < 0 ? 6 : 1, K < 0 ? 6 : 8)))
+void plv_sample_kernel(const float* __restrict__ pts, const float* __restrict__ rays, const float* __restrict__ ts, int64_t R, int64_t N,
+                       VoxGrid g, const float* __restrict__ den, const float* __restrict__ rgb, float* __restrict__ raw,
+                       float* __restrict__ sh) {
+  for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
+    float Y[SH_MAX_K], px, py, pz, v[5];
+    plv_ray_basis<K>(rays, n % R, Y);
+    vox_position(pts, rays, ts, R, n, px, py, pz);
+    vox_gather<K>(px, py, pz, g, den, rgb, Y, v);
+    *(float4*)(raw + n * 4) = make_float4(v[0], v[1], v[2], v[3]);
+    if constexpr (K >= 0) sh[n] = v[4];
+  }
+}
+
+// ------------------------------------------------------------------------------------ gather: gradient w.r.t. the positions
+// g_pts[n, a] = (1 / voxel_len) sum_u (dw_u / dxyz_a) v_u with the per-corner value
+//   v_u = ((g_raw[n, 0] den[row_u] + g_raw[n, 1] rgb[row_u, 0]) + g_raw[n, 2] rgb[row_u, 1]) + g_raw[n, 3] rgb[row_u, 2]
+//         (+ g_sh[n] sum_k Y_k rgb[row_u, 3 + k] with the view-dependent head),
+// g_a <- g_a + (dw_u / dxyz_a) v_u in corner order, then the division.  In the reference only xyz = (p - centre of corner 0) /
+// voxel_len depends on p -- the floors and both clamps carry no gradient -- so the derivative is the one of the polynomial this cell's
+// weights are (vox_dweight), inside the grid and in the extrapolated region alike.  A gather (no atomics), one thread per sample.
+// A non-finite coordinate makes the whole row NaN (one NaN fraction alone would leave the other two axes' sums finite).
+template <int K>
+__global__ __launch_bounds__(256) void plv_backward_pts_kernel(const float* __restrict__ pts, const float* __restrict__ rays, int64_t R,
+                                                               int64_t N, VoxGrid g, const float* __restrict__ den,
+                                                               const float* __restrict__ rgb, const float* __restrict__ g_raw,
+                                                               const float* __restrict__ g_sh, float* __restrict__ g_pts) {
+  for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
+    float Y[SH_MAX_K];
+    plv_ray_basis<K>(rays, n % R, Y);
+    const VoxCell c = vox_cell(pts[n * 3], pts[n * 3 + 1], pts[n * 3 + 2], g);
+    const float4 gv = *(const float4*)(g_raw + n * 4);
+    float gs = 0.f;
+    if constexpr (K >= 0) gs = g_sh[n];
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int64_t row = vox_row(c, u, g.S);
+      float q[Plv<K>::C], dx, dy, dz;
+      plv_load_row<K>(rgb + row * Plv<K>::C, q);
+      float v = ((gv.x * den[row] + gv.y * q[0]) + gv.z * q[1]) + gv.w * q[2];
+      if constexpr (K >= 0) v = v + gs * plv_contract<K>(q, Y);
+      vox_dweight(c, u, dx, dy, dz);
+      gx = gx + dx * v;
+      gy = gy + dy * v;
+      gz = gz + dz * v;
+    }
+    const bool bad = (c.x != c.x) | (c.y != c.y) | (c.z != c.z);
+    const float nan = __builtin_nanf("");
+    g_pts[n * 3] = bad ? nan : gx / g.vl;
+    g_pts[n * 3 + 1] = bad ? nan : gy / g.vl;
+    g_pts[n * 3 + 2] = bad ? nan : gz / g.vl;
+  }
+}
+
+// ------------------------------------------------------------------------------------ scatter-add
+// Corner u of sample n receives w_u [g_raw[n, 0] | g_raw[n, 1..3] | g_sh[n] Y_k]: 1 + C sums per grid row, 4 with the RGB head, 29 at
+// K = 4, on voxel_scatter.h's table.  1024 rows x 29 sums x 8 B do not fit a CU's 160 KiB, so the table comes in two geometries:
+//   variant 1 (FULL)  whole rows in the table, as many rows as fit 60 KiB (two workgroups per CU): fp32 mode keeps 4-byte
+//                     entries (512 rows at K = 4), the deterministic mode 8-byte fixed-point entries (256 rows)
+//   variant 2 (LEAD)  1024 rows x 4 sums x 8 B for [density | rgb]; the SH block goes straight to the global accumulators.  This
+//                     is the RGB head's table (it has no SH block).
+// NA_PLV_SCATTER (voxel_plv.hip) picks the variant na_voxel_plv_sample_backward runs (DESIGN.md 3p has the times of both).
+constexpr int PLV_LDS_BUDGET = 60 * 1024;  // table bytes of a workgroup: two workgroups share a CU's 160 KiB
+
+template <int K, int VARIANT, bool DET> struct PlvTable {
+  static constexpr int SUMS = VARIANT == 1 ? 1 + Plv<K>::C : 4;   // sums of a table row
+  static constexpr int ENTRY = (DET || VARIANT == 2) ? 8 : 4;     // bytes of a sum
+  static constexpr int rows_for(int r) { return (r * 2 * (SUMS * ENTRY + 4) <= PLV_LDS_BUDGET && r < 1024) ? rows_for(r * 2) : r; }
+  static constexpr int ROWS = rows_for(1);                        // a power of two, 1024 at most
+  using type = VoxTable<SUMS, typename std::conditional<ENTRY == 8, unsigned long long, float>::type, ROWS, DET>;
+};
+
+template <int K, int VARIANT, bool DET>
+__global__ __launch_bounds__(256) void plv_backward_kernel(const float* __restrict__ pts, const float* __restrict__ rays,
+                                                           const float* __restrict__ ts, int64_t R, int64_t N, VoxGrid g,
+                                                           const float* __restrict__ g_raw, const float* __restrict__ g_sh,
+                                                           float* __restrict__ g_den, float* __restrict__ g_rgb,
+                                                           long long* __restrict__ fix) {
+  using Table = typename PlvTable<K, VARIANT, DET>::type;
+  constexpr int C = Plv<K>::C, NK = Plv<K>::NK, SUMS = PlvTable<K, VARIANT, DET>::SUMS, ROWS = PlvTable<K, VARIANT, DET>::ROWS;
+  const int64_t S3 = (int64_t)g.S * g.S * g.S;
+  long long* fix_rgb = DET ? fix + S3 : nullptr;
+  long long* fix_den = DET ? fix : nullptr;
+  // sum e of grid row id: e = 0 density, e = 1 + c channel c of the rgb row
+  auto add_global = [&](uint32_t id, int e, float v) {
+    if (e == 0) accumulate(g_den, fix_den, (int64_t)id, v);
+    else accumulate(g_rgb, fix_rgb, (int64_t)id * C + (e - 1), v);
+  };
+  __shared__ uint32_t tags[ROWS];
+  __shared__ typename Table::Entry vals[ROWS * SUMS];
+  const Table table{tags, vals, fix_den};
+  table.clear();
+  int64_t n_lo, n_hi;
+  dv_run(N, n_lo, n_hi);
+  for (int64_t base = n_lo; base < n_hi; base += 256) {
+    const int64_t n = base + threadIdx.x;
+    if (n < n_hi) {
+      float Y[SH_MAX_K], px, py, pz;
+      plv_ray_basis<K>(rays, n % R, Y);
+      vox_position(pts, rays, ts, R, n, px, py, pz);
+      const VoxCell c = vox_cell(px, py, pz, g);
+      const float4 gv = *(const float4*)(g_raw + n * 4);
+      float gs = 0.f;
+      if constexpr (K >= 0) gs = g_sh[n];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const uint32_t id = (uint32_t)vox_row(c, u, g.S);
+        const float w = vox_weight(c, u);
+        const float lead[4] = {w * gv.x, w * gv.y, w * gv.z, w * gv.w};
+        const float as = w * gs;
+        const int slot = table.find_slot(id);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (slot >= 0) table.add(id, slot, e, lead[e], add_global);
+          else add_global(id, e, lead[e]);
+        }
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+          const float a = as * Y[k];
+          if (VARIANT == 1 && slot >= 0) table.add(id, slot, 4 + k, a, add_global);
+          else add_global(id, 4 + k, a);
+        }
+      }
+    }
+  }
+  table.flush([&](uint32_t id, int e, typename Table::Entry v) {
+    if (v == 0) return;  // (most rows of a wide table hold no SH sums)
+    const int64_t at = e == 0 ? (int64_t)id : (int64_t)id * C + (e - 1);
+    table.put(e == 0 ? g_den : g_rgb, e == 0 ? fix_den : fix_rgb, at, v);
+  });
+}
+
+template <int K, int VARIANT>
+static void plv_launch_backward(unsigned wg, hipStream_t s, const float* pts, const float* rays, const float* ts, int64_t R, int64_t N,
+                                VoxGrid g, const float* g_raw, const float* g_sh, float* g_den, float* g_rgb, long long* fix) {
+  if (fix != nullptr)
+    hipLaunchKernelGGL((plv_backward_kernel<K, VARIANT, true>), dim3(wg), dim3(256), 0, s, pts, rays, ts, R, N, g, g_raw, g_sh, g_den, g_rgb, fix);
+  else
+    hipLaunchKernelGGL((plv_backward_kernel<K, VARIANT, false>), dim3(wg), dim3(256), 0, s, pts, rays, ts, R, N, g, g_raw, g_sh, g_den, g_rgb, fix);
+}
+
+// ------------------------------------------------------------------------------------ eval route, one launch
+// One thread per ray walks T in order like composite_kernel (vox_alpha, VoxWalk); the basis is evaluated once per ray and held in
+// registers over the walk.  The rows of U steps are gathered first -- their addresses do not depend on the walk -- so 8 U independent
+// row loads are in flight before the U dependent updates run: 4 steps with the RGB head, 2 / 1 with the wider rows (or the rows in
+// flight leave the registers).
+template <int K>
+__global__ __launch_bounds__(64) void plv_render_kernel(const float* __restrict__ rays, const float* __restrict__ pts,
+                                                        const float* __restrict__ ts, int T, int64_t R, VoxGrid g,
+                                                        const float* __restrict__ den, const float* __restrict__ rgb, int act_kind,
+                                                        int bg_kind, float* __restrict__ alpha_out, float* __restrict__ weights_out,
+                                                        float* __restrict__ out) {
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < R; r += (int64_t)gridDim.x * blockDim.x) {
+    const float* ry = rays + r * 6 + 3;
+    const float nrm = sqrtf((ry[0] * ry[0] + ry[1] * ry[1]) + ry[2] * ry[2]);
+    float Y[SH_MAX_K];
+    plv_ray_basis<K>(rays, r, Y);
+    VoxWalk walk;
+    constexpr int U = K < 0 ? 4 : K <= 1 ? 2 : 1;
+    for (int t0 = 0; t0 < T; t0 += U) {
+      float raw[U][5];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int t = t0 + u < T ? t0 + u : T - 1;  // (clamped: the tail gathers the last step again and ignores it)
+        float px, py, pz;
+        vox_position(pts, rays, ts, R, (int64_t)t * R + r, px, py, pz);
+        vox_gather<K>(px, py, pz, g, den, rgb, Y, raw[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int t = t0 + u;
+        if (t < T) {
+          const float a = vox_alpha(raw[u][0], ts, t, T, nrm);
+          const float w = walk.weight(a);
+          if (alpha_out != nullptr) alpha_out[(int64_t)t * R + r] = a;
+          if (weights_out != nullptr) weights_out[(int64_t)t * R + r] = w;
+          float lin = 1.0f;
+          if constexpr (K >= 0) lin = plv_scale(raw[u][4]);
+          const auto colour = [&](float p) { return K >= 0 ? lin * apply_sigmoid_kind(p, act_kind) : apply_sigmoid_kind(p, act_kind); };
+          walk.add(w, colour(raw[u][1]), colour(raw[u][2]), colour(raw[u][3]), t == T - 1);
+        }
+      }
+    }
+    walk.finish(bg_kind, out + r * 3);
+  }
 }
 
 }  // namespace na
