@@ -970,6 +970,38 @@ int na_dyn_voxel_jac_quad(const float* pts, const float* t, int64_t N, const flo
 int na_dyn_voxel_jac_quad_backward(const float* pts, const float* t, int64_t N, int S, int n_ctrl, double grid_radius, const float* v,
                                    const float* g, float* g_ctrl_pts_grid, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * SSIM and the pieces of MS-SSIM (Wang et al. with the choices of pytorch_msssim, which the reference calls: src/utils.py:186-195;
+ * csrc/ssim.hip).  Images x, y are fp32 channel-last [N,H,W,C], C = 1 .. 4 (else NA_EUNSUPPORTED), read in place.
+ * The window G is 11 taps, Gaussian with sigma 1.5, normalised in double and rounded once to fp32, separable, "valid": an H x W image
+ * gives an (H-10) x (W-10) map, and H < 11 or W < 11 is NA_EUNSUPPORTED (pytorch_msssim warns and skips the axis).  Per map pixel
+ *   mu1 = G*x, mu2 = G*y, s1 = G*(x x) - mu1^2, s2 = G*(y y) - mu2^2, s12 = G*(x y) - mu1 mu2, C1 = (0.01 L)^2, C2 = (0.03 L)^2,
+ *   cs = (2 s12 + C2) / (s1 + s2 + C2),   ssim = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) cs,          L = data_range.
+ * N == 0 returns NA_OK without a launch; a NULL required pointer is NA_ENULL and named in na_last_error.  Nothing here uses atomics or
+ * allocates: every result is bit-identical from run to run in every mode.
+ * na_ssim_workspace_bytes  the bytes of workspace na_ssim needs for this shape (0 for a shape it refuses): two floats per 16 x 16
+ *                          tile of the map, image and channel.
+ * na_ssim                  out [N,C,2] = (mean of ssim, mean of cs) over the map, per (n, c).  Two launches on the stream: one forms
+ *                          the moments of a tile with its halo in LDS (the variances centred on the pixel's own means: no
+ *                          cancellation) and writes one pair of partial sums per tile to the workspace, the second adds them in a
+ *                          fixed order (in double) and divides.  A non-finite pixel makes the means of its own (n, c) NaN and touches
+ *                          no other.  A workspace smaller than the query's answer is NA_EWORKSPACE.
+ * na_ssim_backward         g_x [N,H,W,C] = the gradient of sum_{n,c} g[n,c] mean_ssim[n,c] w.r.t. x (y takes none); g is [N,C].  With
+ *                          B1 = mu1^2 + mu2^2 + C1, B2 = s1 + s2 + C2, A1 = 2 mu1 mu2 + C1, S = ssim:  dS/ds1 = -S / B2,
+ *                          dS/ds12 = 2 A1 / (B1 B2),  dS/dmu1 = 2 mu2 (2 s12 + C2) / (B1 B2) - 2 mu1 S / B1,
+ *                          dm = dS/dmu1 - 2 mu1 dS/ds1 - mu2 dS/ds12,  g_x = (G^T[dm] + 2 x G^T[dS/ds1] + y G^T[dS/ds12]) g[n,c] /
+ *                          ((H-10)(W-10)), G^T the transposed ("full") filter.  One launch; the moments are recomputed per tile; every
+ *                          element of g_x is written by exactly one thread.
+ * na_image_halve           out_x, out_y [N,Ho,Wo,C] = F.avg_pool2d(kernel 2, padding (H % 2, W % 2), count_include_pad=True) of x and
+ *                          y in one launch: Ho = H / 2 + H % 2 (Wo alike), every output is ((a + b) + c) + d times 0.25 with 0 for a
+ *                          padded pixel.  y and out_y may both be NULL (one image).                                              */
+size_t na_ssim_workspace_bytes(int64_t N, int H, int W, int C);
+int na_ssim(const float* x, const float* y, int64_t N, int H, int W, int C, float data_range, float* out, void* workspace,
+            size_t workspace_bytes, void* stream);
+int na_ssim_backward(const float* x, const float* y, const float* g, int64_t N, int H, int W, int C, float data_range, float* g_x,
+                     void* stream);
+int na_image_halve(const float* x, const float* y, int64_t N, int H, int W, int C, float* out_x, float* out_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -662,3 +662,19 @@ class DynVoxelJacQuadFn(Function):
         pts, t, *v = ctx.saved_tensors
         g_ctrl = ops.dyn_voxel_jac_quad_backward(pts, t, ctx.S, ctx.spline, ctx.grid_radius, g.contiguous(), v[0] if v else None)
         return g_ctrl, None, None, None, None, None
+
+
+class SSIMFn(Function):
+    """ssim [N,C] of the channel-last pair x, y [N,H,W,C] (ops.ssim); backward is ops.ssim_backward, one launch that recomputes the
+    moments per tile.  The gradient goes to x only: y is the reference image."""
+
+    @staticmethod
+    def forward(ctx, x, y, flag):
+        ctx.flag = flag
+        ctx.save_for_backward(x, y)
+        return ops.ssim(x, y, 1.0, flag)[0].contiguous()
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        return ops.ssim_backward(x, y, g.contiguous(), 1.0, ctx.flag), None, None

@@ -44,6 +44,7 @@ UNITS = [
     ("spline_len.hip", [], ""),
     ("dyn_voxel_div.hip", [], ""),
     ("grid_ops.hip", [], ""),
+    ("ssim.hip", [], ""),
     ("optim.hip", [], ""),
     ("backward.hip", [], ""),
     ("train_gemm.hip", [], ""),

@@ -2185,3 +2185,101 @@ def dyn_voxel_spline_len_backward(pts: torch.Tensor, ctrl_pts_grid: torch.Tensor
     check(lib.na_dyn_voxel_spline_len_backward(_ptr(pts), N, _ptr(ctrl), S, spline, float(grid_radius), _ptr(w),
                                                _ptr(_spline_len_table(str(pts.device))), SPLINE_LEN_SAMPLES, _ptr(g), _ptr(out), _stream()))
     return out
+
+
+# ------------------------------------------------------------------------------------------------- SSIM / MS-SSIM (csrc/ssim.hip)
+SSIM_WINDOW = 11
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)  # pytorch_msssim's default scale weights
+MS_SSIM_MIN_SIDE = (SSIM_WINDOW - 1) * 2 ** (len(MS_SSIM_WEIGHTS) - 1)  # 160: both sides must be LARGER (the library's assertion)
+
+
+def _ssim_images(x: torch.Tensor, y: torch.Tensor, flag: str):
+    """the image pair [N,H,W,C] as the kernels read it: device, fp32, channel-last, contiguous, C = 1 .. 4 -> (x, y, N, H, W, C).
+    flag: the caller's command-line flag, named where a CPU tensor arrives (there is no CPU implementation)"""
+    if not x.is_cuda or not y.is_cuda:
+        raise NotImplementedError(f"{flag} runs on the GPU only: SSIM is a HIP kernel (DESIGN.md 3r) and the images are on "
+                                  f"{x.device} / {y.device}")
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError(f"{flag}: two channel-last images [N,H,W,C] of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    x, y = _f32(x, "x"), _f32(y, "y")
+    N, H, W, Cn = x.shape
+    if not 1 <= Cn <= 4:
+        raise ValueError(f"{flag}: {Cn} channels, 1 .. 4 have a kernel")
+    if min(H, W) < SSIM_WINDOW:
+        raise ValueError(f"{flag}: a {H} x {W} image is smaller than the {SSIM_WINDOW}-tap window")
+    return x, y, N, H, W, Cn
+
+
+def ssim(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, flag: str = "ops.ssim"):
+    """(ssim [N,C], cs [N,C]): the means of SSIM and of its contrast-structure factor over the valid (H-10) x (W-10) map of the
+    channel-last pair x, y [N,H,W,C] (11-tap Gaussian window, sigma 1.5).  Two launches, no atomics: bit-identical from run to run."""
+    lib = _lib.load()
+    x, y, N, H, W, Cn = _ssim_images(x, y, flag)
+    out = torch.empty(N, Cn, 2, device=x.device, dtype=torch.float32)
+    nbytes = int(lib.na_ssim_workspace_bytes(N, H, W, Cn))
+    ws = torch.empty(max(nbytes // 4, 1), device=x.device, dtype=torch.float32)
+    check(lib.na_ssim(_ptr(x), _ptr(y), N, H, W, Cn, float(data_range), _ptr(out), _ptr(ws), nbytes, _stream()))
+    return out[..., 0], out[..., 1]
+
+
+def ssim_backward(x: torch.Tensor, y: torch.Tensor, g: torch.Tensor, data_range: float = 1.0, flag: str = "ops.ssim") -> torch.Tensor:
+    """g_x [N,H,W,C]: the gradient of sum g[n,c] ssim[n,c] w.r.t. x (y takes none); one launch, every element written once"""
+    lib = _lib.load()
+    x, y, N, H, W, Cn = _ssim_images(x, y, flag)
+    g = _f32(g, "g")
+    if tuple(g.shape) != (N, Cn):
+        raise ValueError(f"g must be [N,C] = {(N, Cn)}, got {tuple(g.shape)}")
+    out = torch.empty_like(x)
+    check(lib.na_ssim_backward(_ptr(x), _ptr(y), _ptr(g), N, H, W, Cn, float(data_range), _ptr(out), _stream()))
+    return out
+
+
+def image_halve(x: torch.Tensor, y: Optional[torch.Tensor] = None, flag: str = "ops.image_halve"):
+    """F.avg_pool2d(kernel 2, padding (H % 2, W % 2)) of channel-last images [N,H,W,C] -> [N, H // 2 + H % 2, W // 2 + W % 2, C]; with y
+    both images in ONE launch -> (x', y')"""
+    lib = _lib.load()
+    if not x.is_cuda or (y is not None and not y.is_cuda):
+        raise NotImplementedError(f"{flag} runs on the GPU only: the 2 x 2 pooling between MS-SSIM's scales is a HIP kernel (DESIGN.md 3r)")
+    if x.dim() != 4 or (y is not None and y.shape != x.shape):
+        raise ValueError(f"{flag}: channel-last images [N,H,W,C] of one shape, got {tuple(x.shape)}" + ("" if y is None else f" and {tuple(y.shape)}"))
+    x = _f32(x, "x")
+    y = None if y is None else _f32(y, "y")
+    N, H, W, Cn = x.shape
+    if not 1 <= Cn <= 4:
+        raise ValueError(f"{flag}: {Cn} channels, 1 .. 4 have a kernel")
+    ox = torch.empty(N, H // 2 + H % 2, W // 2 + W % 2, Cn, device=x.device, dtype=torch.float32)
+    oy = None if y is None else torch.empty_like(ox)
+    check(lib.na_image_halve(_ptr(x), _ptr(y), N, H, W, Cn, _ptr(ox), _ptr(oy), _stream()))
+    return ox if y is None else (ox, oy)
+
+
+def ms_ssim_combine(vals: torch.Tensor, weights=MS_SSIM_WEIGHTS) -> torch.Tensor:
+    """[N,C] = prod_i relu(vals[i]) ** weights[i] of the per-scale values vals [5,N,C] (cs of scales 0 .. 3, ssim of scale 4): plain torch
+    on whatever device and dtype vals has, so a host test can feed it reference sums"""
+    if vals.dim() != 3 or vals.shape[0] != len(weights):
+        raise ValueError(f"vals must be [{len(weights)},N,C], got {tuple(vals.shape)}")
+    w = torch.tensor(weights, dtype=vals.dtype, device=vals.device)
+    return torch.prod(torch.relu(vals) ** w[:, None, None], dim=0)
+
+
+def ms_ssim_check_size(H: int, W: int, flag: str = "ops.ms_ssim"):
+    if min(H, W) <= MS_SSIM_MIN_SIDE:
+        raise ValueError(f"{flag}: image size should be larger than {MS_SSIM_MIN_SIDE} due to the {len(MS_SSIM_WEIGHTS) - 1} downsamplings "
+                         f"in ms-ssim, got {H} x {W}")
+
+
+def ms_ssim(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, flag: str = "ops.ms_ssim") -> torch.Tensor:
+    """[N,C] MS-SSIM of the channel-last pair x, y [N,H,W,C], min(H, W) > 160: five scales, image_halve between them, cs of scales
+    0 .. 3 and ssim of scale 4 through relu, weighted geometric mean.  A metric: no backward."""
+    if x.dim() == 4:
+        ms_ssim_check_size(x.shape[1], x.shape[2], flag)
+    vals = []
+    with torch.no_grad():
+        for i in range(len(MS_SSIM_WEIGHTS)):
+            s, cs = ssim(x, y, data_range, flag)
+            if i < len(MS_SSIM_WEIGHTS) - 1:
+                vals.append(cs)
+                x, y = image_halve(x, y, flag)
+            else:
+                vals.append(s)
+        return ms_ssim_combine(torch.stack(vals, dim=0))

@@ -7,7 +7,8 @@
 seeds, loads the dataset (loaders.py), builds the model through the registries, trains (train.py), renders the test set
 with the fused kernels and writes `results.txt` in the reference's format (runner.py:977-995) plus `test_NNN.png`
 (expected | rendered, side by side; with `--depth-images`, `--flow-map`, `--rigidity-map` the maps' panels behind them) and, with
-`--render-over-time CAM`, `time_NNN.png` for a sweep of times through a dynamic model (RGBA with `--with-alpha`).  Flags outside the hot path are rejected by argparse rather than ignored."""
+`--render-over-time CAM`, `time_NNN.png` for a sweep of times through a dynamic model (RGBA with `--with-alpha`); with `--msssim-loss` the
+reference's `ms-ssim` line ends the summary and `results.txt`.  Flags outside the hot path are rejected by argparse rather than ignored."""
 import os
 import sys
 
@@ -116,11 +117,14 @@ def main(argv=None):
         except ImportError:
             pass
     s = summary("", res["test_psnr"])
-    print(s)
+    # --msssim-loss (runner.py:985-990): the reference's line behind the summary, and at the end of results.txt
+    ms = f"\nms-ssim {res['test_msssim']:.03f}" if res.get("test_msssim") is not None else ""
+    print(s + ms)
     with open(os.path.join(outdir, "results.txt"), "w") as f:
         f.write(s)
         for l in lines:
             f.write("\n" + l)
+        f.write(ms)
     if args.render_over_time >= 0:
         write_time_sweep(args, res, outdir)
     if save:

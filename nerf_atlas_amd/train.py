@@ -1,5 +1,5 @@
 """Training and evaluation loops with the reference's recipe (runner.py:609-850 train, :855-995 test,
-:1221-1322 main), restricted to what the five hot-path configs use: l2/l1/rmse loss in RGB, Adam(eps 1e-7) with the
+:1221-1322 main), restricted to what the five hot-path configs use: l2/l1/rmse loss in RGB and `--loss-fns ssim`, Adam(eps 1e-7) with the
 cosine schedule, random crops/views from Python's `random`, pixel jitter 0.1, stratified sampling and density noise
 in training mode, `--volsdf-scale-decay`, `--delta-x-decay`, `--offset-decay`, `--sdf-eikonal` (SDF normals by forward-mode
 tangents through the MLP), `--smooth-normals` in the reference's default epsilon-perturbation form (`--smooth-eps`,
@@ -7,7 +7,7 @@ tangents through the MLP), `--smooth-normals` in the reference's default epsilon
 (forward-mode divergence estimate), `--voxel-tv-sigma` / `--voxel-tv-rgb` (total variation of NeRFVoxel's grids) and this build's
 `--voxel-upsample ITER:RESO`; over `--dyn-model voxel` also `--voxel-tv-bezier` / `--voxel-tv-rigidity`; `--smooth-normals --smooth-eps 0` (double backward) raises.
 The test loop also renders the maps of `--depth-images` / `--flow-map` / `--rigidity-map` (render.render_frame_maps; one launch per tile for
-the voxel D-NeRF); `--render-over-time` and `--with-alpha` are read by runner.main.
+the voxel D-NeRF) and, with `--msssim-loss`, computes SSIM per view and MS-SSIM of the test set (HIP kernels); `--render-over-time` and `--with-alpha` are read by runner.main.
 
 Every forward and backward is a HIP kernel (nerf_atlas_amd/autograd.py); the parameter update is the reference's table of torch.optim
 classes (`--opt-kind adam | sgd | adamw | rmsprop`, `--decay`), each with its step as one HIP launch (load_optim below).
@@ -49,12 +49,23 @@ DEFAULTS = dict(
     voxel_refl_order=None,  # this build's flag: order K (0..4) of the per-voxel pos-linear-view head, the reference's hard-coded 4
     depth_images=False, flow_map=False, rigidity_map=False, with_alpha=False,  # runner.py:360-392: maps next to the test frames
     render_over_time=-1, render_over_time_steps=100, render_over_time_end_sec=1.0,  # runner.py:252-261: a time sweep of one test camera
+    msssim_loss=False,  # runner.py:359, :985-990: report ms-ssim next to the PSNR summary
 )
+
+def ssim_loss(x, ref):
+    """--loss-fns ssim: 1 - mean over (n, c) of SSIM of the [B,h,w,3] crop against the label (ag.SSIMFn: HIP forward and backward).
+    The reference's entry (runner.py:472, src/utils.py:186-188) hands the channel-last crop to a channel-first library and minimises
+    the similarity itself; this is the intended dissimilarity over image channels."""
+    if x.dim() != 4 or min(x.shape[1], x.shape[2]) < 11:
+        raise ValueError(f"--loss-fns ssim needs a crop of at least 11 x 11 pixels (the SSIM window), got {tuple(x.shape)}: raise --crop-size")
+    return 1 - ag.SSIMFn.apply(x, ref, "--loss-fns ssim").mean()
+
 
 loss_map = {
     "l2": F.mse_loss,
     "l1": F.l1_loss,
     "rmse": lambda x, ref: F.mse_loss(x, ref).clamp(min=1e-10).sqrt(),
+    "ssim": ssim_loss,
 }
 
 
@@ -647,6 +658,26 @@ def test(model, cam, labels, args):
     return psnrs, gots
 
 
+def test_similarity(gots, labels):
+    """--msssim-loss (runner.py:985-990, src/utils.py:190-195): (SSIM per view, MS-SSIM of the test set or None).  Both are means over
+    the channels of a view; MS-SSIM is one float, the mean over views and channels as the reference's size_average computes it.  Frames
+    whose smaller side is 160 or less print `msssim failed: <reason>` and leave None, as the reference's try / except does."""
+    from . import ops
+    if type(labels) is tuple:
+        labels = labels[0]
+    ssims, ms = [], []
+    for got, exp in zip(gots, labels):  # (a view at a time: the test set of a scene does not fit twice next to the model)
+        x, y = got[None, ..., :3], exp[None, ..., :3].to(got.device)
+        ssims.append(float(ops.ssim(x, y, flag="--msssim-loss")[0].mean()))
+        if ms is not None:
+            try:
+                ms.append(float(ops.ms_ssim(x, y, flag="--msssim-loss").mean()))
+            except ValueError as e:
+                print(f"msssim failed: {e}")
+                ms = None
+    return ssims, (None if not ms else float(np.mean(ms)))
+
+
 def fit(args, device="cuda", replay_reference_rng=False, init=None, on_iter=None):
     """runner.main() (:1221-1322): seed, load the training set, build model + optimiser + schedule, train, load the
     test set, evaluate.  `init(model)` may overwrite the initial parameters (parity runs use procedural weights);
@@ -684,7 +715,11 @@ def fit(args, device="cuda", replay_reference_rng=False, init=None, on_iter=None
     if args.test_white_bg:
         model.set_bg("white")
     psnrs, gots = test(model, test_cam, test_labels, args)
-    return dict(model=model, losses=losses, reg_terms=list(getattr(train, "last_reg_terms", [])),
+    extra = {}
+    if getattr(args, "msssim_loss", False):
+        with torch.no_grad():
+            extra["test_ssim"], extra["test_msssim"] = test_similarity(gots, test_labels)
+    return dict(extra, model=model, losses=losses, reg_terms=list(getattr(train, "last_reg_terms", [])),
                 tv_terms=[[float(v) for v in row] for row in getattr(train, "last_tv_terms", [])],
                 ffjord_terms=[float(v) for v in getattr(train, "last_ffjord_terms", [])],
                 len_terms=[[float(v) for v in row] for row in getattr(train, "last_len_terms", [])], test_psnr=psnrs, test_psnr_mean=float(np.mean(psnrs)), frames=gots,
