@@ -842,6 +842,41 @@ int na_voxel_plv_render(const float* rays, const float* pts, int64_t R, const fl
                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * NeRFVoxel with the per-voxel spherical-harmonic colour head (SphericalHarmonic.to_voxel, src/refl.py:715-722; csrc/voxel_sh.hip): rgb is
+ * [S,S,S,C] with C = 3 (order+1)^2, channel-major -- coefficient k of colour channel c at c (order+1)^2 + k -- order 0..4.  C does not
+ * identify the head (3 is the RGB head's count, 12 the pos-linear-view head's at order 2), so every entry point takes both and returns
+ * NA_EINVAL unless C == 3 (order+1)^2.  Per sample s_c = sum_u w_u sum_k Y_k(d / max(|d|, 1e-12)) rgb[row_u, c (order+1)^2 + k] with
+ * d = rays[n % R, 3:6]; the colour is act(s_c).  Positions, lookup and memory-safety rule are na_voxel_sample's; each channel block of a
+ * corner's row is contracted with the ray's basis as it arrives (d_uc = Y_0 v, then fma in k order; s_c = s_c + w_u d_uc in corner
+ * order), so no [N, (order+1)^2] or [N, 3, (order+1)^2] array exists in either direction.  With C % 4 == 0 (orders 1 and 3) rows are read
+ * 16 bytes at a time: rgb must then be 16-byte aligned (else NA_EINVAL); raw and g_raw always.
+ * na_voxel_sh_sample               raw [T*R,4] = [density | s_r s_g s_b], before any activation: the RGB head's layout.
+ * na_voxel_sh_sample_backward      g_densities [S^3] += , g_rgb [S^3,C] += (zeroed by the caller): corner u of sample n receives
+ *                                  w_u [g_raw[n,0] | (w_u g_raw[n,1+c]) Y_k], 1 + C sums per row.  fp32 atomics by default; under
+ *                                  na_set_deterministic every contribution goes to 2^-40 fixed point on its own (bitwise independent of
+ *                                  the order of the samples; workspace >= 8 (1 + C) S^3 bytes = 159 MB at S = 64, C = 75, else
+ *                                  NA_EWORKSPACE before anything is written).  ..._variant runs scatter variant 1 (whole rows in the
+ *                                  LDS table) or 2 (a pass per colour channel, [density | one channel block] in the table) for
+ *                                  measurements; the plain entry point runs the shipped one of the mode.
+ * na_voxel_sh_sample_backward_pts  g_pts [N,3] for explicit pts [N,3] (N a multiple of R): na_voxel_sample_backward_pts with the
+ *                                  per-corner value g_raw[n,0] densities[row] + sum_c g_raw[n,1+c] d_uc.  A gather, no atomics; a
+ *                                  non-finite coordinate gives a NaN row.
+ * na_voxel_sh_render               the eval route as one launch: the basis once per ray, then per step the lookup, NA_SIG_* act_kind on
+ *                                  s_c and na_composite's arithmetic against NA_BG_BLACK / NA_BG_WHITE; alpha / weights NULL or [T,R];
+ *                                  out [R,3].  Bit for bit the three operators in a row.  bg random: black, then na_sky_random. */
+int na_voxel_sh_sample(const float* pts, const float* rays, int64_t R, const float* ts, int T, const float* densities, const float* rgb,
+                       int S, int C, int order, double grid_radius, float* raw, void* stream);
+int na_voxel_sh_sample_backward(const float* pts, const float* rays, int64_t R, const float* ts, int T, const float* g_raw, int S, int C,
+                                int order, double grid_radius, float* g_densities, float* g_rgb, void* stream);
+int na_voxel_sh_sample_backward_variant(const float* pts, const float* rays, int64_t R, const float* ts, int T, const float* g_raw, int S,
+                                        int C, int order, double grid_radius, float* g_densities, float* g_rgb, int variant, void* stream);
+int na_voxel_sh_sample_backward_pts(const float* pts, const float* rays, int64_t R, int64_t N, const float* densities, const float* rgb,
+                                    const float* g_raw, int S, int C, int order, double grid_radius, float* g_pts, void* stream);
+int na_voxel_sh_render(const float* rays, const float* pts, int64_t R, const float* ts, int T, const float* densities, const float* rgb,
+                       int S, int C, int order, double grid_radius, int act_kind, int bg_kind, float* alpha, float* weights, float* out,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * DynamicNeRFVoxel (src/nerf.py:1526-1586; csrc/dyn_voxel.hip): the deformation of a voxel D-NeRF.  ctrl_pts_grid [S,S,S,3(n-1)] holds
  * control points 1 .. n-1 of a Bezier spline per voxel (control point 0 is zero), rigidity_grid [S,S,S,1] a rigidity logit; both are
  * read by NeRFVoxel's lookup above at the UNWARPED pts [N,3] (same cells, same weights, same memory-safety rule), t [N] is the time of
@@ -888,6 +923,15 @@ int na_dyn_voxel_plv_render(const float* rays, const float* t_ray, int64_t R, co
                             const float* rgb, const float* ctrl_pts_grid, const float* rigidity_grid, int S, int order, int n_ctrl,
                             double grid_radius, int act_kind, int bg_kind, float* out, float* depth, float* acc, float* flow,
                             float* rigidity_map, float* alpha, float* weights, void* stream);
+
+/* na_dyn_voxel_sh_render      na_dyn_voxel_render over a canonical model with the spherical-harmonic colour head of `order` 0 .. 4
+ *                             (rgb [S^3, C], C == 3 (order+1)^2 else NA_EINVAL; 16-byte aligned at orders 1 and 3): same contract and
+ *                             outputs, the canonical step being na_voxel_sh_render's.  The result equals, bit for bit, na_compute_pts ->
+ *                             na_dyn_voxel_warp -> na_voxel_sh_render(pts = warped) -> na_integrate x 4.                             */
+int na_dyn_voxel_sh_render(const float* rays, const float* t_ray, int64_t R, const float* ts, int T, const float* densities,
+                           const float* rgb, const float* ctrl_pts_grid, const float* rigidity_grid, int S, int C, int order, int n_ctrl,
+                           double grid_radius, int act_kind, int bg_kind, float* out, float* depth, float* acc, float* flow,
+                           float* rigidity_map, float* alpha, float* weights, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Operators on a dense channel-last grid [s0,s1,s2,C], 1 <= C <= 32 (NeRFVoxel's densities and rgb; csrc/grid_ops.hip).

@@ -246,6 +246,19 @@ SIGNATURES = {
                                                    C.c_double, c_f32p, C.c_void_p]),
     "na_voxel_plv_render": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
                                       c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "na_voxel_sh_sample": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_double, c_f32p,
+                                     C.c_void_p]),
+    "na_voxel_sh_sample_backward": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, C.c_double, c_f32p,
+                                              c_f32p, C.c_void_p]),
+    "na_voxel_sh_sample_backward_variant": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                      c_f32p, c_f32p, C.c_int, C.c_void_p]),
+    "na_voxel_sh_sample_backward_pts": (C.c_int, [c_f32p, c_f32p, c_i64, c_i64, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
+                                                  C.c_double, c_f32p, C.c_void_p]),
+    "na_voxel_sh_render": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                     C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "na_dyn_voxel_sh_render": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_double, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                         C.c_void_p]),
     "na_dyn_voxel_warp": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, c_f32p, C.c_int, C.c_int, C.c_double, c_f32p, c_f32p, c_f32p,
                                     C.c_void_p]),
     "na_dyn_voxel_warp_backward": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_double,

@@ -592,6 +592,34 @@ class VoxelPlvSampleFn(Function):
         return g_den, g_rgb, None, None, g_pts, None
 
 
+class VoxelShSampleFn(Function):
+    """raw [..., 4] = [density | s_r s_g s_b] of NeRFVoxel's lookup with the spherical-harmonic colour head (ops.voxel_sh_sample);
+    backward scatters into the two grids (ops.voxel_sh_sample_backward).  Like VoxelPlvSampleFn only the positions are saved -- the rays
+    and explicit pts or ts -- and the cells are recomputed; explicit pts that require a gradient get one
+    (ops.voxel_sh_sample_backward_pts, the grids are saved for it), the rays x ts form has no position gradient."""
+
+    @staticmethod
+    def forward(ctx, densities, rgb, order, grid_radius, rays, pts, ts):
+        ctx.grid_radius, ctx.S, ctx.order = grid_radius, densities.shape[0], order
+        ctx.explicit = pts is not None
+        ctx.pts_grad = ctx.explicit and ctx.needs_input_grad[5]
+        ctx.save_for_backward(rays, pts if ctx.explicit else ts, *((densities, rgb) if ctx.pts_grad else ()))
+        return ops.voxel_sh_sample(densities, rgb, order, grid_radius, rays, pts=pts, ts=ts)
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        saved = ctx.saved_tensors
+        rays, pos = saved[0], saved[1]
+        kw = {"pts": pos} if ctx.explicit else {"ts": pos}
+        g_raw = g_raw.contiguous()
+        g_den = g_rgb = g_pts = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            g_den, g_rgb = ops.voxel_sh_sample_backward(g_raw, ctx.S, ctx.order, ctx.grid_radius, rays, **kw)
+        if ctx.pts_grad:
+            g_pts = ops.voxel_sh_sample_backward_pts(g_raw, pos, rays, saved[2], saved[3], ctx.order, ctx.grid_radius)
+        return g_den, g_rgb, None, None, None, g_pts, None
+
+
 class DynVoxelWarpFn(Function):
     """(warped, dp, rigidity) of DynamicNeRFVoxel's deformation (ops.dyn_voxel_warp, one launch); all three are differentiable --
     `warped` feeds the canonical lookup, `dp` and `rigidity` the offset regularisers -- and backward is one scatter-add into the two

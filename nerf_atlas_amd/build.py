@@ -39,6 +39,7 @@ UNITS = [
     ("composite_rayts.hip", [], ""),
     ("voxel.hip", [], ""),
     ("voxel_plv.hip", [], ""),
+    ("voxel_sh.hip", [], ""),
     ("dyn_voxel.hip", [], ""),
     ("dyn_voxel_render.hip", [], ""),
     ("spline_len.hip", [], ""),

@@ -22,7 +22,8 @@
 // C = 3), 0 .. 4 the pos-linear-view head of that order (na_dyn_voxel_plv_render, C = 3 + (K+1)^2: the ray's basis once per thread and
 // the linear scale).  Lookup, alpha and the walk are plv_render_kernel<K>'s own functions (vox_gather<K>, vox_alpha, VoxWalk), so the
 // result equals the composition over na_voxel_render / na_voxel_plv_render bit for bit; the deformation is na_dyn_voxel_warp's
-// (dv_gather, dv_spline).
+// (dv_gather, dv_spline).  The tag SH is voxel_plv.h's: the per-voxel spherical-harmonic colour head (na_dyn_voxel_sh_render,
+// C = 3 (K+1)^2; the step of na_voxel_sh_render: no linear scale).
 #include "dyn_voxel_spline.h"
 #include "voxel_plv.h"
 
@@ -46,7 +47,7 @@ struct DvrMaps {
   float* weights;   // [T,R]
 };
 
-template <int NC, int K>
+template <int NC, int K, bool SH = false>
 __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const float* __restrict__ rays, const float* __restrict__ t_ray,
                                                                         const float* __restrict__ ts, int T, int64_t R, VoxGrid g,
                                                                         const float* __restrict__ den, const float* __restrict__ rgb,
@@ -81,11 +82,11 @@ __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const fl
 #pragma unroll
         for (int a = 0; a < 3; ++a) rdp[a] = dp[a] * rg;  // (rigid_dp: the product formed first, once)
         // ... the canonical lookup at the warped point, and plv_render_kernel's step up to the running product
-        vox_gather<K>(px + rdp[0], py + rdp[1], pz + rdp[2], g, den, rgb, Y, raw);
+        vox_gather<K, SH>(px + rdp[0], py + rdp[1], pz + rdp[2], g, den, rgb, Y, raw);
         const float a = vox_alpha(raw[0], ts, t, T, nrm);
         if (live && m.alpha != nullptr) m.alpha[(int64_t)t * R + r] = a;
         float c0 = apply_sigmoid_kind(raw[1], act_kind), c1 = apply_sigmoid_kind(raw[2], act_kind), c2 = apply_sigmoid_kind(raw[3], act_kind);
-        if constexpr (K >= 0) {
+        if constexpr (K >= 0 && !SH) {
           const float lin = plv_scale(raw[4]);
           c0 = lin * c0; c1 = lin * c1; c2 = lin * c2;
         }
@@ -125,8 +126,8 @@ __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const fl
 
 using namespace na;
 
-// `order` -1: the per-voxel RGB head (C = 3); 0 .. 4: the pos-linear-view head
-static int dyn_voxel_render_any(const char* who, int order, const float* rays, const float* t_ray, int64_t R, const float* ts, int T,
+// `order` -1: the per-voxel RGB head (C = 3); 0 .. 4: the pos-linear-view head, or with `sh` the spherical-harmonic colour head
+static int dyn_voxel_render_any(const char* who, int order, bool sh, const float* rays, const float* t_ray, int64_t R, const float* ts, int T,
                                 const float* densities, const float* rgb, const float* ctrl_pts_grid, const float* rigidity_grid, int S,
                                 int n_ctrl, double grid_radius, int act_kind, int bg_kind, float* out, float* depth, float* acc,
                                 float* flow, float* rigidity_map, float* alpha, float* weights, void* stream) {
@@ -137,20 +138,34 @@ static int dyn_voxel_render_any(const char* who, int order, const float* rays, c
   NA_DVR_PTR(rays); NA_DVR_PTR(t_ray); NA_DVR_PTR(ts); NA_DVR_PTR(densities); NA_DVR_PTR(rgb); NA_DVR_PTR(ctrl_pts_grid);
   NA_DVR_PTR(rigidity_grid); NA_DVR_PTR(out);
 #undef NA_DVR_PTR
-  NA_REQUIRE(order < 0 || ((order + 1) * (order + 1) + 3) % 4 != 0 || ((uintptr_t)rgb & 15) == 0, NA_EINVAL,
+  const int row = order < 0 ? 3 : sh ? 3 * (order + 1) * (order + 1) : 3 + (order + 1) * (order + 1);  // floats of a grid row
+  NA_REQUIRE(order < 0 || row % 4 != 0 || ((uintptr_t)rgb & 15) == 0, NA_EINVAL,
              "%s: rgb must be 16-byte aligned at order %d", who, order);
   const VoxGrid g = vox_grid(S, grid_radius);
   const DvrMaps m{depth, acc, flow, rigidity_map, alpha, weights};
-#define NA_DVR_LAUNCH_K(NC, K)                                                                                                             \
-  hipLaunchKernelGGL((dyn_voxel_render_kernel<NC, K>), dim3(grid_for(R, NA_DVR_BLOCK / NA_DVR_LANES)), dim3(NA_DVR_BLOCK), 0, (hipStream_t)stream, \
-                     rays, t_ray, ts, T, R, g, densities, rgb, ctrl_pts_grid, rigidity_grid, act_kind, bg_kind, out, m)
+#define NA_DVR_LAUNCH_KS(NC, K, SH)                                                                                                        \
+  hipLaunchKernelGGL((dyn_voxel_render_kernel<NC, K, SH>), dim3(grid_for(R, NA_DVR_BLOCK / NA_DVR_LANES)), dim3(NA_DVR_BLOCK), 0,                  \
+                     (hipStream_t)stream, rays, t_ray, ts, T, R, g, densities, rgb, ctrl_pts_grid, rigidity_grid, act_kind, bg_kind, out, m)
+#define NA_DVR_LAUNCH_K(NC, K) NA_DVR_LAUNCH_KS(NC, K, false)
+#define NA_DVR_LAUNCH_S0(NC) NA_DVR_LAUNCH_KS(NC, 0, true)
+#define NA_DVR_LAUNCH_S1(NC) NA_DVR_LAUNCH_KS(NC, 1, true)
+#define NA_DVR_LAUNCH_S2(NC) NA_DVR_LAUNCH_KS(NC, 2, true)
+#define NA_DVR_LAUNCH_S3(NC) NA_DVR_LAUNCH_KS(NC, 3, true)
+#define NA_DVR_LAUNCH_S4(NC) NA_DVR_LAUNCH_KS(NC, 4, true)
 #define NA_DVR_LAUNCH_M1(NC) NA_DVR_LAUNCH_K(NC, -1)
 #define NA_DVR_LAUNCH_0(NC) NA_DVR_LAUNCH_K(NC, 0)
 #define NA_DVR_LAUNCH_1(NC) NA_DVR_LAUNCH_K(NC, 1)
 #define NA_DVR_LAUNCH_2(NC) NA_DVR_LAUNCH_K(NC, 2)
 #define NA_DVR_LAUNCH_3(NC) NA_DVR_LAUNCH_K(NC, 3)
 #define NA_DVR_LAUNCH_4(NC) NA_DVR_LAUNCH_K(NC, 4)
-  switch (order) {
+  if (sh) switch (order) {
+    case 0: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_S0) break;
+    case 1: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_S1) break;
+    case 2: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_S2) break;
+    case 3: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_S3) break;
+    default: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_S4) break;
+  }
+  else switch (order) {
     case 0: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_0) break;
     case 1: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_1) break;
     case 2: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_2) break;
@@ -171,7 +186,7 @@ int na_dyn_voxel_render(const float* rays, const float* t_ray, int64_t R, const 
   NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED,
              "na_dyn_voxel_render: n_ctrl %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", n_ctrl);
   if (int rc = vox_check_grid("na_dyn_voxel_render", S, C, grid_radius)) return rc;
-  return dyn_voxel_render_any("na_dyn_voxel_render", -1, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid, S, n_ctrl,
+  return dyn_voxel_render_any("na_dyn_voxel_render", -1, false, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid, S, n_ctrl,
                               grid_radius, act_kind, bg_kind, out, depth, acc, flow, rigidity_map, alpha, weights, stream);
 }
 
@@ -183,7 +198,20 @@ int na_dyn_voxel_plv_render(const float* rays, const float* t_ray, int64_t R, co
   NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED,
              "na_dyn_voxel_plv_render: n_ctrl %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", n_ctrl);
   if (int rc = vox_plv_check_grid("na_dyn_voxel_plv_render", S, order, grid_radius)) return rc;
-  return dyn_voxel_render_any("na_dyn_voxel_plv_render", order, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid, S,
+  return dyn_voxel_render_any("na_dyn_voxel_plv_render", order, false, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid, S,
+                              n_ctrl, grid_radius, act_kind, bg_kind, out, depth, acc, flow, rigidity_map, alpha, weights, stream);
+}
+
+int na_dyn_voxel_sh_render(const float* rays, const float* t_ray, int64_t R, const float* ts, int T, const float* densities,
+                           const float* rgb, const float* ctrl_pts_grid, const float* rigidity_grid, int S, int C, int order, int n_ctrl,
+                           double grid_radius, int act_kind, int bg_kind, float* out, float* depth, float* acc, float* flow,
+                           float* rigidity_map, float* alpha, float* weights, void* stream) {
+  NA_REQUIRE(T >= 1 && R >= 0, NA_EINVAL, "na_dyn_voxel_sh_render: bad shape T=%d R=%lld", T, (long long)R);
+  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED,
+             "na_dyn_voxel_sh_render: n_ctrl %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", n_ctrl);
+  if (int rc = vox_plv_check_grid("na_dyn_voxel_sh_render", S, order, grid_radius)) return rc;
+  NA_REQUIRE(C == 3 * (order + 1) * (order + 1), NA_EINVAL, "na_dyn_voxel_sh_render: C = %d, order %d holds 3 (order + 1)^2", C, order);
+  return dyn_voxel_render_any("na_dyn_voxel_sh_render", order, true, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid, S,
                               n_ctrl, grid_radius, act_kind, bg_kind, out, depth, acc, flow, rigidity_map, alpha, weights, stream);
 }
 

@@ -8,6 +8,14 @@
 // basis, no sh output and no linear scale: `if constexpr (K >= 0)` leaves the RGB head's own code.  The ray of sample n is n % R.
 // Also here, for dyn_voxel_render.hip as well: the lookup (vox_gather) and one compositing step (vox_alpha, VoxWalk).
 //
+// A third head rides on the same kernels under the tag SH (entry points in voxel_sh.hip): the per-voxel spherical-harmonic
+// colour (SphericalHarmonic.to_voxel, src/refl.py:715-722, the Plenoxels model).  The grid row is 3 channel blocks of NK = (K+1)^2
+// coefficients, C = 3 NK floats, coefficient k of colour channel c at c NK + k, and
+//     rgb_c = act(s_c),   s_c = sum_u w_u sum_k Y_k(normalize(view)) row_u[c NK + k].
+// Each block is contracted as it arrives, with the association below (d_uc for row_u[c NK ..], then s_c = s_c + w_u d_uc), so a block that
+// equals a pos-linear-view row's coefficients gives that head's s bit for bit; the outputs are v[0] = density, v[1..3] = s_c: the RGB
+// head's raw [N, 4], with no sh output and no linear scale.
+//
 // ASSOCIATION (one function for every route; tests/voxel_plv_ref.py derives the bound from these counts):
 //     d_u = fma(Y_k, row_u[3 + k], d_u) for k = 1 .. NK-1 in k order, from d_u = Y_0 * row_u[3]      (coefficients first: NK roundings)
 //     s   = s + w_u * d_u for the corners u = 0 .. 7 in corner order, from s = 0                     (a product and a sum per corner)
@@ -23,10 +31,10 @@
 
 namespace na {
 
-template <int K> struct Plv {
-  static constexpr int NK = (K + 1) * (K + 1);  // coefficients per voxel (none at K = -1)
-  static constexpr int C = 3 + NK;              // floats per grid row: 3 | 4, 7, 12, 19, 28
-  static constexpr bool ALIGNED = C % 4 == 0;   // rows of 4 C bytes are 16-byte aligned for K = 0, 2, 4 only
+template <int K, bool SH = false> struct Plv {
+  static constexpr int NK = (K + 1) * (K + 1);  // coefficients per voxel and channel (none at K = -1)
+  static constexpr int C = SH ? 3 * NK : 3 + NK;  // floats per grid row: 3 | 4, 7, 12, 19, 28 | SH: 3, 12, 27, 48, 75
+  static constexpr bool ALIGNED = C % 4 == 0;   // rows of 4 C bytes are 16-byte aligned for K = 0, 2, 4 only (SH: K = 1, 3)
 };
 
 // one grid row into registers: 16-byte loads where every row is 16-byte aligned, 4-byte loads otherwise
@@ -56,6 +64,42 @@ template <int K> __device__ __forceinline__ float plv_contract(const float (&r)[
   }
 }
 
+// vox_row for a corner loop that stays a loop (the SH head's rows are too wide to unroll over): the cell's ids are read once, in front
+// of the loop, and corner u selects among scalars -- a run-time index into the cell's arrays would put the cell into scratch
+struct VoxRows {
+  int64_t x0, x1, y0, y1, z0, z1;
+  __device__ __forceinline__ VoxRows(const VoxCell& c, int S)
+      : x0((int64_t)c.ix[0] * S * S), x1((int64_t)c.ix[1] * S * S), y0((int64_t)c.iy[0] * S), y1((int64_t)c.iy[1] * S), z0(c.iz[0]), z1(c.iz[1]) {}
+  // (by value: `bit ? x1 : x0` on the members is an lvalue, a select between two ADDRESSES, and the struct stays in memory)
+  static __device__ __forceinline__ int64_t pick(bool hi, int64_t a, int64_t b) { return hi ? b : a; }
+  __device__ __forceinline__ int64_t operator()(int u) const { return pick(u & 1, x0, x1) + pick(u & 2, y0, y1) + pick(u & 4, z0, z1); }
+};
+
+// SH head: d[c] = sum_k Y_k q[c NK + k] for the three channel blocks of one grid row, each block loaded (16 bytes at a time where the
+// rows are aligned: NK is then a multiple of 4) and contracted on its own with plv_contract's association -- a row never sits in
+// registers whole
+template <int K> __device__ __forceinline__ void sh_contract_row(const float* __restrict__ q, const float (&Y)[SH_MAX_K], float (&d)[3]) {
+  constexpr int NK = Plv<K, true>::NK;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float r[NK];
+    if constexpr (Plv<K, true>::ALIGNED) {
+#pragma unroll
+      for (int i = 0; i < NK / 4; ++i) {
+        const float4 v = ((const float4*)(q + c * NK))[i];
+        r[4 * i] = v.x; r[4 * i + 1] = v.y; r[4 * i + 2] = v.z; r[4 * i + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < NK; ++k) r[k] = q[c * NK + k];
+    }
+    float a = Y[0] * r[0];
+#pragma unroll
+    for (int k = 1; k < NK; ++k) a = fmaf(Y[k], r[k], a);
+    d[c] = a;
+  }
+}
+
 // the basis of ray r (dirs = rays[:, 3:6], un-normalised: sh_basis normalises with F.normalize's eps like na_sh_shade)
 template <int K> __device__ __forceinline__ void plv_ray_basis(const float* __restrict__ rays, int64_t r, float (&Y)[SH_MAX_K]) {
   if constexpr (K >= 0) {
@@ -65,24 +109,41 @@ template <int K> __device__ __forceinline__ void plv_ray_basis(const float* __re
 }
 
 // v[0] = density, v[1..3] = colour parameters, v[4] = s (K >= 0): the per-sample lookup of every kernel.  Sums over the 8 corners
-// in corner order (the S = 64 grid of the RGB head is 4 MiB and stays in the L2 / Infinity Cache).
-template <int K>
+// in corner order (the S = 64 grid of the RGB head is 4 MiB and stays in the L2 / Infinity Cache).  SH: v[1..3] = s_c, v[4] unused.
+template <int K, bool SH = false>
 __device__ __forceinline__ void vox_gather(float px, float py, float pz, const VoxGrid& g, const float* __restrict__ den,
                                            const float* __restrict__ rgb, const float (&Y)[SH_MAX_K], float v[5]) {
   const VoxCell c = vox_cell(px, py, pz, g);
   v[0] = v[1] = v[2] = v[3] = v[4] = 0.f;
+  if constexpr (SH) {
+    // the corners as a real loop, one row in flight: unrolled, all 8 rows' loads are hoisted (600 registers at K = 4) and the render
+    // kernels spill
+    const VoxRows rows(c, g.S);
+#pragma unroll 1
+    for (int u = 0; u < 8; ++u) {
+      const int64_t row = rows(u);
+      const float w = vox_weight(c, u);
+      float d[3];
+      sh_contract_row<K>(rgb + row * Plv<K, true>::C, Y, d);
+      v[0] = v[0] + w * den[row];
+      v[1] = v[1] + w * d[0];
+      v[2] = v[2] + w * d[1];
+      v[3] = v[3] + w * d[2];
+    }
+  } else {
 #pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int64_t row = vox_row(c, u, g.S);
-    const float w = vox_weight(c, u);
-    float r[Plv<K>::C];
-    plv_load_row<K>(rgb + row * Plv<K>::C, r);
-    const float d = plv_contract<K>(r, Y);
-    v[0] = v[0] + w * den[row];
-    v[1] = v[1] + w * r[0];
-    v[2] = v[2] + w * r[1];
-    v[3] = v[3] + w * r[2];
-    if constexpr (K >= 0) v[4] = v[4] + w * d;
+    for (int u = 0; u < 8; ++u) {
+      const int64_t row = vox_row(c, u, g.S);
+      const float w = vox_weight(c, u);
+      float r[Plv<K>::C];
+      plv_load_row<K>(rgb + row * Plv<K>::C, r);
+      const float d = plv_contract<K>(r, Y);
+      v[0] = v[0] + w * den[row];
+      v[1] = v[1] + w * r[0];
+      v[2] = v[2] + w * r[1];
+      v[3] = v[3] + w * r[2];
+      if constexpr (K >= 0) v[4] = v[4] + w * d;
+    }
   }
 }
 
@@ -137,7 +198,7 @@ struct VoxWalk {
 // ------------------------------------------------------------------------------------ gather
 // one thread per sample, one 16-byte row store (+ sh [N] = s with the view-dependent head).  The RGB head's instantiation is pinned to
 // the 6 waves per SIMD it had as a kernel of its own (72 VGPRs; left alone the allocator takes 91 for the same instructions).
-template <int K>
+template <int K, bool SH = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K < 0 ? 6 : 1, K < 0 ? 6 : 8)))
 void plv_sample_kernel(const float* __restrict__ pts, const float* __restrict__ rays, const float* __restrict__ ts, int64_t R, int64_t N,
                        VoxGrid g, const float* __restrict__ den, const float* __restrict__ rgb, float* __restrict__ raw,
@@ -146,21 +207,21 @@ void plv_sample_kernel(const float* __restrict__ pts, const float* __restrict__ 
     float Y[SH_MAX_K], px, py, pz, v[5];
     plv_ray_basis<K>(rays, n % R, Y);
     vox_position(pts, rays, ts, R, n, px, py, pz);
-    vox_gather<K>(px, py, pz, g, den, rgb, Y, v);
+    vox_gather<K, SH>(px, py, pz, g, den, rgb, Y, v);
     *(float4*)(raw + n * 4) = make_float4(v[0], v[1], v[2], v[3]);
-    if constexpr (K >= 0) sh[n] = v[4];
+    if constexpr (K >= 0 && !SH) sh[n] = v[4];
   }
 }
 
 // ------------------------------------------------------------------------------------ gather: gradient w.r.t. the positions
 // g_pts[n, a] = (1 / voxel_len) sum_u (dw_u / dxyz_a) v_u with the per-corner value
 //   v_u = ((g_raw[n, 0] den[row_u] + g_raw[n, 1] rgb[row_u, 0]) + g_raw[n, 2] rgb[row_u, 1]) + g_raw[n, 3] rgb[row_u, 2]
-//         (+ g_sh[n] sum_k Y_k rgb[row_u, 3 + k] with the view-dependent head),
+//         (+ g_sh[n] sum_k Y_k rgb[row_u, 3 + k] with the view-dependent head; SH: d_uc in the place of rgb[row_u, c], no g_sh),
 // g_a <- g_a + (dw_u / dxyz_a) v_u in corner order, then the division.  In the reference only xyz = (p - centre of corner 0) /
 // voxel_len depends on p -- the floors and both clamps carry no gradient -- so the derivative is the one of the polynomial this cell's
 // weights are (vox_dweight), inside the grid and in the extrapolated region alike.  A gather (no atomics), one thread per sample.
 // A non-finite coordinate makes the whole row NaN (one NaN fraction alone would leave the other two axes' sums finite).
-template <int K>
+template <int K, bool SH = false>
 __global__ __launch_bounds__(256) void plv_backward_pts_kernel(const float* __restrict__ pts, const float* __restrict__ rays, int64_t R,
                                                                int64_t N, VoxGrid g, const float* __restrict__ den,
                                                                const float* __restrict__ rgb, const float* __restrict__ g_raw,
@@ -171,15 +232,22 @@ __global__ __launch_bounds__(256) void plv_backward_pts_kernel(const float* __re
     const VoxCell c = vox_cell(pts[n * 3], pts[n * 3 + 1], pts[n * 3 + 2], g);
     const float4 gv = *(const float4*)(g_raw + n * 4);
     float gs = 0.f;
-    if constexpr (K >= 0) gs = g_sh[n];
+    if constexpr (K >= 0 && !SH) gs = g_sh[n];
     float gx = 0.f, gy = 0.f, gz = 0.f;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int64_t row = vox_row(c, u, g.S);
-      float q[Plv<K>::C], dx, dy, dz;
-      plv_load_row<K>(rgb + row * Plv<K>::C, q);
-      float v = ((gv.x * den[row] + gv.y * q[0]) + gv.z * q[1]) + gv.w * q[2];
-      if constexpr (K >= 0) v = v + gs * plv_contract<K>(q, Y);
+      float dx, dy, dz, v;
+      if constexpr (SH) {
+        float d[3];
+        sh_contract_row<K>(rgb + row * Plv<K, true>::C, Y, d);
+        v = ((gv.x * den[row] + gv.y * d[0]) + gv.z * d[1]) + gv.w * d[2];
+      } else {
+        float q[Plv<K>::C];
+        plv_load_row<K>(rgb + row * Plv<K>::C, q);
+        v = ((gv.x * den[row] + gv.y * q[0]) + gv.z * q[1]) + gv.w * q[2];
+        if constexpr (K >= 0) v = v + gs * plv_contract<K>(q, Y);
+      }
       vox_dweight(c, u, dx, dy, dz);
       gx = gx + dx * v;
       gy = gy + dy * v;
@@ -203,11 +271,15 @@ __global__ __launch_bounds__(256) void plv_backward_pts_kernel(const float* __re
 // NA_PLV_SCATTER (voxel_plv.hip) picks the variant na_voxel_plv_sample_backward runs (DESIGN.md 3p has the times of both).
 constexpr int PLV_LDS_BUDGET = 60 * 1024;  // table bytes of a workgroup: two workgroups share a CU's 160 KiB
 
+// rows of a table of `sums` entries of `entry` bytes (and a 4-byte tag) inside the budget: a power of two, 1024 at most
+constexpr int plv_table_rows(int sums, int entry, int r = 1) {
+  return (r * 2 * (sums * entry + 4) <= PLV_LDS_BUDGET && r < 1024) ? plv_table_rows(sums, entry, r * 2) : r;
+}
+
 template <int K, int VARIANT, bool DET> struct PlvTable {
   static constexpr int SUMS = VARIANT == 1 ? 1 + Plv<K>::C : 4;   // sums of a table row
   static constexpr int ENTRY = (DET || VARIANT == 2) ? 8 : 4;     // bytes of a sum
-  static constexpr int rows_for(int r) { return (r * 2 * (SUMS * ENTRY + 4) <= PLV_LDS_BUDGET && r < 1024) ? rows_for(r * 2) : r; }
-  static constexpr int ROWS = rows_for(1);                        // a power of two, 1024 at most
+  static constexpr int ROWS = plv_table_rows(SUMS, ENTRY);
   using type = VoxTable<SUMS, typename std::conditional<ENTRY == 8, unsigned long long, float>::type, ROWS, DET>;
 };
 
@@ -280,12 +352,105 @@ static void plv_launch_backward(unsigned wg, hipStream_t s, const float* pts, co
     hipLaunchKernelGGL((plv_backward_kernel<K, VARIANT, false>), dim3(wg), dim3(256), 0, s, pts, rays, ts, R, N, g, g_raw, g_sh, g_den, g_rgb, fix);
 }
 
+// ------------------------------------------------------------------------------------ scatter-add, SH head
+// Corner u of sample n receives w_u [g_raw[n, 0] | (w_u g_raw[n, 1 + c]) Y_k]: 1 + C = 1 + 3 NK sums per grid row, 76 at K = 4 -- whole
+// rows at the 60 KiB budget leave 128 table rows in fp32 and 64 in fixed point, where the narrower heads have 512 .. 1024.  Two
+// geometries, one kernel body (PASSES x CPP = 3 channel blocks):
+//   variant 1 (ROWS)      one pass, whole rows [density | 3 blocks] in the table
+//   variant 2 (CHANNELS)  three passes over the workgroup's run, one per colour channel, the table holding [density | ONE block]: a third
+//                         of the sums per row buys up to four times the rows (512 / 256 at K = 4), for cells, weights and basis
+//                         computed three times; the density sum rides in pass 0
+// Every sum has one home whatever the geometry, and the deterministic mode adds integers only: the variants agree bit for bit there.
+// NA_SH_SCATTER / NA_SH_SCATTER_DET (voxel_sh.hip) pick the variant of each mode (DESIGN.md 3s has the times of both).
+template <int K, int VARIANT, bool DET> struct ShTable {
+  static constexpr int NK = Plv<K, true>::NK, CPP = VARIANT == 1 ? 3 : 1, PASSES = 3 / CPP;  // channel blocks per pass
+  static constexpr int SUMS = 1 + CPP * NK, ENTRY = DET ? 8 : 4;
+  static constexpr int ROWS = plv_table_rows(SUMS, ENTRY);
+  using type = VoxTable<SUMS, typename std::conditional<DET, unsigned long long, float>::type, ROWS, DET>;
+};
+
+template <int K, int VARIANT, bool DET>
+__global__ __launch_bounds__(256) void sh_backward_kernel(const float* __restrict__ pts, const float* __restrict__ rays,
+                                                          const float* __restrict__ ts, int64_t R, int64_t N, VoxGrid g,
+                                                          const float* __restrict__ g_raw, float* __restrict__ g_den,
+                                                          float* __restrict__ g_rgb, long long* __restrict__ fix) {
+  using Geo = ShTable<K, VARIANT, DET>;
+  using Table = typename Geo::type;
+  constexpr int NK = Geo::NK, C = 3 * NK, CPP = Geo::CPP, SUMS = Geo::SUMS, ROWS = Geo::ROWS;
+  const int64_t S3 = (int64_t)g.S * g.S * g.S;
+  long long* fix_rgb = DET ? fix + S3 : nullptr;
+  long long* fix_den = DET ? fix : nullptr;
+  __shared__ uint32_t tags[ROWS];
+  __shared__ typename Table::Entry vals[ROWS * SUMS];
+  const Table table{tags, vals, fix_den};
+  int64_t n_lo, n_hi;
+  dv_run(N, n_lo, n_hi);
+  for (int pass = 0; pass < Geo::PASSES; ++pass) {
+    const int c0 = pass * CPP;  // first colour channel of this pass
+    // sum e of a table row of this pass: e = 0 density, e = 1 + cc NK + k coefficient k of channel c0 + cc
+    auto add_global = [&](uint32_t id, int e, float v) {
+      if (e == 0) accumulate(g_den, fix_den, (int64_t)id, v);
+      else accumulate(g_rgb, fix_rgb, (int64_t)id * C + c0 * NK + (e - 1), v);
+    };
+    if (pass > 0) __syncthreads();  // (the flush of the pass before has read the table)
+    table.clear();
+    for (int64_t base = n_lo; base < n_hi; base += 256) {
+      const int64_t n = base + threadIdx.x;
+      if (n < n_hi) {
+        float Y[SH_MAX_K], px, py, pz;
+        plv_ray_basis<K>(rays, n % R, Y);
+        vox_position(pts, rays, ts, R, n, px, py, pz);
+        const VoxCell c = vox_cell(px, py, pz, g);
+        const float4 gv = *(const float4*)(g_raw + n * 4);
+        float gc[CPP];
+        if constexpr (CPP == 3) { gc[0] = gv.y; gc[1] = gv.z; gc[2] = gv.w; }
+        else gc[0] = pass == 0 ? gv.y : pass == 1 ? gv.z : gv.w;
+        const VoxRows rows(c, g.S);
+#pragma unroll 1  // (the body is up to 76 table adds)
+        for (int u = 0; u < 8; ++u) {
+          const uint32_t id = (uint32_t)rows(u);
+          const float w = vox_weight(c, u);
+          const int slot = table.find_slot(id);
+          if (pass == 0) {
+            if (slot >= 0) table.add(id, slot, 0, w * gv.x, add_global);
+            else add_global(id, 0, w * gv.x);
+          }
+#pragma unroll
+          for (int cc = 0; cc < CPP; ++cc) {
+            const float wg = w * gc[cc];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+              const float a = wg * Y[k];
+              if (slot >= 0) table.add(id, slot, 1 + cc * NK + k, a, add_global);
+              else add_global(id, 1 + cc * NK + k, a);
+            }
+          }
+        }
+      }
+    }
+    table.flush([&](uint32_t id, int e, typename Table::Entry v) {
+      if (v == 0) return;
+      const int64_t at = e == 0 ? (int64_t)id : (int64_t)id * C + c0 * NK + (e - 1);
+      table.put(e == 0 ? g_den : g_rgb, e == 0 ? fix_den : fix_rgb, at, v);
+    });
+  }
+}
+
+template <int K, int VARIANT>
+static void sh_launch_backward(unsigned wg, hipStream_t s, const float* pts, const float* rays, const float* ts, int64_t R, int64_t N,
+                               VoxGrid g, const float* g_raw, float* g_den, float* g_rgb, long long* fix) {
+  if (fix != nullptr)
+    hipLaunchKernelGGL((sh_backward_kernel<K, VARIANT, true>), dim3(wg), dim3(256), 0, s, pts, rays, ts, R, N, g, g_raw, g_den, g_rgb, fix);
+  else
+    hipLaunchKernelGGL((sh_backward_kernel<K, VARIANT, false>), dim3(wg), dim3(256), 0, s, pts, rays, ts, R, N, g, g_raw, g_den, g_rgb, fix);
+}
+
 // ------------------------------------------------------------------------------------ eval route, one launch
 // One thread per ray walks T in order like composite_kernel (vox_alpha, VoxWalk); the basis is evaluated once per ray and held in
 // registers over the walk.  The rows of U steps are gathered first -- their addresses do not depend on the walk -- so 8 U independent
 // row loads are in flight before the U dependent updates run: 4 steps with the RGB head, 2 / 1 with the wider rows (or the rows in
-// flight leave the registers).
-template <int K>
+// flight leave the registers).  SH: one step, and the colour is the activation of s_c alone.
+template <int K, bool SH = false>
 __global__ __launch_bounds__(64) void plv_render_kernel(const float* __restrict__ rays, const float* __restrict__ pts,
                                                         const float* __restrict__ ts, int T, int64_t R, VoxGrid g,
                                                         const float* __restrict__ den, const float* __restrict__ rgb, int act_kind,
@@ -297,7 +462,7 @@ __global__ __launch_bounds__(64) void plv_render_kernel(const float* __restrict_
     float Y[SH_MAX_K];
     plv_ray_basis<K>(rays, r, Y);
     VoxWalk walk;
-    constexpr int U = K < 0 ? 4 : K <= 1 ? 2 : 1;
+    constexpr int U = K < 0 ? 4 : (K <= 1 && !SH) ? 2 : 1;
     for (int t0 = 0; t0 < T; t0 += U) {
       float raw[U][5];
 #pragma unroll
@@ -305,7 +470,7 @@ __global__ __launch_bounds__(64) void plv_render_kernel(const float* __restrict_
         const int t = t0 + u < T ? t0 + u : T - 1;  // (clamped: the tail gathers the last step again and ignores it)
         float px, py, pz;
         vox_position(pts, rays, ts, R, (int64_t)t * R + r, px, py, pz);
-        vox_gather<K>(px, py, pz, g, den, rgb, Y, raw[u]);
+        vox_gather<K, SH>(px, py, pz, g, den, rgb, Y, raw[u]);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -316,8 +481,8 @@ __global__ __launch_bounds__(64) void plv_render_kernel(const float* __restrict_
           if (alpha_out != nullptr) alpha_out[(int64_t)t * R + r] = a;
           if (weights_out != nullptr) weights_out[(int64_t)t * R + r] = w;
           float lin = 1.0f;
-          if constexpr (K >= 0) lin = plv_scale(raw[u][4]);
-          const auto colour = [&](float p) { return K >= 0 ? lin * apply_sigmoid_kind(p, act_kind) : apply_sigmoid_kind(p, act_kind); };
+          if constexpr (K >= 0 && !SH) lin = plv_scale(raw[u][4]);
+          const auto colour = [&](float p) { return K >= 0 && !SH ? lin * apply_sigmoid_kind(p, act_kind) : apply_sigmoid_kind(p, act_kind); };
           walk.add(w, colour(raw[u][1]), colour(raw[u][2]), colour(raw[u][3]), t == T - 1);
         }
       }

@@ -586,15 +586,31 @@ def random_sample_grid(grid, samples: int = 32 ** 3):
     return utils.randint(0, s0 * s1 * s2, (samples,), grid.device)
 
 
+def channel_slabs(n_channels: int, width: int = ops.GRID_MAX_C):
+    """[(lo, hi)]: contiguous channel slabs at most `width` wide that cover 0 .. n_channels (the grid kernels take 1 .. 32 channels; the
+    spherical-harmonic voxel head has 48 at order 3 and 75 at order 4)"""
+    return [(lo, min(lo + width, n_channels)) for lo in range(0, n_channels, width)]
+
+
+def slab_weights(n_channels: int, width: int = ops.GRID_MAX_C):
+    """the weight of each slab's mean in the mean over all channels: its share of the channels"""
+    return [(hi - lo) / n_channels for lo, hi in channel_slabs(n_channels, width)]
+
+
 def total_variation(grid, samples: int = 32 ** 3, idxs=None):
     """src/nerf.py:381-389 as one launch forward and one backward (autograd.GridTVFn).  idxs: explicit flat indices
-    (range-checked on the host) instead of a draw."""
+    (range-checked on the host) instead of a draw.  A grid of more than 32 channels runs as contiguous channel slabs over the SAME
+    indices: the term is elementwise per channel, so the mean over all channels is the width-weighted mean of the slabs' means."""
     trusted = idxs is None
     if trusted:
         idxs = random_sample_grid(grid, samples)
-    if ag.needs_grad(grid):
-        return ag.GridTVFn.apply(grid, idxs, trusted)
-    return ops.grid_tv(grid.detach(), idxs, trusted)
+
+    def term(g):
+        return ag.GridTVFn.apply(g, idxs, trusted) if ag.needs_grad(g) else ops.grid_tv(g.detach(), idxs, trusted)
+    if grid.shape[-1] <= ops.GRID_MAX_C:
+        return term(grid)
+    slabs, weights = channel_slabs(grid.shape[-1]), slab_weights(grid.shape[-1])
+    return sum(w * term(grid[..., lo:hi].contiguous()) for w, (lo, hi) in zip(weights, slabs))
 
 
 def arc_len_grid(grid, samples: int = 16 ** 3, idxs=None):
@@ -621,8 +637,10 @@ class NeRFVoxel(CommonNeRF):
     8-neighbour lookup (csrc/voxel.hip) -- no MLP anywhere.  The static model with the per-voxel RGB head
     (`--refl-kind pos`, refl.Positional.to_voxel) or the view-dependent one (`--refl-kind pos-linear-view --voxel-refl-order K`,
     refl.PosLinearView.to_voxel: rgb rows [raw rgb | (K+1)^2 spherical-harmonic coefficients], csrc/voxel_plv.hip, DESIGN.md 3p --
-    both routes below then run the ops.voxel_plv_* / autograd.VoxelPlvSampleFn operators); the parameters keep the reference's names,
-    so its state_dict loads.
+    both routes below then run the ops.voxel_plv_* / autograd.VoxelPlvSampleFn operators), or the spherical-harmonic colour itself
+    (`--refl-kind sph-har --voxel-sh-order K`, refl.SphericalHarmonic.to_voxel: rgb rows of 3 (K+1)^2 coefficients, csrc/voxel_sh.hip,
+    DESIGN.md 3s -- ops.voxel_sh_* / autograd.VoxelShSampleFn, whose raw output is the RGB head's); `_head_kind` selects.  The
+    parameters keep the reference's names, so its state_dict loads.
 
     Routes of `forward` / `from_pts`:
       eval, no gradients  ops.voxel_render: positions, lookup, activation and compositing as ONE launch (two with bg "random")
@@ -671,7 +689,9 @@ class NeRFVoxel(CommonNeRF):
         if not self.densities.is_cuda:
             raise ValueError("NeRFVoxel.upsample: the grids must live on the GPU (the upsampling has no CPU implementation)")
         with torch.no_grad():
-            self.rgb = nn.Parameter(ops.grid_upsample(self.rgb.data.contiguous(), reso))
+            # (trilinear upsampling is per channel: a grid of more than 32 channels is the concatenation of its slabs' results)
+            self.rgb = nn.Parameter(torch.cat([ops.grid_upsample(self.rgb.data[..., lo:hi].contiguous(), reso)
+                                               for lo, hi in channel_slabs(self.rgb.shape[-1])], dim=-1))
             self.densities = nn.Parameter(ops.grid_upsample(self.densities.data.contiguous(), reso))
         self._set_resolution(reso)
 
@@ -710,18 +730,35 @@ class NeRFVoxel(CommonNeRF):
         kind = self.sigmoid_kind if self._head is None else getattr(self._head, "act_kind", None)
         return kind if kind in ops.SIGMOID else None
 
+    def _head_kind(self):
+        """which kernels read the rgb rows: "plv" [raw rgb | (order + 1)^2 coefficients] (refl.PosLinearView, csrc/voxel_plv.hip),
+        "sh" 3 channel blocks of (order + 1)^2 coefficients (refl.SphericalHarmonic, csrc/voxel_sh.hip), else "rgb" (csrc/voxel.hip)"""
+        return {refl.PosLinearView: "plv", refl.SphericalHarmonic: "sh"}.get(type(self._head), "rgb")
+
     def _plv(self):
-        """the pos-linear-view head is installed: rgb rows are [raw rgb | (order + 1)^2 coefficients] (csrc/voxel_plv.hip)"""
-        return type(self._head) is refl.PosLinearView
+        """the pos-linear-view head is installed"""
+        return self._head_kind() == "plv"
+
+    def _sh_order(self):
+        """the order of the installed spherical-harmonic colour head, or None"""
+        return self._head.order if self._head_kind() == "sh" else None
 
     def _fusable(self, pts=None):
         if not self.training and not ag.needs_grad(pts, self.densities, self.rgb) and self._act_kind() is not None and self._plv():
             return self.rgb.shape[-1] == 3 + self._head.num_sh_coeffs
+        if self._head_kind() == "sh":
+            return (not self.training and not ag.needs_grad(pts, self.densities, self.rgb) and self._act_kind() is not None
+                    and self.rgb.shape[-1] == 3 * self._head.num_sh_coeffs)
         return (not self.training and not ag.needs_grad(pts, self.densities, self.rgb) and self.rgb.shape[-1] == 3
                 and self._act_kind() is not None and (self._head is None or type(self._head) is refl.Positional))
 
     def _render(self, rays, ts, pts=None):
-        render = ops.voxel_plv_render if self._plv() else ops.voxel_render
+        kind = self._head_kind()
+        if kind == "sh":
+            out, self.alpha, self.weights = ops.voxel_sh_render(rays.contiguous(), ts, self.densities.data, self.rgb.data, self._head.order,
+                                                                self.grid_radius, self._act_kind(), self._kernel_bg(), True, pts=pts)
+            return self._finish_sky(out)
+        render = ops.voxel_plv_render if kind == "plv" else ops.voxel_render
         out, self.alpha, self.weights = render(rays.contiguous(), ts, self.densities.data, self.rgb.data, self.grid_radius,
                                                self._act_kind(), self._kernel_bg(), True, pts=pts)
         return self._finish_sky(out)
@@ -736,7 +773,11 @@ class NeRFVoxel(CommonNeRF):
             else:
                 density, params = raw[..., 0].contiguous(), raw[..., 1:]
             return self._composite(density, self.brdf(params=params.contiguous(), view=r_d, sh=sh), ts, rays)
-        if pts is None:
+        if self._head_kind() == "sh":
+            # lookup with every channel block contracted in the kernel: raw is the RGB head's [density | 3 colour logits]
+            raw = ag.VoxelShSampleFn.apply(self.densities, self.rgb, self._head.order, self.grid_radius, rays.contiguous(),
+                                           None if pts is None else pts.contiguous(), None if pts is not None else ts)
+        elif pts is None:
             raw = ag.VoxelSampleFn.apply(self.densities, self.rgb, self.grid_radius, None, rays.contiguous(), ts)
         else:
             raw = ag.VoxelSampleFn.apply(self.densities, self.rgb, self.grid_radius, pts.contiguous(), None, None)
@@ -1090,7 +1131,7 @@ class DynamicNeRFVoxel(nn.Module):
                                "torch.no_grad()); training goes through forward")
         if not c._fusable():
             raise RuntimeError(f"DynamicNeRFVoxel.forward_maps needs the canonical model's one-launch route: the per-voxel RGB head "
-                               f"with 3 colour parameters (or the pos-linear-view head) and a named activation, got {type(c._head).__name__} / {c.rgb.shape[-1]} / "
+                               f"with 3 colour parameters (or the pos-linear-view / sph-har voxel head) and a named activation, got {type(c._head).__name__} / {c.rgb.shape[-1]} / "
                                f"{c.sigmoid_kind}")
         if c.resolution != self.rigidity_grid.shape[0]:
             raise ValueError(f"DynamicNeRFVoxel: the canonical grids are {c.resolution}^3 and the deformation grids "
@@ -1101,7 +1142,7 @@ class DynamicNeRFVoxel(nn.Module):
             want.append("weights")  # (the random sky is added behind the launch from the weights)
         tt = t[:, None, None].expand(rays.shape[:-1]).contiguous()
         res = ops.dyn_voxel_render(rays.contiguous(), tt, ts, c.densities.data, c.rgb.data, self.ctrl_pts_grid.data, self.rigidity_grid.data,
-                                   self.spline, c.grid_radius, c._act_kind(), c._kernel_bg(), want=want, plv=c._plv())
+                                   self.spline, c.grid_radius, c._act_kind(), c._kernel_bg(), want=want, plv=c._plv(), sh_order=c._sh_order())
         weights = res.pop("weights", None)
         if weights is not None:
             kept, c.weights = c.weights, weights

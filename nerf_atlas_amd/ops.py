@@ -1847,6 +1847,90 @@ def voxel_plv_render(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tens
     return out, alpha, weights
 
 
+# ------------------------------------------------------------------------------------------------- NeRFVoxel, spherical-harmonic colour head (csrc/voxel_sh.hip)
+def _voxel_sh_grid(densities: torch.Tensor, rgb: torch.Tensor, order: int):
+    """(densities, rgb, S, C) of the spherical-harmonic voxel head: rgb [S,S,S, 3 (order+1)^2], a 16-byte aligned grid.  The channel count
+    does not identify the head (3 is the RGB head's, 12 the pos-linear-view head's at order 2): the order is explicit and checked."""
+    if isinstance(order, bool) or not isinstance(order, int) or order not in range(5):
+        raise ValueError(f"order {order!r} outside 0..4")
+    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
+    if Cn != 3 * (order + 1) ** 2:
+        raise ValueError(f"rgb has {Cn} channels: the spherical-harmonic voxel head of order {order} holds 3 (order + 1)^2 = {3 * (order + 1) ** 2}")
+    return densities, _aligned16(rgb), S, Cn
+
+
+def _voxel_sh_g_raw(g_raw: torch.Tensor, n: int) -> torch.Tensor:
+    g_raw = _f32(g_raw, "g_raw")
+    if g_raw.numel() != n * 4:
+        raise ValueError(f"g_raw must be [..., 4] with one row per sample ({n}), got {tuple(g_raw.shape)}")
+    return _aligned16(g_raw)
+
+
+def voxel_sh_sample(densities: torch.Tensor, rgb: torch.Tensor, order: int, grid_radius: float, rays: torch.Tensor,
+                    pts: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """raw [..., 4] = [density | s_r s_g s_b], s_c = sum_k Y_k(normalize(rays[..., 3:])) c_ck with c_ck the interpolated coefficient k of
+    colour channel c (rgb[..., c (order+1)^2 + k]), of NeRFVoxel's lookup with the spherical-harmonic head, at explicit pts
+    [T, *rays.shape[:-1], 3] or at o + t d of rays x ts [T].  The RGB head's layout: no coefficient array exists."""
+    lib = _lib.load()
+    densities, rgb, S, Cn = _voxel_sh_grid(densities, rgb, order)
+    pts, rays, ts, R, T, batch = _voxel_plv_positions(rays, pts, ts)
+    raw = torch.empty(batch + (4,), device=densities.device, dtype=torch.float32)
+    check(lib.na_voxel_sh_sample(_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, Cn, order, float(grid_radius),
+                                 _ptr(raw), _stream()))
+    return raw
+
+
+def voxel_sh_sample_backward(g_raw: torch.Tensor, S: int, order: int, grid_radius: float, rays: torch.Tensor,
+                             pts: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None, variant: Optional[int] = None):
+    """(g_densities [S,S,S,1], g_rgb [S,S,S, 3 (order+1)^2]) of voxel_sh_sample given g_raw [..., 4] and the same positions.
+    variant: scatter variant 1 or 2 (measurements); None runs the shipped one of the mode."""
+    lib = _lib.load()
+    if S % 2 != 0 or S < 2:
+        raise ValueError(f"voxel resolution {S}: even resolutions only")
+    if isinstance(order, bool) or not isinstance(order, int) or order not in range(5):
+        raise ValueError(f"order {order!r} outside 0..4")
+    pts, rays, ts, R, T, _ = _voxel_plv_positions(rays, pts, ts)
+    g_raw = _voxel_sh_g_raw(g_raw, T * R)
+    Cn = 3 * (order + 1) ** 2
+    config.require_deterministic_workspace(8 * S ** 3 * (1 + Cn))  # (a no-op outside config.set_deterministic's mode)
+    g_den = torch.zeros(S, S, S, 1, device=g_raw.device, dtype=torch.float32)
+    g_rgb = torch.zeros(S, S, S, Cn, device=g_raw.device, dtype=torch.float32)
+    args = (_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(g_raw), S, Cn, order, float(grid_radius), _ptr(g_den), _ptr(g_rgb))
+    if variant is None:
+        check(lib.na_voxel_sh_sample_backward(*args, _stream()))
+    else:
+        check(lib.na_voxel_sh_sample_backward_variant(*args, int(variant), _stream()))
+    return g_den, g_rgb
+
+
+def voxel_sh_sample_backward_pts(g_raw: torch.Tensor, pts: torch.Tensor, rays: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor,
+                                 order: int, grid_radius: float) -> torch.Tensor:
+    """g_pts [..., 3]: the gradient of voxel_sh_sample w.r.t. explicit pts given g_raw [..., 4] (a gather, no atomics)"""
+    lib = _lib.load()
+    densities, rgb, S, Cn = _voxel_sh_grid(densities, rgb, order)
+    pts, rays, _, R, T, _ = _voxel_plv_positions(rays, pts, None)
+    g_raw = _voxel_sh_g_raw(g_raw, T * R)
+    g_pts = torch.empty(pts.shape, device=pts.device, dtype=torch.float32)
+    check(lib.na_voxel_sh_sample_backward_pts(_ptr(pts), _ptr(rays), R, T * R, _ptr(densities), _ptr(rgb), _ptr(g_raw), S, Cn, order,
+                                              float(grid_radius), _ptr(g_pts), _stream()))
+    return g_pts
+
+
+def voxel_sh_render(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, order: int, grid_radius: float,
+                    sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True, pts: Optional[torch.Tensor] = None):
+    """NeRFVoxel's eval route with the spherical-harmonic head as ONE launch: basis per ray, positions (o + t d, or explicit pts
+    [T, ..., 3]) -> lookup -> activation -> compositing.  Outputs and backgrounds of voxel_render."""
+    lib = _lib.load()
+    densities, rgb, S, Cn = _voxel_sh_grid(densities, rgb, order)
+    rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
+    T = ts.shape[0]
+    R, pts = _ls_batch(rays, T, pts)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
+    check(lib.na_voxel_sh_render(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, Cn, order, float(grid_radius),
+                                 SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
+    return out, alpha, weights
+
+
 # ------------------------------------------------------------------------------------------------- DynamicNeRFVoxel (csrc/dyn_voxel.hip)
 def _dyn_voxel_grids(ctrl_pts_grid: torch.Tensor, rigidity_grid: torch.Tensor, spline: int):
     """S of ctrl_pts_grid [S,S,S,3(spline-1)] and rigidity_grid [S,S,S,1]"""
@@ -1972,15 +2056,21 @@ DYN_VOXEL_MAPS = ("depth", "acc", "flow", "rigidity", "alpha", "weights")
 
 def dyn_voxel_render(rays: torch.Tensor, t: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor,
                      ctrl_pts_grid: torch.Tensor, rigidity_grid: torch.Tensor, spline: int, grid_radius: float,
-                     sigmoid_kind: str = "upshifted", bg: str = "black", want=("depth", "flow", "rigidity"), plv: bool = False):
+                     sigmoid_kind: str = "upshifted", bg: str = "black", want=("depth", "flow", "rigidity"), plv: bool = False,
+                     sh_order: Optional[int] = None):
     """DynamicNeRFVoxel's test-time render as ONE launch (csrc/dyn_voxel_render.hip): rays [..., 6] at times t [...] (one per ray, expanded
     by the caller) over the steps ts [T] -> dict(rgb [..., 3] + the outputs named in `want`: depth [..., 1], acc [..., 1], flow [..., 3],
     rigidity [..., 1] -- the maps of runner.py:894-916 -- and alpha, weights [T, ...]).  Bit for bit compute_pts -> dyn_voxel_warp ->
     voxel_render(pts=warped) -> integrate x 4, without their per-sample tensors.  bg black | white (random: black, then sky_random).
     plv: the canonical model carries the pos-linear-view head (rgb [S,S,S, 3 + (order+1)^2]; na_dyn_voxel_plv_render, the composition
-    then being over voxel_plv_render)."""
+    then being over voxel_plv_render).  sh_order: it carries the spherical-harmonic colour head of that order (rgb [S,S,S, 3 (order+1)^2];
+    na_dyn_voxel_sh_render, the composition over voxel_sh_render)."""
     lib = _lib.load()
-    if plv:
+    if sh_order is not None:
+        if plv:
+            raise ValueError("dyn_voxel_render: plv and sh_order name two different heads")
+        densities, rgb, S, Cn = _voxel_sh_grid(densities, rgb, sh_order)
+    elif plv:
         densities, rgb, S, Cn = _voxel_plv_grid(densities, rgb)  # (Cn: the order)
     else:
         densities, rgb, S, Cn = _voxel_grid(densities, rgb)
@@ -2003,8 +2093,9 @@ def dyn_voxel_render(rays: torch.Tensor, t: torch.Tensor, ts: torch.Tensor, dens
                         ("alpha", (T,) + batch), ("weights", (T,) + batch)):
         if name in want:
             res[name] = new(*shape)
-    entry = lib.na_dyn_voxel_plv_render if plv else lib.na_dyn_voxel_render
-    check(entry(_ptr(rays), _ptr(t), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), _ptr(ctrl), _ptr(rig), S, Cn, spline, float(grid_radius),
+    entry = lib.na_dyn_voxel_sh_render if sh_order is not None else lib.na_dyn_voxel_plv_render if plv else lib.na_dyn_voxel_render
+    head = (Cn, sh_order) if sh_order is not None else (Cn,)
+    check(entry(_ptr(rays), _ptr(t), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), _ptr(ctrl), _ptr(rig), S, *head, spline, float(grid_radius),
                 SIGMOID[sigmoid_kind], BG[bg], _ptr(res["rgb"]), *(_ptr(res.get(name)) for name in DYN_VOXEL_MAPS), _stream()))
     return res
 

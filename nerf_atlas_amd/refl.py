@@ -162,21 +162,43 @@ class SphericalHarmonic(Reflectance):
                Linears as a per-ray bias (ops.linear_f32_rows over the latent columns, read where `first` left them); no [N, 2],
                [N, 256] or [N, 322] tensor exists.
       plain    training, or one direction per sample: the MLP through SkipConnMLP's own paths, then the expansion as one kernel
-               (autograd.ShShadeFn / ops.sh_shade)."""
+               (autograd.ShShadeFn / ops.sh_shade).
+    The per-voxel form (`to_voxel`, --voxel-sh-order K) has no MLP: the grid holds 3 (K+1)^2 coefficients per voxel and
+    NeRFVoxel's lookup contracts them with the ray's basis (csrc/voxel_sh.hip)."""
 
-    def __init__(self, space=None, order: int = 2, view="elaz", **kwargs):
+    def __init__(self, space=None, order: int = 2, view="elaz", voxel_order=None, **kwargs):
         super().__init__(**kwargs)
         if not (isinstance(order, int) and 0 <= order <= 4):
             raise ValueError(f"spherical-harmonic order must be an integer in 0..4, got {order!r}")
+        if voxel_order is not None and not (isinstance(voxel_order, int) and not isinstance(voxel_order, bool) and 0 <= voxel_order <= 4):
+            raise ValueError(f"--voxel-sh-order must be an integer in 0..4, got {voxel_order!r}")
+        self.voxel_order = voxel_order  # order of the per-voxel expansion `to_voxel` installs (None: no voxel form)
         if view != "elaz":
             raise NotImplementedError(f"SphericalHarmonic(view={view!r}): only the reference's default view encoding 'elaz' is built")
         self.order = order
         self.mlp = SkipConnMLP(in_size=2, out=self.out_features * (order + 1) * (order + 1), latent_size=self.latent_size,
                                enc=FourierEncoder(input_dims=2), num_layers=5, hidden_size=128, init="xavier")
 
+    def voxel_forward(self, params, view):
+        """NeRFVoxel's lookup has contracted the coefficients with the ray's basis (ops.voxel_sh_sample): `params` [..., 3] are the three
+        expansions s_c, and the colour is their activation as `forward` applies it (the reference's voxel lambda applies none and
+        never ran: DESIGN.md 7)"""
+        return self.act(params)
+
     def to_voxel(self):
-        raise NotImplementedError("refl kind 'sph-har' as a voxel head is not built (the reference's own form raises a TypeError, "
-                                  "torch.Size + list, at src/refl.py:720): --model voxel takes --refl-kind pos")
+        """src/refl.py:715-722 as intended: the MLP is deleted and the grid holds 3 (K+1)^2 coefficients per voxel, channel-major (the
+        layout of the reference's reshape(..., feats, -1)).  The reference's own form dies with torch.Size + list at src/refl.py:720;
+        --voxel-sh-order K selects this one, and without it the head has no voxel form."""
+        if self.voxel_order is None:
+            raise NotImplementedError("refl kind 'sph-har' as a voxel head (3 (K + 1)^2 spherical-harmonic coefficients per voxel) needs "
+                                      "--voxel-sh-order K, K in 0..4 (the reference's own form raises a TypeError, torch.Size + list, at "
+                                      "src/refl.py:720); without it --model voxel takes --refl-kind pos")
+        if self.out_features != 3:
+            raise NotImplementedError(f"the sph-har voxel head with out_features = {self.out_features} colour channels (3 have a kernel)")
+        del self.mlp
+        self.order = order = self.voxel_order
+        self.num_sh_coeffs = (order + 1) * (order + 1)
+        return self.out_features * self.num_sh_coeffs, self.voxel_forward
 
     def _hoistable(self, view, latent):
         m = self.mlp
@@ -268,6 +290,7 @@ def load(args, refl_kind: str, space_kind: str, latent_size: int):
     kwargs = {}
     if refl_kind == "sph-har":
         kwargs["order"] = getattr(args, "refl_order", 2)  # src/refl.py:33
+        kwargs["voxel_order"] = getattr(args, "voxel_sh_order", None)  # this build's flag
     if refl_kind == "pos-linear-view":
         kwargs["voxel_order"] = getattr(args, "voxel_refl_order", None)  # this build's flag
     return cons(latent_size=latent_size, act=args.sigmoid_kind, out_features=args.feature_space,

@@ -47,6 +47,7 @@ DEFAULTS = dict(
     voxel_random_spline_len_decay=0.0, spline_len_decay=0.0,  # runner.py:276-283
     voxel_upsample=[],  # this build's flag: ITER:RESO pairs, NeRFVoxel.upsample(RESO) at the start of iteration ITER
     voxel_refl_order=None,  # this build's flag: order K (0..4) of the per-voxel pos-linear-view head, the reference's hard-coded 4
+    voxel_sh_order=None,  # this build's flag: order K (0..4) of the per-voxel spherical-harmonic colour head
     depth_images=False, flow_map=False, rigidity_map=False, with_alpha=False,  # runner.py:360-392: maps next to the test frames
     render_over_time=-1, render_over_time_steps=100, render_over_time_end_sec=1.0,  # runner.py:252-261: a time sweep of one test camera
     msssim_loss=False,  # runner.py:359, :985-990: report ms-ssim next to the PSNR summary
@@ -119,7 +120,7 @@ def args_from_argv(argv) -> SimpleNamespace:
         elif isinstance(v, list):
             p.add_argument(flag, nargs="+", default=v, type=type(v[0]) if v else str)
         elif v is None:
-            p.add_argument(flag, default=None, type=(int if k in ("spline", "voxel_refl_order") else str))
+            p.add_argument(flag, default=None, type=(int if k in ("spline", "voxel_refl_order", "voxel_sh_order") else str))
         else:
             p.add_argument(flag, type=type(v), default=v)
     p.add_argument("--nosave", action="store_true")
@@ -142,6 +143,21 @@ def check_voxel_refl_order(args):
         raise ValueError(f"--voxel-refl-order {k} over --model {args.model}: the flag sets the per-voxel head of --model voxel")
     if args.refl_kind != "pos-linear-view":
         raise ValueError(f"--voxel-refl-order {k} with --refl-kind {args.refl_kind}: the flag belongs to --refl-kind pos-linear-view")
+
+
+def check_voxel_sh_order(args):
+    """--voxel-sh-order K: the order of the per-voxel spherical-harmonic colour SphericalHarmonic.to_voxel installs (3 (K+1)^2
+    coefficients per voxel).  Only meaningful for --model voxel --refl-kind sph-har; anything else raises by name.  --refl-order stays
+    the MLP head's order."""
+    k = getattr(args, "voxel_sh_order", None)
+    if k is None:
+        return
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= 4:
+        raise ValueError(f"--voxel-sh-order {k!r}: an integer in 0..4")
+    if args.model != "voxel":
+        raise ValueError(f"--voxel-sh-order {k} over --model {args.model}: the flag sets the per-voxel head of --model voxel")
+    if args.refl_kind != "sph-har":
+        raise ValueError(f"--voxel-sh-order {k} with --refl-kind {args.refl_kind}: the flag belongs to --refl-kind sph-har")
 
 
 def seed(s):
@@ -169,6 +185,7 @@ def load_model(args, is_dyn=False, device="cuda"):
             raise ValueError(f"--steps-fine {steps_fine} (coarse -> fine training) needs --model plain --refl-kind view without --mip "
                              f"and without a --dyn-model; got {why}")
     check_voxel_refl_order(args)
+    check_voxel_sh_order(args)
     model = nerf.load_nerf(args)
     if is_dyn:
         model = nerf.load_dyn(args, model, device)
