@@ -375,6 +375,21 @@ int na_linear_wgrad_bf16x3_ow(const float* x0, int in0, const float* x1, int in1
                               int pre_act, float* dW, float* db, void* stream);
 size_t na_train_packed_bytes(int M, int K);
 int na_train_gemm_packed_ok(int64_t N, int M);
+/* Which kernel family a shape runs -- what the entry points themselves dispatch on, for callers and tests that must know:
+ * K-staged tiles (small batches, widths > 1024; the _pk entry points return NA_EUNSUPPORTED there), the layer-synchronous
+ * streaming kernels, the row-stream kernel of a narrow output (K = 256, M <= 128), the row-stream kernel on the narrow second
+ * source of a skip layer with the streaming kernel on its first, W resident in registers (train_fwd.hip).  `in` of the
+ * unpacked input gradient is in0 + in1. */
+#define NA_TRAIN_PATH_KSTAGED 0
+#define NA_TRAIN_PATH_LS 1
+#define NA_TRAIN_PATH_NARROW 2
+#define NA_TRAIN_PATH_NARROW_X1 3
+#define NA_TRAIN_PATH_RESIDENT 4
+int na_linear_bf16x3_path(int64_t N, int out);
+int na_linear_dgrad_bf16x3_path(int64_t N, int in);
+int na_linear_wgrad_bf16x3_path(int64_t N, int out, int in0, int in1);
+int na_linear_bf16x3_pk_path(int64_t N, int out, int in0, int in1, int pre_act);
+int na_linear_dgrad_bf16x3_pk_path(int64_t N, int out, int in0, int in1);
 int na_train_pack_many(int n, const float* const* W, const int* M, const int* K, const int* ld, const int* transposed,
                        void* const* dst, void* stream);
 int na_linear_bf16x3_pk(const float* x0, int in0, const float* x1, int in1, int64_t N, const void* w_packed, const float* b,

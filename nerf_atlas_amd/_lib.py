@@ -125,6 +125,11 @@ SIGNATURES = {
                                             c_f32p, C.c_void_p]),
     "na_train_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "na_train_gemm_packed_ok": (C.c_int, [c_i64, C.c_int]),
+    "na_linear_bf16x3_path": (C.c_int, [c_i64, C.c_int]),
+    "na_linear_dgrad_bf16x3_path": (C.c_int, [c_i64, C.c_int]),
+    "na_linear_wgrad_bf16x3_path": (C.c_int, [c_i64, C.c_int, C.c_int, C.c_int]),
+    "na_linear_bf16x3_pk_path": (C.c_int, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "na_linear_dgrad_bf16x3_pk_path": (C.c_int, [c_i64, C.c_int, C.c_int, C.c_int]),
     "na_train_pack_many": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                      C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_void_p]),
     "na_linear_bf16x3_pk": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_i64, C.c_void_p, c_f32p, C.c_int, C.c_int, c_f32p,

@@ -1278,6 +1278,25 @@ static bool lsnt_wanted(int64_t N, int M) {
   return !tiled && N >= 2048 && M <= 1024;
 }
 
+// Which kernel family a shape runs (NA_TRAIN_PATH_*): the entry points below dispatch on these, and the C ABI hands them out
+// (na_linear_bf16x3_path ...) so that a test can assert the path a shape took instead of restating the rule.
+static int fwd_path(int64_t N, int out) { return lsnt_wanted(N, out) ? NA_TRAIN_PATH_LS : NA_TRAIN_PATH_KSTAGED; }
+static int fwd_pk_path(int64_t N, int out, int in0, int in1, int act) {
+  if (!lsnt_wanted(N, out)) return NA_TRAIN_PATH_KSTAGED;
+  if (train_fwd_wanted(N, out, in0, in1, act)) return NA_TRAIN_PATH_RESIDENT;
+  if (in1 == 0 && nrw::wanted(N, out, in0)) return NA_TRAIN_PATH_NARROW;
+  return NA_TRAIN_PATH_LS;
+}
+static int dgrad_pk_path(int64_t N, int out, int in0, int in1) {
+  if (!lsnt_wanted(N, in0 + in1)) return NA_TRAIN_PATH_KSTAGED;
+  if (in1 == 0 && nrw::wanted(N, in0, out)) return NA_TRAIN_PATH_NARROW;
+  if (in1 > 0 && (in0 & 63) == 0 && nrw::wanted(N, in1, out)) return NA_TRAIN_PATH_NARROW_X1;
+  return NA_TRAIN_PATH_LS;
+}
+static int wgrad_path(int64_t N, int out, int in0, int in1) {
+  return lsnt_wanted(N, out) && out <= 256 && in0 <= 256 && in1 <= 256 ? NA_TRAIN_PATH_LS : NA_TRAIN_PATH_KSTAGED;
+}
+
 extern "C" {
 
 int na_linear_bf16x3(const float* x0, int in0, const float* x1, int in1, int64_t N, const float* W, const float* b,
@@ -1294,7 +1313,7 @@ int na_linear_bf16x3(const float* x0, int in0, const float* x1, int in1, int64_t
   a.bias = b;
   a.y0 = y;
   a.c0 = out;
-  if (lsnt_wanted(N, out)) {
+  if (fwd_path(N, out) == NA_TRAIN_PATH_LS) {
     lsnt::Args l{};
     l.a = a.a; l.M = out; l.act = pre_act; l.bias = b; l.y0 = y; l.c0 = out;
     const int rc = lsnt::launch<0>(l, W, in0 + in1, (hipStream_t)stream, "na_linear_bf16x3");
@@ -1321,7 +1340,7 @@ int na_linear_dgrad_bf16x3(const float* dY, int out, int64_t N, const float* Wt,
   a.x1 = x1;
   a.c0 = in0;
   a.c1 = in1;
-  if (lsnt_wanted(N, in0 + in1)) {
+  if (fwd_path(N, in0 + in1) == NA_TRAIN_PATH_LS) {  // (the input gradient is the same GEMM with in0 + in1 output columns)
     lsnt::Args l{};
     l.a = a.a; l.M = in0 + in1; l.act = pre_act; l.y0 = a.y0; l.y1 = a.y1; l.x0 = x0; l.x1 = x1; l.c0 = in0; l.c1 = in1;
     const int rc = lsnt::launch<1>(l, Wt, out, (hipStream_t)stream, "na_linear_dgrad_bf16x3");
@@ -1345,7 +1364,7 @@ static int wgrad_bf16x3_impl(const float* x0, int in0, const float* x1, int in1,
   NA_REQUIRE(pre_act >= NA_ACT_NONE && pre_act <= NA_ACT_SIN, NA_EUNSUPPORTED, "na_linear_wgrad_bf16x3: activation %d", pre_act);
   // The layer-synchronous kernel, one launch per source of the concatenation (dY is read again for the second: the sources of
   // a skip layer are [hidden 256 | encoding 38 or 69]); wider shapes and small batches stay on the K-staged kernel.
-  const bool ls0 = lsnt_wanted(N, out) && out <= 256 && in0 <= 256 && in1 <= 256;
+  const bool ls0 = wgrad_path(N, out, in0, in1) == NA_TRAIN_PATH_LS;
   if (ls0) {
     int rc = lstn::launch(dY, out, x0, in0, pre_act, N, dW, in0 + in1, db, (hipStream_t)stream, "na_linear_wgrad_bf16x3", overwrite);
     if (rc != lsnt::kNoScratch) {
@@ -1439,6 +1458,12 @@ int na_linear_wgrad_bf16x3_cols(const float* x, int in, int64_t N, const float* 
 // ---- round 5: the B operands of a whole training step packed by one launch, and the GEMMs that take them --------------------
 int na_train_gemm_packed_ok(int64_t N, int M) { return (M >= 1 && lsnt_wanted(N, M)) ? 1 : 0; }
 
+int na_linear_bf16x3_path(int64_t N, int out) { return fwd_path(N, out); }
+int na_linear_dgrad_bf16x3_path(int64_t N, int in) { return fwd_path(N, in); }
+int na_linear_wgrad_bf16x3_path(int64_t N, int out, int in0, int in1) { return wgrad_path(N, out, in0, in1); }
+int na_linear_bf16x3_pk_path(int64_t N, int out, int in0, int in1, int pre_act) { return fwd_pk_path(N, out, in0, in1, pre_act); }
+int na_linear_dgrad_bf16x3_pk_path(int64_t N, int out, int in0, int in1) { return dgrad_pk_path(N, out, in0, in1); }
+
 size_t na_train_packed_bytes(int M, int K) { return (M >= 1 && M <= 1024 && K >= 1) ? lsnt::packed_bytes(M, K) : 0; }
 
 int na_train_pack_many(int n, const float* const* W, const int* M, const int* K, const int* ld, const int* transposed,
@@ -1474,11 +1499,12 @@ int na_linear_bf16x3_pk(const float* x0, int in0, const float* x1, int in1, int6
   NA_REQUIRE(in0 >= 1 && in1 >= 0 && out >= 1 && N >= 0, NA_EINVAL, "na_linear_bf16x3_pk: bad shape");
   NA_REQUIRE(in1 == 0 || x1 != nullptr, NA_ENULL, "na_linear_bf16x3_pk: in1>0 needs x1");
   NA_REQUIRE(pre_act >= NA_ACT_NONE && pre_act <= NA_ACT_SIN, NA_EUNSUPPORTED, "na_linear_bf16x3_pk: activation %d", pre_act);
-  NA_REQUIRE(lsnt_wanted(N, out), NA_EUNSUPPORTED, "na_linear_bf16x3_pk: this batch / width runs the K-staged kernel: call "
+  const int path = fwd_pk_path(N, out, in0, in1, pre_act);
+  NA_REQUIRE(path != NA_TRAIN_PATH_KSTAGED, NA_EUNSUPPORTED, "na_linear_bf16x3_pk: this batch / width runs the K-staged kernel: call "
              "na_linear_bf16x3 (na_train_gemm_packed_ok says which)");
-  if (train_fwd_wanted(N, out, in0, in1, pre_act))  // a 256 wide layer (hidden, skip [256 | 38 / 69]): W resident in registers, one pass (train_fwd.hip)
+  if (path == NA_TRAIN_PATH_RESIDENT)  // a 256 wide layer (hidden, skip [256 | 38 / 69]): W resident in registers, one pass (train_fwd.hip)
     return train_fwd_launch(x0, in0, x1, in1, N, w_packed, b, out, pre_act, y, (hipStream_t)stream, "na_linear_bf16x3_pk");
-  if (in1 == 0 && nrw::wanted(N, out, in0)) {  // a narrow output (256 -> 65 / 3): the row-stream kernel
+  if (path == NA_TRAIN_PATH_NARROW) {  // a narrow output (256 -> 65 / 3): the row-stream kernel
     nrw::Args n{};
     n.a = x0; n.N = N; n.wp = (const char*)w_packed; n.M = out; n.act = pre_act; n.bias = b; n.y = y;
     return nrw::launch<0>(n, (hipStream_t)stream, "na_linear_bf16x3_pk");
@@ -1497,17 +1523,18 @@ int na_linear_dgrad_bf16x3_pk(const float* dY, int out, int64_t N, const void* w
   NA_REQUIRE(pre_act >= NA_ACT_NONE && pre_act <= NA_ACT_SIN, NA_EUNSUPPORTED, "na_linear_dgrad_bf16x3_pk: activation %d", pre_act);
   NA_REQUIRE(pre_act == NA_ACT_NONE || ((g_x0 == nullptr || x0) && (g_x1 == nullptr || in1 == 0 || x1)), NA_ENULL,
              "na_linear_dgrad_bf16x3_pk: the activation derivative needs the forward inputs");
-  NA_REQUIRE(lsnt_wanted(N, in0 + in1), NA_EUNSUPPORTED, "na_linear_dgrad_bf16x3_pk: this batch / width runs the K-staged kernel: call "
+  const int path = dgrad_pk_path(N, out, in0, in1);
+  NA_REQUIRE(path != NA_TRAIN_PATH_KSTAGED, NA_EUNSUPPORTED, "na_linear_dgrad_bf16x3_pk: this batch / width runs the K-staged kernel: call "
              "na_linear_dgrad_bf16x3 (na_train_gemm_packed_ok says which)");
   // narrow gradients on the row-stream kernel (round 5): a narrow single source (the init Linears: 256 -> 38 / 69), and the
   // narrow SECOND source of a skip layer [256 | 38], whose 256 wide columns then run as a plain single-pass layer (the
   // packed W^T is column-group major: rows 0..255 are its first four groups, the narrow rows start at group in0 / 64)
-  if (in1 == 0 && nrw::wanted(N, in0, out)) {
+  if (path == NA_TRAIN_PATH_NARROW) {
     nrw::Args n{};
     n.a = dY; n.N = N; n.wp = (const char*)wt_packed; n.M = in0; n.act = pre_act; n.xd = x0; n.y = g_x0;
     return nrw::launch<1>(n, (hipStream_t)stream, "na_linear_dgrad_bf16x3_pk");
   }
-  if (in1 > 0 && (in0 & 63) == 0 && nrw::wanted(N, in1, out)) {
+  if (path == NA_TRAIN_PATH_NARROW_X1) {
     if (g_x1 != nullptr) {
       nrw::Args n{};
       n.a = dY; n.N = N; n.wp = (const char*)wt_packed + (size_t)(in0 / 64) * (2 * 2 * lsnt::SEG); n.M = in1; n.act = pre_act; n.xd = x1;

@@ -196,12 +196,15 @@ __global__ __launch_bounds__(64 * WM * WN) void linear_nt_kernel(NtArgs g) {
       f32x4 v = *(const f32x4*)(Cs + lrow * CP + c4 * 4);
       const bool first = col < g.c0;
       float* dst = first ? g.y0 : g.y1;
-      if (dst == nullptr) continue;
       const int ld = first ? g.c0 : g.c1;
       const int cc = first ? col : col - g.c0;
       const float* xin = MODE == 1 ? (first ? g.x0 : g.x1) : nullptr;
       const bool whole = (ld & 3) == 0 && (cc & 3) == 0 && cc + 4 <= ld && (first || (g.c0 & 3) == 0);
       if (whole) {
+        // (an output that was not asked for: only here -- four columns that straddle the two outputs start in the first and may
+        // end in the second, which the element-wise branch decides column by column; skipping them with a null FIRST output
+        // left the second output's leading 4 - (c0 & 3) columns unwritten)
+        if (dst == nullptr) continue;
         if (MODE == 0 && g.bias != nullptr) {
           const f32x4 bj = *(const f32x4*)(g.bias + col);
           v += bj;

@@ -23,8 +23,14 @@ __device__ __forceinline__ float trev(float x) {
   float r = fmaf(x, 0.15915493667125702f, -q);
   return fmaf(x, 6.4206382432985265e-09f, r);
 }
+// A NaN stays NaN (mlp_engine.h act_apply): the median alone returns its finite bound for it, and a NaN activation then entered
+// the forward and the weight gradient as 3.0e38 -- finite results from a poisoned sample.  (sin: v_sin_f32 of the NaN that trev
+// makes of a NaN or an infinity is NaN.)
 __device__ __forceinline__ float tact(float v, int act) {
-  if (act == NA_ACT_LEAKY_RELU) return __builtin_amdgcn_fmed3f(v, v * 0.01f, 3.0e38f);
+  if (act == NA_ACT_LEAKY_RELU) {
+    const float m = __builtin_amdgcn_fmed3f(v, v * 0.01f, 3.0e38f);
+    return v != v ? v : m;
+  }
   if (act == NA_ACT_SIN) return __builtin_amdgcn_sinf(trev(v));
   return v;
 }

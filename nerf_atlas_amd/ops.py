@@ -654,6 +654,28 @@ def train_gemm_packed_ok(N: int, M: int) -> bool:
     return bool(_lib.load().na_train_gemm_packed_ok(int(N), int(M)))
 
 
+TRAIN_PATH = {0: "k_staged", 1: "ls", 2: "narrow", 3: "narrow_x1", 4: "resident"}   # include/nerf_atlas_amd.h NA_TRAIN_PATH_*
+
+
+def linear_f32_path(N: int, out: int, in0: int = 0, in1: int = 0, pre_act: str = "none", packed: bool = False) -> str:
+    """The kernel family linear_f32(split_bf16=True) runs this shape on (na_linear_bf16x3_path / _pk_path)."""
+    lib = _lib.load()
+    return TRAIN_PATH[lib.na_linear_bf16x3_pk_path(int(N), int(out), int(in0), int(in1), ACT[pre_act]) if packed
+                      else lib.na_linear_bf16x3_path(int(N), int(out))]
+
+
+def linear_dgrad_path(N: int, out: int, in0: int, in1: int = 0, packed: bool = False) -> str:
+    """The kernel family linear_dgrad runs this shape on (na_linear_dgrad_bf16x3_path / _pk_path)."""
+    lib = _lib.load()
+    return TRAIN_PATH[lib.na_linear_dgrad_bf16x3_pk_path(int(N), int(out), int(in0), int(in1)) if packed
+                      else lib.na_linear_dgrad_bf16x3_path(int(N), int(in0) + int(in1))]
+
+
+def linear_wgrad_path(N: int, out: int, in0: int, in1: int = 0) -> str:
+    """The kernel family linear_wgrad(split_bf16=True) runs this shape on (na_linear_wgrad_bf16x3_path)."""
+    return TRAIN_PATH[_lib.load().na_linear_wgrad_bf16x3_path(int(N), int(out), int(in0), int(in1))]
+
+
 def train_pack_many(mats):
     """ONE launch packs every B operand of a training step (na_train_pack_many).  mats: [(W [rows, cols] fp32 contiguous,
     transposed)] -- the operand is W itself (a forward's [out, in]) or, with transposed, W^T (an input gradient's [in, out], read
