@@ -791,6 +791,25 @@ __device__ __forceinline__ void recs(f32x16 (&acc)[NT][NBk], const f32x16 (&cb)[
   __builtin_amdgcn_s_setprio(0);
 }
 
+// ---- the weight registers as recs<.., NREC, NG, .., PAR0> over the records rec0 .. rec0 + NG - 1 leaves them, without its
+// products: for a wave whose result of the phase nobody reads (MODEL 0: the shadow row groups in view.out, which encode the next
+// pass's [hash | x] group instead).  a16 / a6 and the scale slot of the record BEHIND the call, the other slot the call's last record.
+template <int NREC, int NG = 4, int PAR0 = 0>
+__device__ __forceinline__ void recs_ring(Regs& R, __amdgpu_buffer_rsrc_t rs, int xrec, int rec0, int lane) {
+  int nrc = rec0 + NG;
+  nrc = nrc >= NREC ? 0 : nrc;
+  const int noff = __builtin_amdgcn_readfirstlane(xrec + nrc * REC);
+  const int loff = __builtin_amdgcn_readfirstlane(xrec + (rec0 + NG - 1) * REC);
+  R.asc[(PAR0 + NG - 1) & 1] = wloadsc(rs, lane, loff);
+  R.asc[(PAR0 + NG) & 1] = wloadsc(rs, lane, noff);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    a16set(R.a16[0], c, wload16(rs, lane, noff, 0, c));
+    a16set(R.a16[1], c, wload16(rs, lane, noff, 1, c));
+  }
+  R.a6 = wload6(rs, lane, noff);
+}
+
 // v_cvt_scalef32_2xpk16_fp6_f32 writes its six destination registers while it still reads its scale and the tails of its
 // sources (tools/hw/cvt_fp6_overlap.hip), and the compiler's builtin does not say so: this form marks the destination
 // early-clobber, i.e. disjoint from every operand.  (The builtin form lets the allocator put the destination on the first six

@@ -20,6 +20,7 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
   constexpr bool TRAIN = MODEL == 9;  // MODEL 0 that also leaves every Linear's output rows in HBM for the backward pass (train_store below)
   constexpr bool HEAD2 = MODEL == 7 || MODEL == 8;  // the reflectance head has a hash encoder of its own (src/refl.py:230-290)
   constexpr bool MIP = MODEL == 6;
+  constexpr bool PREGATHER = MODEL == 0 && PREC == NA_PREC_F16X;  // the shadow waves hash-encode the next pass in view.out (pregather below)
   constexpr int PPP = PREC == NA_PREC_F16X ? x::hdr_units(MODEL)
                       : MODEL == 1 ? kTinyPairs : MODEL == 2 ? kViewPairs : MODEL == 3 ? kSirenPairs : MODEL == 4 ? kHashMlpPairs : kPairsPerPass;  // pairs per pass and row group
   // rays / elaz are read with scalar (SMEM) loads below; both were written by kernels that ran just before this one, into
@@ -39,10 +40,10 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
       return;
     }
   }
-  const int lane = threadIdx.x & 63;
+  int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int rg = wv & 3, g = wv >> 2;
-  const int hi = lane >> 5, ln = lane & 31;
+  int hi = lane >> 5, ln = lane & 31;
   char* hb = smem + g * C::GROUP;
   char* ib = hb + C::HREG;
   const bool owner = rg < NB;           // this wave owns block rg of its group (encoder, out layers, compositing)
@@ -424,7 +425,7 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
   auto pass_tail = [&](int pl) {
     if (NB == 4 || owner) {
       const TsPair tc = ts_load(pl);
-      tnext = ts_load(pl + 1);
+      if constexpr (!PREGATHER) tnext = ts_load(pl + 1);  // (PREGATHER: only the shadows encode)
       prev_dn = own_dn;
       if constexpr (PREC == NA_PREC_F16X) density = *(const float*)(ib + blk * x::KQ + 6144 + 1024 + ln * 16 + 12);
       composite(prev_geom(pl, tc), oc[0], density);
@@ -575,6 +576,87 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
           n1[0] = u[0]; n1[1] = u[1]; n1[2] = u[2]; n1[3] = u[3]; n1[4] = w[0]; n1[5] = w[1]; n1[6] = w[2]; n1[7] = w[3];
           x::store_block<NA_ACT_LEAKY_RELU, 3>(ib + blk * x::KQ, n0, n1, ml, a.sat_gen);
         }
+    }
+  };
+  // ---- MODEL 0, NA_PREC_F16X: the [hash | x] group of block b of pass p + 1 is produced DURING view.out of pass p, by block b's
+  // shadow wave (row group b + 2), whose view.out products nobody reads (x::recs_ring keeps its weight registers in step).  Lane
+  // (sample, h) gathers the levels 4 h .. 4 h + 3 one after the other (two rounds in flight: the accumulators are dead) and so holds
+  // MFMA lane (sample, h)'s sixteen hash features in slot order: no exchange between the lane halves, ONE conversion on 64 lanes
+  // into the block's init group -- free since view.L0, except the density in the spare dword of the T operand (KEEP7) and the
+  // compositing partials in the padding chunk (NCHW = 3), which the owner's pass_tail / the next EP still read.  The raw values
+  // for the skip connection wait in registers (pg0, pgx) across the barrier: their stash, this wave's K64 region of block 1, is
+  // still read by view.out's products; EP stores them (pregather_stash) and E1 re-enters them (reenter_pregather), shadows only.
+  // The same table entries, trilinear arithmetic, slots, per-lane maximum and conversion instructions as hash_group_ep.
+  f32x16 pg0;
+  float pgx[3] = {0.f, 0.f, 0.f};
+  if constexpr (PREGATHER) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) pg0[e] = 0.f;
+  }
+  // (a wave or pass that does not encode leaves pg0 / pgx DEFINED: carried unchanged they would be live through the whole pass)
+  auto pregather_none = [&]() {
+    if constexpr (PREGATHER) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) pg0[e] = 0.f;
+      pgx[0] = pgx[1] = pgx[2] = 0.f;
+    }
+  };
+  auto pregather = [&](int pl) {  // (tnext = ts_load(pl), own_setup(pl) have run)
+    if constexpr (PREGATHER) {
+      if (pl >= a.npg) {  // (behind the last pass of the stream there is nothing to encode)
+        pregather_none();
+      } else {
+        const Geom q = geom(pl, blk, tnext);
+        // the lane half, recomputed here and opaque to the optimiser: from `hi` the per-lane resolutions and table bases of the four
+        // levels were hoisted out of the pass loop and spilled, and `hi` itself is one more register held through the whole pass
+        int hq;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_lshrrev_b32 %0, 5, %0" : "=v"(hq));
+        f32x16 pgt;
+        HashGather hg[2];
+        hash_level_issue(q.px, q.py, q.pz, a.tables, hq ? a.res.n[4] : a.res.n[0], 4 * hq, hg[0]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float f[4];
+          if (k + 1 < 4) hash_level_issue(q.px, q.py, q.pz, a.tables, hq ? a.res.n[4 + k + 1] : a.res.n[k + 1], 4 * hq + k + 1, hg[(k + 1) & 1]);
+          hash_level_finish(hg[k & 1], f);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) pgt[4 * k + e] = f[e];
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        f32x16 n1;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) n1[e] = 0.f;
+        if (hi == 0) { n1[0] = q.px; n1[1] = q.py; n1[2] = q.pz; n1[3] = q.px; n1[4] = q.py; n1[5] = q.pz; }
+        pgx[0] = n1[0]; pgx[1] = n1[1]; pgx[2] = n1[2];
+        x::store_block<NA_ACT_NONE, 3, true>(ib + blk * x::KQ, pgt, n1, lane, a.sat_gen);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) pg0[e] = pgt[e];
+      }
+    }
+  };
+  auto pregather_stash = [&]() {  // EP, shadows: lane = MFMA lane
+    if constexpr (PREGATHER) {
+      char* st = hb + x::BLKH + rg * x::KQ + lane * 16;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) *(f32x4*)(st + c * 1024) = f32x4{pg0[4 * c], pg0[4 * c + 1], pg0[4 * c + 2], pg0[4 * c + 3]};
+      *(f32x4*)(st + 4096) = f32x4{pgx[0], pgx[1], pgx[2], pgx[0]};
+      *(f32x4*)(st + 5120) = f32x4{pgx[1], pgx[2], 0.f, 0.f};
+    }
+  };
+  auto reenter_pregather = [&]() {  // E1, shadows: reenter_hash on all 64 lanes
+    if constexpr (PREGATHER) {
+      const char* st = hb + x::BLKH + rg * x::KQ + lane * 16;
+      f32x16 n0, n1;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const f32x4 v = *(const f32x4*)(st + c * 1024);
+        n0[4 * c] = v[0]; n0[4 * c + 1] = v[1]; n0[4 * c + 2] = v[2]; n0[4 * c + 3] = v[3];
+      }
+      const f32x4 u = *(const f32x4*)(st + 4096), w = *(const f32x4*)(st + 5120);
+#pragma unroll
+      for (int e = 0; e < 16; ++e) n1[e] = 0.f;
+      n1[0] = u[0]; n1[1] = u[1]; n1[2] = u[2]; n1[3] = u[3]; n1[4] = w[0]; n1[5] = w[1]; n1[6] = w[2]; n1[7] = w[3];
+      x::store_block<NA_ACT_LEAKY_RELU, 3>(ib + blk * x::KQ, n0, n1, lane, a.sat_gen);
     }
   };
   // ---- MODEL 7 / 8 (round 6): the reflectance head's OWN hash encoder (src/refl.py:233-237, 253-257: `enc=HashEncoder()`, a second set
@@ -787,6 +869,9 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
   if constexpr (M0 || MODEL == 4) {
     tnext = ts_load(0);
     own_setup(0);
+    if constexpr (PREGATHER) {
+      if (!owner) pregather(0);  // (pass 0 has no view.out in front of it)
+    }
   }
   for (int pass = 0; pass < a.npg; ++pass) {
     int cur = 0;
@@ -812,6 +897,11 @@ __global__ __launch_bounds__(512) void render_ls_kernel(Args a) {
     } else {
       composite(prev_geom(prev, ts_load(prev)), oc[0], density);
     }
+  }
+  if constexpr (PREGATHER) {
+    // the lane index again, from nothing: held from the top of the kernel for the few uses below it was spilled across the pass loop
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    hi = lane >> 5; ln = lane & 31;
   }
   __syncthreads();
   if ((MODEL < 4 || M0) && prev >= 0) combine(prev);

@@ -10,12 +10,20 @@
     // distinct 128-B lines per instruction, 8 MiB of tables): ~10k cycles per group and pass whether issued as four rounds,
     // two or one (measured); spreading the levels over the epilogues of the other layers was slower still (every gathering
     // wave stalls ~3k cycles per round and those epilogues have ~1.8k cycles of slack).
+    // (MODEL 0 in NA_PREC_F16X: the encoder has left this phase -- the shadow waves run it under the previous pass's view.out, below)
     STAMP(0);
     if (prev >= 0) combine(prev);  // (partials: written before the barrier that closed view.out; EP does not touch their chunk)
     if constexpr (PREC == NA_PREC_F16X) {
-      if constexpr (MIP) { geo_setup(pass); mip_setup(); }
-      hash_group_ep(pass);
-      if constexpr (MIP) gen_ipe(std::integral_constant<int, NA_ACT_NONE>{});
+      if constexpr (MIP) {
+        geo_setup(pass); mip_setup();
+        hash_group_ep(pass);
+        gen_ipe(std::integral_constant<int, NA_ACT_NONE>{});
+      } else {
+        // MODEL 0: the [hash | x] group of this pass was produced under the previous pass's view.out by the shadow waves (pregather,
+        // ls_kernel.h); what is left here are their raw values for E1's re-entry, whose stash was still being read until the barrier
+        if (!owner) pregather_stash();
+        STAMP(7);
+      }
     } else
     if (NB == 4 || owner) {  // (bf16x3: row groups 2,3 own no block -- nothing to encode or composite)
       STAMP(8);
@@ -87,7 +95,8 @@
       SYNC();
       {
         x::store_acts<NA_ACT_LEAKY_RELU, NB, 0, 1>(acc, hb, rg, lane, a.sat_gen);
-        reenter_hash();
+        if constexpr (MIP) reenter_hash();
+        else if (!owner) reenter_pregather();
         x::store_acts<NA_ACT_LEAKY_RELU, NB, 1, 2>(acc, hb, rg, lane, a.sat_gen);
         load_bias2(1);
       }
@@ -212,9 +221,20 @@
         x::store_acts<NA_ACT_SIN, NB>(acc, hb, rg, lane, a.sat_gen);
       }
       SYNC();
-      x::recs<1, 1, true, XNR>(ocx, bo, XR, wrs, xrec, RVO, hb + blk * x::BLKH, lane);            // view.out (block per wave)
-      oc[0] = ocx[0][0];
-      pass_tail(pass);
+      if constexpr (MIP) {
+        x::recs<1, 1, true, XNR>(ocx, bo, XR, wrs, xrec, RVO, hb + blk * x::BLKH, lane);          // view.out (block per wave)
+        oc[0] = ocx[0][0];
+        pass_tail(pass);
+      } else {
+        // MODEL 0: the owner of block blk runs its products and composites; the shadow of the block has no products (nobody reads
+        // them) -- the weight registers as the products would leave them, then the next pass's [hash | x] group of the block
+        if (owner) x::recs<1, 1, true, XNR>(ocx, bo, XR, wrs, xrec, RVO, hb + blk * x::BLKH, lane);  // view.out (block per wave)
+        else x::recs_ring<XNR>(XR, wrs, xrec, RVO, lane);
+        if (owner) oc[0] = ocx[0][0];
+        pass_tail(pass);
+        if (owner) pregather_none();
+        else pregather(pass + 1);
+      }
       SYNC();
     } else {
     // ================= `first` MLP (LeakyReLU)
