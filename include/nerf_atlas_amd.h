@@ -1061,6 +1061,36 @@ int na_ssim_backward(const float* x, const float* y, const float* g, int64_t N, 
                      void* stream);
 int na_image_halve(const float* x, const float* y, int64_t N, int H, int W, int C, float* out_x, float* out_y, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The reference's loss wrapper (runner.py:552-594, src/utils.py:198-204, 279-314; csrc/image_loss.hip): --loss-fns
+ * l2 | l1 | rmse in --color-spaces rgb | hsv | luminance | xyz under --tone-map and --gamma-correct-loss, of got, ref [P,3] fp32.
+ *   gamma (only when gamma != 1)   got <- f(clamp(got, min 1e-10)), ref <- f(ref);  f = sqrt at gamma == 0.5, pow(., gamma) otherwise
+ *   tone map (when tone_map != 0)  v <- v / (1 + v) on both
+ *   spaces                         rgb: v;  hsv: (0, 0, max v) -- what the reference's rgb2hsv returns --;  luminance: one channel,
+ *                                  0.2126 r + 0.7152 g + 0.0722 b;  xyz: the CIE matrix / 0.17697
+ *   per space                      l2 = mean d^2, l1 = mean |d|, rmse = sqrt(clamp(l2, min 1e-10)) over P x channels (hsv: 3, luminance: 1)
+ *   loss                           mean over the spaces of the mean over the functions
+ * A NaN in got makes the loss NaN.  spaces / fns are non-empty masks of NA_SPACE_* / NA_LOSS_*, P >= 1, gamma finite and > 0 (else
+ * NA_EINVAL); a NULL pointer is NA_ENULL.  No floating-point atomics: every result is bit-identical from run to run in every mode.
+ * na_image_loss_workspace_bytes  the bytes of workspace na_image_loss needs for P pixels (0 for a P it refuses): a 64-byte header and
+ *                                eight partial sums per workgroup.
+ * na_image_loss                  ONE launch: out[0] = the loss, stats[8] = (mean d^2 of the four spaces in bit order, then mean |d|;
+ *                                0 for a space that is off): what the backward needs.  The workspace's first word is an arrival
+ *                                counter: it must be 0 before the first call and every call leaves it 0 (one workspace serves any
+ *                                number of calls in stream order).  A workspace smaller than the query's answer is NA_EWORKSPACE,
+ *                                returned before anything is written.
+ * na_image_loss_backward         ONE launch, elementwise: g_got [P,3] = g_up[0] d loss / d got (g_up a device scalar; ref takes none)
+ *                                from got, ref and the forward's stats.  Per channel d a / d x = gamma a / x at x >= 1e-10 and exactly 0
+ *                                below, d b / d a = 1 / (1 + a)^2; hsv's term goes to the arg-max channel, the lowest index on a tie;
+ *                                |d| takes the gradient 0 at d = 0 and the rmse term is exactly 0 while l2 < 1e-10.               */
+enum { NA_SPACE_RGB = 1, NA_SPACE_HSV = 2, NA_SPACE_LUMINANCE = 4, NA_SPACE_XYZ = 8 };
+enum { NA_LOSS_L2 = 1, NA_LOSS_L1 = 2, NA_LOSS_RMSE = 4 };
+size_t na_image_loss_workspace_bytes(int64_t P);
+int na_image_loss(const float* got, const float* ref, int64_t P, int spaces, int fns, float gamma, int tone_map, float* out, float* stats,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int na_image_loss_backward(const float* got, const float* ref, int64_t P, int spaces, int fns, float gamma, int tone_map, const float* stats,
+                           const float* g_up, float* g_got, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -287,6 +287,9 @@ SIGNATURES = {
     "na_ssim": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_int, C.c_float, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "na_ssim_backward": (C.c_int, [c_f32p, c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_int, C.c_float, c_f32p, C.c_void_p]),
     "na_image_halve": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_void_p]),
+    "na_image_loss_workspace_bytes": (C.c_size_t, [c_i64]),
+    "na_image_loss": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_float, C.c_int, c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "na_image_loss_backward": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_float, C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p]),
 }
 
 _lib = None

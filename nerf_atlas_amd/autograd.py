@@ -706,3 +706,20 @@ class SSIMFn(Function):
     def backward(ctx, g):
         x, y = ctx.saved_tensors
         return ops.ssim_backward(x, y, g.contiguous(), 1.0, ctx.flag), None, None
+
+
+class ImageLossFn(Function):
+    """the reference's loss wrapper of got against ref [..., 3] (ops.image_loss: one launch); backward is ops.image_loss_backward, one
+    elementwise launch that reads the upstream scalar on the device.  The gradient goes to got only: ref is the label."""
+
+    @staticmethod
+    def forward(ctx, got, ref, loss_fns, color_spaces, tone_map, gamma):
+        ctx.cfg = (tuple(loss_fns), tuple(color_spaces), bool(tone_map), float(gamma))
+        loss, stats = ops.image_loss(got, ref, *ctx.cfg)
+        ctx.save_for_backward(got, ref, stats)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        got, ref, stats = ctx.saved_tensors
+        return ops.image_loss_backward(got, ref, stats, g.contiguous(), *ctx.cfg), None, None, None, None, None

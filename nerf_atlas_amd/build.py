@@ -46,6 +46,7 @@ UNITS = [
     ("dyn_voxel_div.hip", [], ""),
     ("grid_ops.hip", [], ""),
     ("ssim.hip", [], ""),
+    ("image_loss.hip", [], ""),
     ("optim.hip", [], ""),
     ("backward.hip", [], ""),
     ("train_gemm.hip", [], ""),

@@ -2396,3 +2396,70 @@ def ms_ssim(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, flag: str
             else:
                 vals.append(s)
         return ms_ssim_combine(torch.stack(vals, dim=0))
+
+
+# ------------------------------------------------------------------------------------------------- the loss wrapper (csrc/image_loss.hip)
+IMAGE_SPACES = {"rgb": 1, "hsv": 2, "luminance": 4, "xyz": 8}   # NA_SPACE_*
+IMAGE_LOSS_FNS = {"l2": 1, "l1": 2, "rmse": 4}                   # NA_LOSS_*
+_image_loss_ws = {}  # (device index, stream) -> the zeroed workspace na_image_loss leaves zeroed (its arrival counter)
+
+
+def image_loss_masks(loss_fns, color_spaces, gamma, flag: str = "ops.image_loss"):
+    """(mask of spaces, mask of functions, gamma) of the names of --color-spaces / --loss-fns and of --gamma-correct-loss; anything the
+    kernel has no form for raises a ValueError that names it"""
+    masks = []
+    for names, table, what in ((color_spaces, IMAGE_SPACES, "--color-spaces"), (loss_fns, IMAGE_LOSS_FNS, "--loss-fns")):
+        names = list(names)
+        if not names:
+            raise ValueError(f"{flag}: {what} is empty, must provide at least 1")
+        bad = [n for n in names if n not in table]
+        if bad:
+            raise ValueError(f"{flag}: {what} {bad[0]!r} is not one of {sorted(table)}")
+        if len(set(names)) != len(names):
+            raise ValueError(f"{flag}: {what} {names} names an entry twice")
+        masks.append(sum(table[n] for n in names))
+    gamma = float(gamma)
+    if not (gamma > 0 and gamma != float("inf")):
+        raise ValueError(f"{flag}: --gamma-correct-loss {gamma} must be finite and > 0")
+    return masks[0], masks[1], gamma
+
+
+def _image_pair(got: torch.Tensor, ref: torch.Tensor, flag: str):
+    if got.shape != ref.shape or got.dim() < 1 or got.shape[-1] != 3 or got.numel() == 0:
+        raise ValueError(f"{flag}: two images [..., 3] of one shape with at least one pixel, got {tuple(got.shape)} and {tuple(ref.shape)}")
+    return _f32(got, "got"), _f32(ref, "ref"), got.numel() // 3
+
+
+def image_loss(got: torch.Tensor, ref: torch.Tensor, loss_fns=("l2",), color_spaces=("rgb",), tone_map: bool = False, gamma: float = 1.0,
+               flag: str = "ops.image_loss"):
+    """(loss, stats[8]) of got, ref [..., 3]: the mean over color_spaces of the mean over loss_fns, after the gamma step and the tone
+    map (the reference's loss wrapper).  ONE launch, no host synchronisation, bit-identical from run to run; stats feeds the backward."""
+    lib = _lib.load()
+    spaces, fns, gamma = image_loss_masks(loss_fns, color_spaces, gamma, flag)
+    got, ref, P = _image_pair(got, ref, flag)
+    nbytes = int(lib.na_image_loss_workspace_bytes(P))
+    key = (got.device.index, torch.cuda.current_stream().cuda_stream)
+    ws = _image_loss_ws.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _image_loss_ws[key] = torch.zeros(max(nbytes // 4, 1024), device=got.device, dtype=torch.float32)
+    out = torch.empty((), device=got.device, dtype=torch.float32)
+    stats = torch.empty(8, device=got.device, dtype=torch.float32)
+    check(lib.na_image_loss(_ptr(got), _ptr(ref), P, spaces, fns, gamma, int(bool(tone_map)), _ptr(out), _ptr(stats), _ptr(ws), ws.numel() * 4,
+                            _stream()))
+    return out, stats
+
+
+def image_loss_backward(got: torch.Tensor, ref: torch.Tensor, stats: torch.Tensor, g_up: torch.Tensor, loss_fns=("l2",), color_spaces=("rgb",),
+                        tone_map: bool = False, gamma: float = 1.0, flag: str = "ops.image_loss") -> torch.Tensor:
+    """g_got (shaped like got) = g_up d loss / d got from the forward's stats; g_up is a device scalar the kernel reads.  ONE launch,
+    every element written once"""
+    lib = _lib.load()
+    spaces, fns, gamma = image_loss_masks(loss_fns, color_spaces, gamma, flag)
+    shape = got.shape
+    got, ref, P = _image_pair(got, ref, flag)
+    stats, g_up = _f32(stats, "stats"), _f32(g_up, "g_up")
+    if stats.numel() != 8 or g_up.numel() != 1:
+        raise ValueError(f"{flag}: stats of 8 floats and a scalar g_up, got {tuple(stats.shape)} and {tuple(g_up.shape)}")
+    out = torch.empty(P, 3, device=got.device, dtype=torch.float32)
+    check(lib.na_image_loss_backward(_ptr(got), _ptr(ref), P, spaces, fns, gamma, int(bool(tone_map)), _ptr(stats), _ptr(g_up), _ptr(out), _stream()))
+    return out.view(shape)

@@ -1,5 +1,6 @@
 """Training and evaluation loops with the reference's recipe (runner.py:609-850 train, :855-995 test,
-:1221-1322 main), restricted to what the five hot-path configs use: l2/l1/rmse loss in RGB and `--loss-fns ssim`, Adam(eps 1e-7) with the
+:1221-1322 main), restricted to what the five hot-path configs use: l2/l1/rmse loss and `--loss-fns ssim`, the loss wrapper `--color-spaces` /
+`--tone-map` / `--gamma-correct-loss` / `--autogamma-correct-loss` (one HIP launch each way), Adam(eps 1e-7) with the
 cosine schedule, random crops/views from Python's `random`, pixel jitter 0.1, stratified sampling and density noise
 in training mode, `--volsdf-scale-decay`, `--delta-x-decay`, `--offset-decay`, `--sdf-eikonal` (SDF normals by forward-mode
 tangents through the MLP), `--smooth-normals` in the reference's default epsilon-perturbation form (`--smooth-eps`,
@@ -15,6 +16,7 @@ With `replay_reference_rng=True` the stochastic tensors come from torch's CPU ge
 against tests/golden/train_parity_*.json).
 """
 import argparse
+import math
 import os
 import random
 import re
@@ -51,6 +53,8 @@ DEFAULTS = dict(
     depth_images=False, flow_map=False, rigidity_map=False, with_alpha=False,  # runner.py:360-392: maps next to the test frames
     render_over_time=-1, render_over_time_steps=100, render_over_time_end_sec=1.0,  # runner.py:252-261: a time sweep of one test camera
     msssim_loss=False,  # runner.py:359, :985-990: report ms-ssim next to the PSNR summary
+    # runner.py:100-113, 552-594, 1159-1170: the layers the reference wraps around --loss-fns
+    color_spaces=["rgb"], tone_map=False, gamma_correct_loss=1.0, autogamma_correct_loss=False,
 )
 
 def ssim_loss(x, ref):
@@ -198,12 +202,77 @@ def load_model(args, is_dyn=False, device="cuda"):
     return model.to(device)
 
 
+def image_loss_torch(got, ref, loss_fns=("l2",), color_spaces=("rgb",), tone_map=False, gamma=1.0):
+    """The loss ops.image_loss computes, composed from torch operators in the dtype and on the device of its arguments: what a CPU
+    fit() trains with, and the wiring's reference in the tests (the definition: include/nerf_atlas_amd.h)."""
+    from . import ops
+    ops.image_loss_masks(loss_fns, color_spaces, gamma, "image_loss_torch")
+    if gamma != 1.0:
+        got = got.clamp(min=1e-10)
+        got, ref = (got.sqrt(), ref.sqrt()) if gamma == 0.5 else (got.pow(gamma), ref.pow(gamma))
+    if tone_map:
+        got, ref = got / (1 + got), ref / (1 + ref)
+    xyz = torch.tensor([[0.49, 0.31, 0.2], [0.17697, 0.8124, 0.01063], [0.0, 0.01, 0.99]], dtype=torch.float32, device=got.device).to(got.dtype)
+
+    def space(name, v):
+        if name == "rgb":
+            return v
+        if name == "luminance":
+            return 0.2126 * v[..., 0:1] + 0.7152 * v[..., 1:2] + 0.0722 * v[..., 2:3]
+        if name == "xyz":
+            return (v.reshape(-1, 3) @ xyz.T) / 0.17697
+        top = v.max(dim=-1).values  # hsv: the reference's rgb2hsv returns (0, 0, max)
+        return torch.stack([torch.zeros_like(top), torch.zeros_like(top), top], dim=-1)
+    total = 0
+    for name in color_spaces:
+        a, b = space(name, got), space(name, ref)
+        total = total + sum(loss_map[k](a, b) for k in loss_fns) / len(loss_fns)
+    return total / len(color_spaces)
+
+
+def image_loss_is_default(args) -> bool:
+    """none of --color-spaces / --tone-map / --gamma-correct-loss changes what --loss-fns alone computes"""
+    return (list(getattr(args, "color_spaces", ["rgb"])) == ["rgb"] and not getattr(args, "tone_map", False)
+            and getattr(args, "gamma_correct_loss", 1.0) == 1.0)
+
+
 def load_loss_fn(args):
-    fns = [loss_map[k] for k in args.loss_fns]
-    assert len(fns) > 0, "must provide at least 1 loss function"
-    if len(fns) == 1:
-        return fns[0]
-    return lambda x, ref: sum(fn(x, ref) for fn in fns) / len(fns)
+    if image_loss_is_default(args):
+        fns = [loss_map[k] for k in args.loss_fns]
+        assert len(fns) > 0, "must provide at least 1 loss function"
+        if len(fns) == 1:
+            return fns[0]
+        return lambda x, ref: sum(fn(x, ref) for fn in fns) / len(fns)
+    # the rest of the reference's wrapper (runner.py:566-594): one HIP launch each way (ag.ImageLossFn, DESIGN.md 3u)
+    from . import ops
+    loss_fns, spaces, tone_map, gamma = list(args.loss_fns), list(args.color_spaces), bool(args.tone_map), args.gamma_correct_loss
+    if "ssim" in loss_fns:
+        raise ValueError("--loss-fns ssim together with --color-spaces / --tone-map / --gamma-correct-loss: the reference hands its "
+                         "channel-first SSIM a colour-converted channel-last crop, there is nothing to reproduce (DESIGN.md 7)")
+    ops.image_loss_masks(loss_fns, spaces, gamma, "load_loss_fn")
+    gamma = float(gamma)
+
+    def loss_fn(x, ref):
+        if not x.is_cuda:
+            return image_loss_torch(x, ref, loss_fns, spaces, tone_map, gamma)
+        return ag.ImageLossFn.apply(x.contiguous(), ref.contiguous(), loss_fns, spaces, tone_map, gamma)
+    return loss_fn
+
+
+def auto_gamma(args, labels):
+    """--autogamma-correct-loss (runner.py:1159-1170): --gamma-correct-loss from the labels' mean, on the host, once before training.
+    A dynamic dataset's labels are a tuple; the mean is the image tensor's (the reference raises there: DESIGN.md 7)."""
+    if not getattr(args, "autogamma_correct_loss", False):
+        return
+    images = labels[0] if type(labels) is tuple else labels
+    weight = (math.log(0.5) / images.mean().log()).clamp(min=0).item()
+    if weight < 0.55:
+        weight = 0.5
+    if weight >= 0.9:
+        print(f"[note]: autogamma correct would darken/hardly change image ({weight}), ignoring.")
+    else:
+        args.gamma_correct_loss = weight
+        print(f"[note]: autogamma correction weight is: {weight}")
 
 
 class _OneLaunchStep:
@@ -721,6 +790,7 @@ def fit(args, device="cuda", replay_reference_rng=False, init=None, on_iter=None
             cam = cam[:args.train_imgs]
         model.nerf.steps, model.nerf.t_near, model.nerf.t_far = args.steps, args.near, args.far  # set_per_run :1048-1050
         unset_voxel_tv(args, model)
+        auto_gamma(args, labels)
         opt = load_optim(args, model.parameters())
         sched = None if args.no_sched else torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=args.epochs,
                                                                                        eta_min=args.sched_min)

@@ -1359,9 +1359,54 @@ def g29():
              divergence=r64["divergence"], g_ctrl=r64["g_ctrl"], dev=np.array([dev[k] for k in ("div_approx", "divergence", "g_ctrl", "dp")]))
 
 
+IMAGE_LOSS_PROVENANCE = (
+    "g30_image_loss.npz: tools/gen_golden.py g30 -- the reference's runner.load_loss_fn over tests/image_loss_ref.py COMBOS, CPU fp32\n"
+    "train_parity_voxel_image_loss.json: tools/ref_train_fixture.py voxel_image_loss --epochs 200 --size 32 --crop-size 16 --steps 32 "
+    "--batch-size 4 -- the reference's runner.main, CPU fp32, 8 threads\n")
+
+
+def g30():
+    """g30_image_loss: the reference's own runner.load_loss_fn(args, None) (runner.py:552-594) over the table of flag combinations of
+    tests/image_loss_ref.py (COMBOS), in fp32, on that module's kink-free draw at P = 1025 and its hand-made edge set at P = 7: the
+    loss and d loss / d got, and next to them the deviation of that fp32 result from the module's fp64 restatement (`g_dev`: per
+    combination and input set the loss's and the gradient's largest absolute deviation; rgb2xyz builds an fp32 matrix and cannot run
+    in fp64 itself)."""
+    import types as _types
+    import runner
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import image_loss_ref as R
+    sets = {"draw": R.kink_free_draw(1025, 30), "edge": R.edge_set()}
+    out = dict(combos=np.array([R.combo_name(c) for c in R.COMBOS]))
+    dev = np.zeros((len(R.COMBOS), 2, 2))
+    for si, (sname, (got, ref)) in enumerate(sets.items()):
+        out[f"{sname}_got"], out[f"{sname}_ref"] = got, ref
+        losses, grads = [], []
+        for ci, (fns, spaces, tone, gamma) in enumerate(R.COMBOS):
+            args = _types.SimpleNamespace(style_img=None, loss_fns=list(fns), color_spaces=list(spaces), tone_map=tone,
+                                          gamma_correct_loss=gamma, volsdf_alternate=False, model="plain")
+            fn = runner.load_loss_fn(args, None)
+            with torch.enable_grad():
+                x = torch.from_numpy(got).clone().requires_grad_(True)
+                loss = fn(x, torch.from_numpy(ref))
+                g, = torch.autograd.grad(loss, x)
+            r = R.restate(got, ref, fns, spaces, tone, gamma)
+            losses.append(float(loss))
+            grads.append(g.numpy())
+            dev[ci, si] = abs(float(loss) - r["loss"]), np.abs(g.numpy().astype(np.float64) - r["grad"]).max()
+            over = max(dev[ci, si, 0] / max(r["loss_bound"], 1e-300), float((np.abs(g.numpy() - r["grad"]) / np.maximum(r["grad_bound"], 1e-300))
+                                                                            [r["grad_bound"] > 0].max(initial=0.0)))
+            print(f"g30 {sname:4s} {R.combo_name((fns, spaces, tone, gamma)):44s} loss {float(loss):.6f} dev {dev[ci, si, 0]:.1e} "
+                  f"grad dev {dev[ci, si, 1]:.1e}  worst dev / bound {over:.2f}")
+        out[f"{sname}_loss"], out[f"{sname}_grad"] = np.array(losses, np.float32), np.stack(grads).astype(np.float32)
+    save("g30_image_loss", g_dev=dev, **out)
+    # the two image-loss fixtures' provenance lines, in a file of their own next to PROVENANCE.txt (which describes the generator's build)
+    with open(os.path.join(OUT, "PROVENANCE_image_loss.txt"), "w") as f:
+        f.write(IMAGE_LOSS_PROVENANCE)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25", "g26", "g27", "g28", "g29"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23", "g24", "g25", "g26", "g27", "g28", "g29", "g30"]
     for g in which:
         globals()[g]()
     with open(os.path.join(OUT, "PROVENANCE.txt"), "w") as f:

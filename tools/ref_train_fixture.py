@@ -19,6 +19,7 @@ Runs only in the build container; nothing of the reference is copied or travels.
 import argparse
 import json
 import os
+import re
 import sys
 import tempfile
 import time
@@ -68,6 +69,13 @@ RECIPES = {
     # times the parity bar (2e-3) within the first 50 iterations: the fixture then pins the terms, not only the stream position.
     "voxel_tv": (False, ["--model", "voxel", "--refl-kind", "pos", "--loss-fns", "l2", "-lr", "5e-2", "--voxel-tv-sigma", "0.02",
                          "--voxel-tv-rgb", "0.02"]),
+    # the `voxel` recipe under the rest of the reference's loss wrapper (runner.py:552-594, src/utils.py:198-204, 279-314): two loss functions
+    # in three colour spaces, tone-mapped, under a square-root gamma.  Recorded with the `voxel` recipe's flags; the fixture also carries
+    # that recipe's trajectory (`losses_without_flags`, copied from train_parity_voxel.json after checking that the two argv differ in
+    # the four loss flags only) and asserts that the two curves separate by ten times the parity bar (2e-4) within the first 10
+    # iterations: the fixture then pins the loss, not only the stream position.
+    "voxel_image_loss": (False, ["--model", "voxel", "--refl-kind", "pos", "--loss-fns", "l2", "rmse", "-lr", "5e-2", "--color-spaces", "rgb",
+                                 "xyz", "hsv", "--tone-map", "--gamma-correct-loss", "0.5"]),
     # the `voxel` recipe under the other optimisers of the reference's table (runner.py:440-458: --opt-kind rmsprop / adamw / sgd; eps
     # 1e-7, AdamW with torch's default decay 1e-2).  Recorded with the `voxel` recipe's flags.  Each kind at a rate at which it learns on
     # this scene in 200 iterations: SGD at rates 1 .. 500 does not leave the start (the l2 gradient of a voxel is ~1e-6).
@@ -378,6 +386,28 @@ def main():
         fixture["losses_without_tv"] = base["losses"]
         sep = np.abs(np.array(fixture["losses"][:50]) - np.array(base["losses"][:50])).max()
         print(f"voxel_tv: the trajectories with and without the terms separate by {sep:.2e} within the first 50 iterations")
+    if cfg.name == "voxel_image_loss":
+        with open(os.path.join(REPO, "tests", "golden", "train_parity_voxel.json")) as f:
+            base = json.load(f)
+        loss_flags = ("--loss-fns", "--color-spaces", "--tone-map", "--gamma-correct-loss")
+
+        def drop(av):  # (a loss flag and the values behind it)
+            out, skipping = [], False
+            for x in av:
+                if x in loss_flags:
+                    skipping = True
+                elif skipping and not (x.startswith("-") and not re.fullmatch(r"-?[0-9.e+-]+", x)):
+                    continue
+                else:
+                    skipping = False
+                    out.append(x)
+            return out
+        assert drop(fixture["argv"]) == drop(base["argv"]) and base["seed"] == cfg.seed, "record voxel_image_loss with the flags of the voxel fixture"
+        fixture["losses_without_flags"] = base["losses"]
+        sep = float(np.abs(np.array(fixture["losses"][:10]) - np.array(base["losses"][:10])).max())
+        fixture["separation_first10"] = sep
+        print(f"voxel_image_loss: the curves with and without the four flags separate by {sep:.2e} within the first 10 iterations")
+        assert sep > 10 * 2e-4, "the two reference curves do not separate: the fixture would pin only the stream position"
     path = cfg.out or os.path.join(REPO, "tests", "golden", f"train_parity_{cfg.name}.json")
     with open(path, "w") as f:
         json.dump(fixture, f, indent=1)
