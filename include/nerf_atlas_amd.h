@@ -891,6 +891,35 @@ int na_voxel_sh_render(const float* rays, const float* pts, int64_t R, const flo
                        int S, int C, int order, double grid_radius, int act_kind, int bg_kind, float* alpha, float* weights, float* out,
                        void* stream);
 
+/* NeRFVoxel coarse -> fine (`--voxel-steps-fine`, this build's flag; csrc/voxel_fine.hip): a proposal pass over the density
+ * grid alone, na_resample_ts, and a fine pass over every ray's own merged row.
+ * na_voxel_proposal          one launch: alpha (NULL or [T,R]) and weights [T,R] of rays [R,6] over the shared steps ts [T], from densities
+ *                            [S,S,S,1] only -- bit for bit the alpha / weights of na_voxel_render / na_voxel_plv_render /
+ *                            na_voxel_sh_render on the same rays, steps and density grid (softplus density, black background).
+ * na_voxel_render_rayts      na_voxel_render / na_voxel_plv_render / na_voxel_sh_render over PER-RAY steps ts_ray [R,M] (one increasing row
+ * na_voxel_plv_render_rayts  per ray: `merged` of na_resample_ts) in the place of ts [T]; positions are o + t d (there are no explicit
+ * na_voxel_sh_render_rayts   pts).  Step lengths are max(ts_ray[r,t+1] - ts_ray[r,t], 1e-5) |d|, the closing one 1e10 |d|.  out [R,3]
+ *                            is required, alpha / weights are NULL or [M,R]; bg black or white.  Rows that all equal one shared row
+ *                            give the shared-step renderer's three outputs bit for bit.
+ * na_voxel_fine_lanes        any of the four with the number of lanes that share a ray named (4, 8, 16, 32, 64; measurements):
+ *                            head NA_VOX_HEAD_*, shared_row != 0 reads ts_ray as one [M] row for every ray.
+ * Codes as the shared-step renderers': NA_EINVAL shapes / resolution / order / grid_radius / C of the SH head / alignment, NA_ENULL,
+ * NA_EUNSUPPORTED activation / bg / C != 3 of the RGB head; R == 0 is NA_OK.                                                          */
+enum { NA_VOX_HEAD_RGB = 0, NA_VOX_HEAD_PLV = 1, NA_VOX_HEAD_SH = 2, NA_VOX_HEAD_DENSITY = 3 };
+int na_voxel_proposal(const float* rays, int64_t R, const float* ts, int T, const float* densities, int S, double grid_radius, float* alpha,
+                      float* weights, void* stream);
+int na_voxel_render_rayts(const float* rays, int64_t R, const float* ts_ray, int M, const float* densities, const float* rgb, int S, int C,
+                          double grid_radius, int act_kind, int bg_kind, float* alpha, float* weights, float* out, void* stream);
+int na_voxel_plv_render_rayts(const float* rays, int64_t R, const float* ts_ray, int M, const float* densities, const float* rgb, int S,
+                              int order, double grid_radius, int act_kind, int bg_kind, float* alpha, float* weights, float* out,
+                              void* stream);
+int na_voxel_sh_render_rayts(const float* rays, int64_t R, const float* ts_ray, int M, const float* densities, const float* rgb, int S, int C,
+                             int order, double grid_radius, int act_kind, int bg_kind, float* alpha, float* weights, float* out,
+                             void* stream);
+int na_voxel_fine_lanes(int head, int order, int lanes, int shared_row, const float* rays, int64_t R, const float* ts_ray, int M,
+                        const float* densities, const float* rgb, int S, double grid_radius, int act_kind, int bg_kind, float* alpha,
+                        float* weights, float* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * DynamicNeRFVoxel (src/nerf.py:1526-1586; csrc/dyn_voxel.hip): the deformation of a voxel D-NeRF.  ctrl_pts_grid [S,S,S,3(n-1)] holds
  * control points 1 .. n-1 of a Bezier spline per voxel (control point 0 is zero), rigidity_grid [S,S,S,1] a rigidity logit; both are

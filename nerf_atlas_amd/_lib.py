@@ -261,6 +261,15 @@ SIGNATURES = {
                                                   C.c_double, c_f32p, C.c_void_p]),
     "na_voxel_sh_render": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                      C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "na_voxel_proposal": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_int, c_f32p, C.c_int, C.c_double, c_f32p, c_f32p, C.c_void_p]),
+    "na_voxel_render_rayts": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                        c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "na_voxel_plv_render_rayts": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                            c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "na_voxel_sh_render_rayts": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                           C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "na_voxel_fine_lanes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_double,
+                                      C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "na_dyn_voxel_sh_render": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_double, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                          C.c_void_p]),

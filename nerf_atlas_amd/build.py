@@ -40,6 +40,7 @@ UNITS = [
     ("voxel.hip", [], ""),
     ("voxel_plv.hip", [], ""),
     ("voxel_sh.hip", [], ""),
+    ("voxel_fine.hip", [], ""),
     ("dyn_voxel.hip", [], ""),
     ("dyn_voxel_render.hip", [], ""),
     ("spline_len.hip", [], ""),

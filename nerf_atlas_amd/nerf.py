@@ -646,6 +646,8 @@ class NeRFVoxel(CommonNeRF):
       eval, no gradients  ops.voxel_render: positions, lookup, activation and compositing as ONE launch (two with bg "random")
       otherwise           autograd.VoxelSampleFn (lookup; its backward is the scatter-add into the two grids), the head's activation on
                           the colour columns (autograd.SigmoidFn), CommonNeRF._composite's nodes
+    `steps_fine > 0` (`--voxel-steps-fine`, this build's flag; a plain attribute, not in the state_dict): `forward` renders coarse -> fine
+    (`forward_coarse_fine`: a density-only proposal pass, ops.resample_ts, the fine pass over per-ray steps on the same two routes).
     There is no density noise (the reference class has no noise_std).  Explicit positions that require a gradient (from_pts under
     DynamicNeRFVoxel) receive one from the lookup's node; the positions o + t d of `forward` are formed in the kernels and have none."""
 
@@ -663,6 +665,7 @@ class NeRFVoxel(CommonNeRF):
         self.voxel_len = grid_radius * 2 / resolution
         self.brdf = self._bare_brdf
         self._head = None
+        self.steps_fine = 0  # > 0: forward renders coarse -> fine over steps + steps_fine samples per ray (forward_coarse_fine)
 
     def _bare_brdf(self, params, view):
         """src/nerf.py:425: before a head is installed the colour is act(parameters)"""
@@ -788,11 +791,47 @@ class NeRFVoxel(CommonNeRF):
         return self._composite(density, self.brdf(params=params.contiguous(), view=r_d), ts, rays)
 
     def forward(self, rays):
+        if self.steps_fine > 0: return self.forward_coarse_fine(rays, self.steps_fine)
         r_o, r_d, self.ts, _ = compute_ts(rays, self.t_near, self.t_far, self.steps, perturb=self._perturb())
         self.ts_ray = None
         if self._fusable():
             return self._render(rays, self.ts)
         return self._operators(rays, self.ts, r_d)  # (positions o + t d are formed inside the lookup kernels, as na_compute_pts forms them)
+
+    def _render_rayts(self, rays, ts_ray):
+        """`_render` over per-ray steps: the fine pass of the eval route as one launch (two with bg "random")"""
+        kind = self._head_kind()
+        if kind == "sh":
+            out, self.alpha, self.weights = ops.voxel_sh_render_rayts(rays, ts_ray, self.densities.data, self.rgb.data, self._head.order,
+                                                                      self.grid_radius, self._act_kind(), self._kernel_bg(), True)
+            return self._finish_sky(out)
+        render = ops.voxel_plv_render_rayts if kind == "plv" else ops.voxel_render_rayts
+        out, self.alpha, self.weights = render(rays, ts_ray, self.densities.data, self.rgb.data, self.grid_radius, self._act_kind(),
+                                               self._kernel_bg(), True)
+        return self._finish_sky(out)
+
+    def forward_coarse_fine(self, rays, steps_fine: int, u=None):
+        """Coarse -> fine rendering (`--voxel-steps-fine`, this build's flag).  A proposal pass reads the DENSITY grid alone at
+        the `self.steps` shared steps (ops.voxel_proposal: the renderers' alpha / weights, no colour, no image, no graph -- the weights
+        are constants); `steps_fine` new positions per ray are drawn from them by inverse cdf (ops.resample_ts; u: the caller's
+        [steps_fine, *batch] draws, else one utils.rand draw per new sample in training mode, linspace in eval mode); the fine pass runs
+        over every ray's own merged row, on the route `_fusable` picks: one launch in eval mode without gradients, else the operators
+        (ops.compute_pts_rayts -> the head's lookup node -> CompositeRayTsFn).  There is no coarse image: the merged row contains every
+        coarse step, which so receives its gradient through the fine image.  No gradient flows through the sample positions.
+        Protocol of PlainNeRF's: `ts` the [steps] shared row, `ts_ray` [*batch, steps + steps_fine] what alpha / weights follow."""
+        rays = rays.contiguous()
+        r_o, r_d, ts, _ = compute_ts(rays, self.t_near, self.t_far, self.steps, perturb=self._perturb())
+        _, w = ops.voxel_proposal(rays, ts, self.densities.data, self.grid_radius)
+        if u is None and self.training:
+            u = utils.rand((steps_fine,) + tuple(rays.shape[:-1]), rays.device)
+        ts_ray = ops.resample_ts(ts, w, steps_fine, u)
+        if self._fusable():
+            out = self._render_rayts(rays, ts_ray)
+        else:
+            pts = ops.compute_pts_rayts(rays, ts_ray)
+            out = self._operators(rays, ts_ray, r_d, pts=pts)
+        self.ts, self.ts_ray = ts, ts_ray
+        return out
 
     def from_pts(self, pts, ts, r_o, r_d, refl_latent=None, rays=None):
         if rays is None: rays = torch.cat([r_o, r_d], dim=-1).contiguous()

@@ -1953,6 +1953,95 @@ def voxel_sh_render(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tenso
     return out, alpha, weights
 
 
+# ------------------------------------------------------------------------------------------------- NeRFVoxel coarse -> fine (csrc/voxel_fine.hip)
+VOX_HEAD = {"rgb": 0, "plv": 1, "sh": 2, "density": 3}   # include/nerf_atlas_amd.h NA_VOX_HEAD_*
+VOXEL_FINE_LANES = (4, 8, 16, 32, 64)                    # lanes per ray na_voxel_fine_lanes is instantiated for
+
+
+def voxel_proposal(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, grid_radius: float):
+    """The proposal pass of NeRFVoxel's coarse -> fine route as ONE launch: (alpha [T, ...], weights [T, ...]) of rays [..., 6] over the
+    shared steps ts [T] from the density grid [S,S,S,1] alone -- bit for bit what voxel_render / voxel_plv_render / voxel_sh_render return
+    as alpha and weights for the same rays, steps and density grid."""
+    lib = _lib.load()
+    densities, rays, ts = _f32(densities, "densities"), _f32(rays, "rays"), _f32(ts, "ts")
+    S = densities.shape[0]
+    if densities.dim() != 4 or tuple(densities.shape) != (S, S, S, 1):
+        raise ValueError(f"the density grid must be [S,S,S,1], got {tuple(densities.shape)}")
+    if S % 2 != 0 or S < 2:
+        raise ValueError(f"voxel resolution {S}: even resolutions only (the reference's ids are floor(.) + S / 2)")
+    if rays.shape[-1] != 6 or ts.dim() != 1:
+        raise ValueError(f"rays must be [..., 6] and ts [T], got {tuple(rays.shape)} and {tuple(ts.shape)}")
+    T, R = ts.shape[0], rays.numel() // 6
+    alpha = torch.empty((T,) + tuple(rays.shape[:-1]), device=rays.device, dtype=torch.float32)
+    weights = torch.empty_like(alpha)
+    check(lib.na_voxel_proposal(_ptr(rays), R, _ptr(ts), T, _ptr(densities), S, float(grid_radius), _ptr(alpha), _ptr(weights), _stream()))
+    return alpha, weights
+
+
+def _voxel_rayts(rays: torch.Tensor, ts_ray: torch.Tensor):
+    """(rays, ts_ray, R, M) of per-ray steps ts_ray [*batch, M] over rays [*batch, 6]"""
+    rays, ts_ray = _f32(rays, "rays"), _f32(ts_ray, "ts_ray")
+    assert rays.shape[-1] == 6 and ts_ray.dim() >= 1 and tuple(ts_ray.shape[:-1]) == tuple(rays.shape[:-1]), (ts_ray.shape, rays.shape)
+    return rays, ts_ray, rays.numel() // 6, ts_ray.shape[-1]
+
+
+def voxel_render_rayts(rays: torch.Tensor, ts_ray: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float,
+                       sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True):
+    """`voxel_render` over per-ray steps ts_ray [..., M] (one increasing row per ray, e.g. `resample_ts`'s): positions o + t d -> lookup ->
+    activation -> compositing as ONE launch.  (out [..., 3], alpha [M, ...], weights [M, ...]); bg black | white."""
+    lib = _lib.load()
+    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
+    rays, ts_ray, R, M = _voxel_rayts(rays, ts_ray)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], M, rays.device, bg, want_weights)
+    check(lib.na_voxel_render_rayts(_ptr(rays), R, _ptr(ts_ray), M, _ptr(densities), _ptr(rgb), S, Cn, float(grid_radius),
+                                    SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
+    return out, alpha, weights
+
+
+def voxel_plv_render_rayts(rays: torch.Tensor, ts_ray: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float,
+                           sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True):
+    """`voxel_plv_render` over per-ray steps ts_ray [..., M]; outputs and backgrounds of voxel_render_rayts."""
+    lib = _lib.load()
+    densities, rgb, S, order = _voxel_plv_grid(densities, rgb)
+    rays, ts_ray, R, M = _voxel_rayts(rays, ts_ray)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], M, rays.device, bg, want_weights)
+    check(lib.na_voxel_plv_render_rayts(_ptr(rays), R, _ptr(ts_ray), M, _ptr(densities), _ptr(rgb), S, order, float(grid_radius),
+                                        SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
+    return out, alpha, weights
+
+
+def voxel_sh_render_rayts(rays: torch.Tensor, ts_ray: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, order: int, grid_radius: float,
+                          sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True):
+    """`voxel_sh_render` over per-ray steps ts_ray [..., M]; outputs and backgrounds of voxel_render_rayts."""
+    lib = _lib.load()
+    densities, rgb, S, Cn = _voxel_sh_grid(densities, rgb, order)
+    rays, ts_ray, R, M = _voxel_rayts(rays, ts_ray)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], M, rays.device, bg, want_weights)
+    check(lib.na_voxel_sh_render_rayts(_ptr(rays), R, _ptr(ts_ray), M, _ptr(densities), _ptr(rgb), S, Cn, order, float(grid_radius),
+                                       SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
+    return out, alpha, weights
+
+
+def voxel_fine_lanes(head: str, lanes: int, rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: Optional[torch.Tensor],
+                     grid_radius: float, order: int = -1, sigmoid_kind: str = "upshifted", bg: str = "black"):
+    """Measurements (tools/voxel_fine_bench.py): the proposal (head "density", ts [T]) or a per-ray-step render (head "rgb" | "plv" | "sh",
+    ts [..., M]) with `lanes` lanes sharing a ray.  (out or None, alpha, weights)."""
+    lib = _lib.load()
+    densities, rays, ts = _f32(densities, "densities"), _f32(rays, "rays"), _f32(ts, "ts")
+    S, R, M = densities.shape[0], rays.numel() // 6, ts.shape[-1]
+    shared = head == "density"
+    assert ts.numel() == (M if shared else R * M), (ts.shape, rays.shape)
+    if not shared:
+        rgb = _aligned16(_f32(rgb, "rgb"))
+        want = {"rgb": 3, "plv": 3 + (order + 1) ** 2, "sh": 3 * (order + 1) ** 2}[head]
+        assert tuple(rgb.shape) == (S, S, S, want), (rgb.shape, head, order)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], M, rays.device, bg, True)
+    check(lib.na_voxel_fine_lanes(VOX_HEAD[head], int(order), int(lanes), 1 if shared else 0, _ptr(rays), R, _ptr(ts), M, _ptr(densities),
+                                  _ptr(None if shared else rgb), S, float(grid_radius), SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha),
+                                  _ptr(weights), _ptr(None if shared else out), _stream()))
+    return (None if shared else out), alpha, weights
+
+
 # ------------------------------------------------------------------------------------------------- DynamicNeRFVoxel (csrc/dyn_voxel.hip)
 def _dyn_voxel_grids(ctrl_pts_grid: torch.Tensor, rigidity_grid: torch.Tensor, spline: int):
     """S of ctrl_pts_grid [S,S,S,3(spline-1)] and rigidity_grid [S,S,S,1]"""

@@ -6,7 +6,7 @@ in training mode, `--volsdf-scale-decay`, `--delta-x-decay`, `--offset-decay`, `
 tangents through the MLP), `--smooth-normals` in the reference's default epsilon-perturbation form (`--smooth-eps`,
 `--smooth-eps-rng`, `--smooth-n-ord`), `--dyn-diverge-decay` (one differentiable direction tangent), `--ffjord-div-decay`
 (forward-mode divergence estimate), `--voxel-tv-sigma` / `--voxel-tv-rgb` (total variation of NeRFVoxel's grids) and this build's
-`--voxel-upsample ITER:RESO`; over `--dyn-model voxel` also `--voxel-tv-bezier` / `--voxel-tv-rigidity`; `--smooth-normals --smooth-eps 0` (double backward) raises.
+`--voxel-upsample ITER:RESO` and `--voxel-steps-fine N` (coarse -> fine sampling of --model voxel); over `--dyn-model voxel` also `--voxel-tv-bezier` / `--voxel-tv-rigidity`; `--smooth-normals --smooth-eps 0` (double backward) raises.
 The test loop also renders the maps of `--depth-images` / `--flow-map` / `--rigidity-map` (render.render_frame_maps; one launch per tile for
 the voxel D-NeRF) and, with `--msssim-loss`, computes SSIM per view and MS-SSIM of the test set (HIP kernels); `--render-over-time` and `--with-alpha` are read by runner.main.
 
@@ -50,6 +50,7 @@ DEFAULTS = dict(
     voxel_upsample=[],  # this build's flag: ITER:RESO pairs, NeRFVoxel.upsample(RESO) at the start of iteration ITER
     voxel_refl_order=None,  # this build's flag: order K (0..4) of the per-voxel pos-linear-view head, the reference's hard-coded 4
     voxel_sh_order=None,  # this build's flag: order K (0..4) of the per-voxel spherical-harmonic colour head
+    voxel_steps_fine=0,  # this build's flag: N resampled steps per ray, --model voxel renders coarse -> fine over steps + N
     depth_images=False, flow_map=False, rigidity_map=False, with_alpha=False,  # runner.py:360-392: maps next to the test frames
     render_over_time=-1, render_over_time_steps=100, render_over_time_end_sec=1.0,  # runner.py:252-261: a time sweep of one test camera
     msssim_loss=False,  # runner.py:359, :985-990: report ms-ssim next to the PSNR summary
@@ -164,6 +165,26 @@ def check_voxel_sh_order(args):
         raise ValueError(f"--voxel-sh-order {k} with --refl-kind {args.refl_kind}: the flag belongs to --refl-kind sph-har")
 
 
+def check_voxel_steps_fine(args, is_dyn=False) -> int:
+    """--voxel-steps-fine N: NeRFVoxel.steps_fine, coarse -> fine rendering of the static --model voxel (a density-only proposal pass,
+    N resampled steps per ray, one fine image and no coarse one: DESIGN.md 3v).  Anything it cannot apply to raises by name.
+    --steps-fine (PlainNeRF's joint coarse + fine loss) is another flag with other semantics and keeps refusing --model voxel."""
+    n = getattr(args, "voxel_steps_fine", 0) or 0
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        raise ValueError(f"--voxel-steps-fine {n!r}: the number of resampled steps per ray is a non-negative integer")
+    if n == 0:
+        return 0
+    if int(getattr(args, "steps_fine", 0) or 0) != 0:
+        raise ValueError(f"--voxel-steps-fine {n} with --steps-fine {args.steps_fine}: --steps-fine trains PlainNeRF on a joint coarse + fine "
+                         "loss, --voxel-steps-fine renders --model voxel coarse -> fine with one image; give one of them")
+    if args.model != "voxel":
+        raise ValueError(f"--voxel-steps-fine {n} over --model {args.model}: the flag sets the sampling of --model voxel")
+    if getattr(args, "dyn_model", None) is not None or is_dyn:
+        raise ValueError(f"--voxel-steps-fine {n} with --dyn-model {getattr(args, 'dyn_model', None)}: the deformation is evaluated at shared "
+                         "samples (a resampled deformation is a separate design); the flag applies to the static --model voxel")
+    return n
+
+
 def seed(s):
     """runner.py:1214-1218."""
     if s == -1:
@@ -177,6 +198,7 @@ def load_model(args, is_dyn=False, device="cuda"):
     """runner.py:1169-1211 for the supported kinds."""
     if args.model == "sdf":
         raise NotImplementedError("--model sdf (surface rendering) is outside the volume-rendering hot path")
+    voxel_steps_fine = check_voxel_steps_fine(args, is_dyn)
     steps_fine = int(getattr(args, "steps_fine", 0) or 0)
     if steps_fine < 0:
         raise ValueError(f"--steps-fine {steps_fine}: the number of resampled steps per ray cannot be negative")
@@ -199,6 +221,8 @@ def load_model(args, is_dyn=False, device="cuda"):
     model.set_refl(refl.load(args, args.refl_kind, args.space_kind, latent))
     if steps_fine > 0:
         model.steps_fine = steps_fine
+    if voxel_steps_fine > 0:
+        model.steps_fine = voxel_steps_fine
     return model.to(device)
 
 
