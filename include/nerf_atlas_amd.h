@@ -920,6 +920,28 @@ int na_voxel_fine_lanes(int head, int order, int lanes, int shared_row, const fl
                         const float* densities, const float* rgb, int S, double grid_radius, int act_kind, int bg_kind, float* alpha,
                         float* weights, float* out, void* stream);
 
+/* NeRFVoxel.sparsify (`--voxel-sparsify`, this build's flag; csrc/voxel_sparse.hip): a liveness table over the voxels and
+ * a renderer that gathers and walks live steps only.  The grids are not modified.
+ * na_voxel_live_table      one launch: keep[v] = !(densities[v] < d_thresh) (a NaN density is kept; the caller's d_thresh is the fp32
+ *                          density whose softplus(d - 1) is the threshold, -inf keeps everything), live [S,S,S] uint8:
+ *                          live[x,y,z] = any keep[min(x+i,S-1), min(y+j,S-1), min(z+k,S-1)], i, j, k in 0..2.  count: NULL, or one
+ *                          int64 that receives the number of non-zero entries.
+ * na_voxel_live_samples    flags [M,R] uint8 of the samples n = t R + r: explicit pts [M R,3], or o + ts[r stride + t] d of rays [R,6]
+ *                          (stride 0: one shared row ts [M]; else per-ray rows, stride >= M).  A sample is live iff
+ *                          live[ix0, iy0, iz0] != 0 for the LOWER ids of the lookup's cell, or a coordinate is not finite.
+ * na_voxel_mask_rows       out[n,:] = flags[n] ? x[n,:] : (fill0, 0, .., 0) for x, out [N,C]; in place is allowed.
+ * na_voxel_sparse_render   na_voxel_fine_lanes's renderers (head NA_VOX_HEAD_RGB / _PLV / _SH) honouring `live` (required: a table of
+ *                          ones renders everything, bit for bit na_voxel_*_render_rayts): a dead sample has alpha = weight = 0 exactly,
+ *                          its colour is not read, the walk skips it; step lengths come from the ray's original row.
+ * Codes as na_voxel_fine_lanes's; a head outside the three and bad lanes are NA_EINVAL, a NULL table NA_ENULL.                     */
+int na_voxel_live_table(const float* densities, int S, float d_thresh, uint8_t* live, int64_t* count, void* stream);
+int na_voxel_live_samples(const float* pts, const float* rays, const float* ts, int64_t stride, int M, int64_t R, int S, double grid_radius,
+                          const uint8_t* live, uint8_t* flags, void* stream);
+int na_voxel_mask_rows(const float* x, const uint8_t* flags, int64_t N, int C, float fill0, float* out, void* stream);
+int na_voxel_sparse_render(int head, int order, int lanes, int shared_row, const float* rays, int64_t R, const float* ts, int M,
+                           const float* densities, const float* rgb, int S, double grid_radius, const uint8_t* live, int act_kind,
+                           int bg_kind, float* alpha, float* weights, float* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * DynamicNeRFVoxel (src/nerf.py:1526-1586; csrc/dyn_voxel.hip): the deformation of a voxel D-NeRF.  ctrl_pts_grid [S,S,S,3(n-1)] holds
  * control points 1 .. n-1 of a Bezier spline per voxel (control point 0 is zero), rigidity_grid [S,S,S,1] a rigidity logit; both are

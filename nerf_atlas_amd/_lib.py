@@ -270,6 +270,12 @@ SIGNATURES = {
                                            C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "na_voxel_fine_lanes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int, C.c_double,
                                       C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "na_voxel_live_table": (C.c_int, [c_f32p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "na_voxel_live_samples": (C.c_int, [c_f32p, c_f32p, c_f32p, c_i64, C.c_int, c_i64, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "na_voxel_mask_rows": (C.c_int, [c_f32p, C.c_void_p, c_i64, C.c_int, C.c_float, c_f32p, C.c_void_p]),
+    "na_voxel_sparse_render": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, C.c_int,
+                                         C.c_double, C.c_void_p, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "na_dyn_voxel_sh_render": (C.c_int, [c_f32p, c_f32p, c_i64, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_double, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                          C.c_void_p]),

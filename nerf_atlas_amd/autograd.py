@@ -561,6 +561,24 @@ class VoxelSampleFn(Function):
         return g_den, g_rgb, None, g_pts, None, None
 
 
+class VoxelMaskRowsFn(Function):
+    """The training route of a sparsified NeRFVoxel: the lookup's rows [..., C] with the dead samples' rows replaced by
+    (fill0, 0, ..., 0) (ops.voxel_mask_rows; flags uint8 [...], ops.voxel_live_samples).  fill0 is ops.VOXEL_DEAD_DENSITY on the raw rows
+    -- a density whose softplus is exactly 0 -- and 0 on the pos-linear-view head's sh column.  The backward is the same kernel on the
+    gradient with fill0 = 0: the scatter behind it receives exact zeros for dead samples.  With all flags set both directions return
+    their input's bits."""
+
+    @staticmethod
+    def forward(ctx, x, flags, fill0=ops.VOXEL_DEAD_DENSITY):
+        ctx.save_for_backward(flags)
+        return ops.voxel_mask_rows(x, flags, fill0)
+
+    @staticmethod
+    def backward(ctx, g):
+        (flags,) = ctx.saved_tensors
+        return ops.voxel_mask_rows(g.contiguous(), flags, 0.0), None, None
+
+
 class VoxelPlvSampleFn(Function):
     """(raw [..., 4], sh [...]) of NeRFVoxel's lookup with the pos-linear-view head (ops.voxel_plv_sample); backward scatters into the
     two grids (ops.voxel_plv_sample_backward).  Like VoxelSampleFn only the positions are saved -- the rays (their directions are the

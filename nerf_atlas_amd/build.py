@@ -41,6 +41,7 @@ UNITS = [
     ("voxel_plv.hip", [], ""),
     ("voxel_sh.hip", [], ""),
     ("voxel_fine.hip", [], ""),
+    ("voxel_sparse.hip", [], ""),
     ("dyn_voxel.hip", [], ""),
     ("dyn_voxel_render.hip", [], ""),
     ("spline_len.hip", [], ""),

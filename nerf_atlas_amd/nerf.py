@@ -648,6 +648,8 @@ class NeRFVoxel(CommonNeRF):
                           the colour columns (autograd.SigmoidFn), CommonNeRF._composite's nodes
     `steps_fine > 0` (`--voxel-steps-fine`, this build's flag; a plain attribute, not in the state_dict): `forward` renders coarse -> fine
     (`forward_coarse_fine`: a density-only proposal pass, ops.resample_ts, the fine pass over per-ray steps on the same two routes).
+    `live` (a uint8 [S,S,S] buffer, None until `sparsify` has run): the eval routes become ops.voxel_sparse_render, which
+    gathers and walks live samples only, and the operator routes mask the lookup's rows (autograd.VoxelMaskRowsFn).
     There is no density noise (the reference class has no noise_std).  Explicit positions that require a gradient (from_pts under
     DynamicNeRFVoxel) receive one from the lookup's node; the positions o + t d of `forward` are formed in the kernels and have none."""
 
@@ -666,6 +668,7 @@ class NeRFVoxel(CommonNeRF):
         self.brdf = self._bare_brdf
         self._head = None
         self.steps_fine = 0  # > 0: forward renders coarse -> fine over steps + steps_fine samples per ray (forward_coarse_fine)
+        self.register_buffer("live", None)  # uint8 [S,S,S] once `sparsify` has run: absent from a state_dict until then
 
     def _bare_brdf(self, params, view):
         """src/nerf.py:425: before a head is installed the colour is act(parameters)"""
@@ -697,6 +700,29 @@ class NeRFVoxel(CommonNeRF):
                                                for lo, hi in channel_slabs(self.rgb.shape[-1])], dim=-1))
             self.densities = nn.Parameter(ops.grid_upsample(self.densities.data.contiguous(), reso))
         self._set_resolution(reso)
+        if self.live is not None:
+            print("[warn]: NeRFVoxel.upsample clears the liveness table (it is per voxel): call sparsify again")
+            self.clear_live()
+
+    def sparsify(self, thresh: float = 1e-2) -> float:
+        """src/nerf.py:444-452 (a stub there): mark the voxels no sample needs and skip them from now on.  A voxel is kept
+        iff its density's softplus(d - 1) is not below `thresh` (compared as raw densities against one fp32 constant, ops.voxel_d_thresh;
+        a NaN density is kept); the buffer `live` uint8 [S,S,S] marks every cell whose samples can read a kept voxel
+        (ops.voxel_live_table, one launch).  A sample outside it has alpha = weight = 0 exactly and its colour is not read: the eval
+        routes gather and walk live samples only (ops.voxel_sparse_render), the operator routes mask the lookup's rows
+        (autograd.VoxelMaskRowsFn).  The grids are NOT modified: the table goes with the checkpoint, a later sparsify
+        replaces it, `clear_live` removes it.  Returns the live fraction of the table."""
+        ops.voxel_d_thresh(thresh)  # (a bad threshold is refused whatever the device)
+        if not self.densities.is_cuda:
+            raise ValueError("NeRFVoxel.sparsify: the grids must live on the GPU (the liveness table has no CPU implementation)")
+        with torch.no_grad():
+            live, count = ops.voxel_live_table(self.densities.data, thresh)
+        self.live = live
+        return float(count.item()) / live.numel()
+
+    def clear_live(self):
+        """remove the liveness table: every route is the dense one again"""
+        self.live = None
 
     def _set_resolution(self, reso: int):
         self.resolution = reso
@@ -715,6 +741,17 @@ class NeRFVoxel(CommonNeRF):
                 self.densities = nn.Parameter(self.densities.new_empty((S, S, S, self.densities.shape[-1])))
                 self.rgb = nn.Parameter(self.rgb.new_empty((S, S, S, self.rgb.shape[-1])))
             self._set_resolution(S)
+        # the checkpoint decides about the liveness table too: one that has it allocates the buffer, one without clears it
+        live = state_dict.get(prefix + "live")
+        if live is None:
+            self.live = None
+        else:
+            S = self.densities.shape[0]
+            if live.dtype != torch.uint8 or tuple(live.shape) != (S, S, S):
+                raise ValueError(f"NeRFVoxel: a state_dict whose liveness table is {live.dtype} {tuple(live.shape)} over grids of {S}^3: "
+                                 f"`live` must be uint8 [{S},{S},{S}]")
+            if self.live is None or tuple(self.live.shape) != (S, S, S):
+                self.live = torch.empty((S, S, S), dtype=torch.uint8, device=self.densities.device)
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     @property
@@ -766,11 +803,28 @@ class NeRFVoxel(CommonNeRF):
                                                self._act_kind(), self._kernel_bg(), True, pts=pts)
         return self._finish_sky(out)
 
+    def _live_flags(self, rays, ts, pts=None):
+        """uint8 [T, *batch] of the samples the lookups of `_operators` read (explicit pts, else o + t d over the shared row)"""
+        if pts is not None:
+            return ops.voxel_live_samples(self.live, self.grid_radius, pts=pts.detach().contiguous())
+        return ops.voxel_live_samples(self.live, self.grid_radius, rays=rays.contiguous(), ts=ts)
+
+    def _render_sparse(self, rays, ts):
+        """the eval route with a liveness table: ONE launch over the shared row ts [T] or per-ray rows ts [*batch, M]"""
+        kind = self._head_kind()
+        order = self._head.order if kind == "sh" else ops.PLV_CHANNELS[self.rgb.shape[-1]] if kind == "plv" else -1
+        out, self.alpha, self.weights = ops.voxel_sparse_render(kind, rays.contiguous(), ts, self.densities.data, self.rgb.data, self.live,
+                                                                self.grid_radius, order, self._act_kind(), self._kernel_bg(), True)
+        return self._finish_sky(out)
+
     def _operators(self, rays, ts, r_d, pts=None):
         if self._plv():
             # lookup with the coefficients contracted in the kernel -> split -> activation -> linear scale -> compositing
             raw, sh = ag.VoxelPlvSampleFn.apply(self.densities, self.rgb, self.grid_radius, rays.contiguous(),
                                                 None if pts is None else pts.contiguous(), None if pts is not None else ts)
+            if self.live is not None:
+                flags = self._live_flags(rays, ts, pts)
+                raw, sh = ag.VoxelMaskRowsFn.apply(raw, flags), ag.VoxelMaskRowsFn.apply(sh, flags, 0.0)
             if ag.needs_grad(raw):
                 density, params = ag.SplitHeadFn.apply(raw)
             else:
@@ -784,6 +838,9 @@ class NeRFVoxel(CommonNeRF):
             raw = ag.VoxelSampleFn.apply(self.densities, self.rgb, self.grid_radius, None, rays.contiguous(), ts)
         else:
             raw = ag.VoxelSampleFn.apply(self.densities, self.rgb, self.grid_radius, pts.contiguous(), None, None)
+        if self.live is not None:
+            # dead samples: density -> a value whose softplus is exactly 0, colour parameters -> 0; their gradient rows -> 0
+            raw = ag.VoxelMaskRowsFn.apply(raw, self._live_flags(rays, ts, pts))
         if ag.needs_grad(raw):
             density, params = ag.SplitHeadFn.apply(raw)
         else:
@@ -795,7 +852,7 @@ class NeRFVoxel(CommonNeRF):
         r_o, r_d, self.ts, _ = compute_ts(rays, self.t_near, self.t_far, self.steps, perturb=self._perturb())
         self.ts_ray = None
         if self._fusable():
-            return self._render(rays, self.ts)
+            return self._render(rays, self.ts) if self.live is None else self._render_sparse(rays, self.ts)
         return self._operators(rays, self.ts, r_d)  # (positions o + t d are formed inside the lookup kernels, as na_compute_pts forms them)
 
     def _render_rayts(self, rays, ts_ray):
@@ -826,7 +883,7 @@ class NeRFVoxel(CommonNeRF):
             u = utils.rand((steps_fine,) + tuple(rays.shape[:-1]), rays.device)
         ts_ray = ops.resample_ts(ts, w, steps_fine, u)
         if self._fusable():
-            out = self._render_rayts(rays, ts_ray)
+            out = self._render_rayts(rays, ts_ray) if self.live is None else self._render_sparse(rays, ts_ray)
         else:
             pts = ops.compute_pts_rayts(rays, ts_ray)
             out = self._operators(rays, ts_ray, r_d, pts=pts)
@@ -836,7 +893,7 @@ class NeRFVoxel(CommonNeRF):
     def from_pts(self, pts, ts, r_o, r_d, refl_latent=None, rays=None):
         if rays is None: rays = torch.cat([r_o, r_d], dim=-1).contiguous()
         self.ts, self.ts_ray = ts, None  # (positions that need a gradient get one from VoxelSampleFn: ops.voxel_sample_backward_pts)
-        if self._fusable(pts):
+        if self.live is None and self._fusable(pts):  # (the sparse launch forms o + t d itself: explicit points take the operators)
             return self._render(rays, ts, pts=pts.contiguous())
         return self._operators(rays, ts, r_d, pts=pts)
 
@@ -1138,7 +1195,13 @@ class DynamicNeRFVoxel(nn.Module):
     def set_refl(self, r): self.canonical.set_refl(r)
     def set_bg(self, bg): self.canonical.set_bg(bg)
 
+    def _no_live(self, who):
+        if getattr(self.canonical, "live", None) is not None:
+            raise ValueError(f"DynamicNeRFVoxel.{who}: the canonical model holds a liveness table (NeRFVoxel.sparsify), which the "
+                             "deformation's renderers and warp do not know; canonical.clear_live() first")
+
     def forward(self, rays_t):
+        self._no_live("forward")
         rays, t = rays_t
         c = self.canonical
         if c.resolution != self.rigidity_grid.shape[0]:
@@ -1163,6 +1226,7 @@ class DynamicNeRFVoxel(nn.Module):
         rigidity_map / alpha_map gives, without the per-sample tensors.  Eval mode without gradients only.  The attributes of the last
         `forward` (`alpha`, `weights`, `dp`, `rigidity`, `pts` -- here and on the canonical model) are left untouched: nothing per sample
         is kept, and a regulariser or map that reads them still sees the last `forward`."""
+        self._no_live("forward_maps")
         rays, t = rays_t
         c = self.canonical
         if self.training or ag.needs_grad(self.ctrl_pts_grid, self.rigidity_grid, c.densities, c.rgb):
@@ -1206,6 +1270,7 @@ class DynamicNeRFVoxel(nn.Module):
         <e, d(rigid_dp)/d(pts) . e> per sample [T,B,H,W], e [T,B,H,W,3] the caller's randn draw -- DynamicNeRF.ffjord_div's name, shape
         and meaning.  The Jacobian of the grid lookup is formed in closed form by one launch (ops.dyn_voxel_jac_quad, DESIGN.md 3q);
         like the reference's, the estimate has no graph."""
+        self._no_live("ffjord_div")
         pts, tt = self._last_samples("ffjord_div")
         with torch.no_grad():
             return ops.dyn_voxel_jac_quad(pts, tt, self.ctrl_pts_grid.data, self.rigidity_grid.data, self.spline,
@@ -1215,6 +1280,7 @@ class DynamicNeRFVoxel(nn.Module):
         """`utils.divergence(model.pts, model.dp)` of runner.py:694-696 at the samples of the last forward, with its graph: the sum of
         all nine entries of d dp / d pts (DynamicNeRF.sum_jacobian_div's docstring says why it is not the trace), [T,B,H,W,1].  One
         launch, linear in ctrl_pts_grid, which is the only parameter its gradient reaches (autograd.DynVoxelJacQuadFn)."""
+        self._no_live("sum_jacobian_div")
         pts, tt = self._last_samples("sum_jacobian_div")
         c = self.canonical
         if ag.needs_grad(self.ctrl_pts_grid):
@@ -1228,6 +1294,7 @@ class DynamicNeRFVoxel(nn.Module):
         points interpolated at the unwarped `pts` with zero first (they exist only inside the kernels: autograd.DynVoxelSplineLenFn,
         DESIGN.md 3n).  weights [T, ...batch] (the canonical's compositing weights, used detached) or None for 1.  The per-sample mean
         for any batch size; the reference's own expression runs at one view only and equals it there."""
+        self._no_live("spline_len")
         if getattr(self, "pts", None) is None:
             raise RuntimeError("DynamicNeRFVoxel.spline_len reads the sample positions of the last forward: render first")
         if weights is not None:

@@ -5,6 +5,8 @@ contiguous), passes raw device pointers + the current HIP stream to the HIP libr
 output tensor.  There is no eager/CPU fallback.
 """
 import ctypes as C
+import math
+import struct
 from typing import Optional, Sequence
 
 import torch
@@ -2040,6 +2042,130 @@ def voxel_fine_lanes(head: str, lanes: int, rays: torch.Tensor, ts: torch.Tensor
                                   _ptr(None if shared else rgb), S, float(grid_radius), SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha),
                                   _ptr(weights), _ptr(None if shared else out), _stream()))
     return (None if shared else out), alpha, weights
+
+
+# ------------------------------------------------------------------------------------------------- NeRFVoxel.sparsify (csrc/voxel_sparse.hip)
+VOXEL_SPARSE_LANES = 16      # lanes per ray of the shipped sparse renderer
+VOXEL_DEAD_DENSITY = -1e30   # what a dead sample's density column is masked to: finite, and fast_softplus(-1e30 - 1) is 0
+
+
+def voxel_d_thresh(thresh: float) -> float:
+    """The raw density whose softplus(d - 1) equals `thresh`, 1 + log(expm1(thresh)) in Python doubles rounded once to fp32; -inf for
+    thresh == 0 (every voxel is kept).  thresh < 0 or not finite raises ValueError."""
+    thresh = float(thresh)
+    if not math.isfinite(thresh) or thresh < 0:
+        raise ValueError(f"sparsify threshold {thresh!r}: a finite density threshold >= 0")
+    if thresh == 0:
+        return float("-inf")
+    try:
+        d = 1 + math.log(math.expm1(thresh))
+    except OverflowError:  # (expm1 leaves the doubles above 709: log(expm1(x)) is x there to every digit)
+        d = 1 + thresh
+    return struct.unpack("f", struct.pack("f", d))[0]
+
+
+def _voxel_live(live: torch.Tensor, S: int, device) -> torch.Tensor:
+    if (not isinstance(live, torch.Tensor) or live.dtype != torch.uint8 or tuple(live.shape) != (S, S, S) or not live.is_contiguous()
+            or live.device != device):
+        raise ValueError(f"the liveness table must be a contiguous uint8 [{S},{S},{S}] tensor on {device}, got "
+                         f"{getattr(live, 'dtype', type(live).__name__)} {tuple(getattr(live, 'shape', ()))} on {getattr(live, 'device', None)}")
+    return live
+
+
+def voxel_live_table(densities: torch.Tensor, thresh: float, want_count: bool = True):
+    """(live uint8 [S,S,S], count int64 [1] or None) of a density grid [S,S,S,1] (or [S,S,S]): a voxel is kept iff
+    !(d < voxel_d_thresh(thresh)) -- a NaN density is kept -- and live[x,y,z] is the OR of the kept voxels in the window x..x+2, y..y+2,
+    z..z+2 clamped at S-1 (the corners a sample whose lower ids are x, y, z can read).  One launch; count is the number of live entries."""
+    lib = _lib.load()
+    densities = _f32(densities, "densities")
+    S = densities.shape[0]
+    if tuple(densities.shape) not in ((S, S, S, 1), (S, S, S)):
+        raise ValueError(f"the density grid must be [S,S,S,1], got {tuple(densities.shape)}")
+    if S % 2 != 0 or S < 2:
+        raise ValueError(f"voxel resolution {S}: even resolutions only (the reference's ids are floor(.) + S / 2)")
+    d = voxel_d_thresh(thresh)
+    live = torch.empty((S, S, S), device=densities.device, dtype=torch.uint8)
+    count = torch.empty(1, device=densities.device, dtype=torch.int64) if want_count else None
+    check(lib.na_voxel_live_table(_ptr(densities), S, d, _ptr(live), _ptr(count), _stream()))
+    return live, count
+
+
+def voxel_live_samples(live: torch.Tensor, grid_radius: float, pts: Optional[torch.Tensor] = None, rays: Optional[torch.Tensor] = None,
+                       ts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 flags of the samples of a voxel lookup: explicit pts [..., 3] (flags [...]), or o + t d of rays [*batch, 6] over a shared row
+    ts [M] or per-ray rows ts [*batch, M] (flags [M, *batch]).  A sample is live iff the table holds non-zero at the LOWER ids of its
+    cell, or one of its coordinates is not finite."""
+    lib = _lib.load()
+    S = live.shape[0]
+    live = _voxel_live(live, S, live.device)
+    if not live.is_cuda:
+        raise ValueError("live must be a CUDA(HIP) tensor: the hot path has no CPU implementation")
+    if pts is not None:
+        pts = _f32(pts, "pts")
+        if pts.shape[-1] != 3:
+            raise ValueError(f"pts must be [..., 3], got {tuple(pts.shape)}")
+        flags = torch.empty(tuple(pts.shape[:-1]), device=live.device, dtype=torch.uint8)
+        check(lib.na_voxel_live_samples(_ptr(pts), _ptr(None), _ptr(None), 0, 1, pts.numel() // 3, S, float(grid_radius), _ptr(live),
+                                        _ptr(flags), _stream()))
+        return flags
+    if rays is None or ts is None:
+        raise ValueError("voxel_live_samples needs explicit pts, or rays and ts")
+    rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
+    shared = ts.dim() == 1  # (one row for every ray)
+    if rays.shape[-1] != 6 or (not shared and tuple(ts.shape[:-1]) != tuple(rays.shape[:-1])):
+        raise ValueError(f"rays must be [..., 6] and ts [M] or [..., M], got {tuple(rays.shape)} and {tuple(ts.shape)}")
+    M, R = ts.shape[-1], rays.numel() // 6
+    flags = torch.empty((M,) + tuple(rays.shape[:-1]), device=live.device, dtype=torch.uint8)
+    check(lib.na_voxel_live_samples(_ptr(None), _ptr(rays), _ptr(ts), 0 if shared else M, M, R, S, float(grid_radius), _ptr(live),
+                                    _ptr(flags), _stream()))
+    return flags
+
+
+def voxel_mask_rows(x: torch.Tensor, flags: torch.Tensor, fill0: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[n, :] = flags[n] ? x[n, :] : (fill0, 0, ..., 0) over the rows of x [..., C] (flags uint8 [...]); x itself with all flags set,
+    bit for bit.  out: None for a new tensor, or x for in place."""
+    lib = _lib.load()
+    x = _f32(x, "x")
+    Cn = x.shape[-1] if x.dim() > flags.dim() else 1
+    N = x.numel() // Cn
+    if flags.dtype != torch.uint8 or flags.numel() != N or not flags.is_cuda:
+        raise ValueError(f"flags must be uint8 on the GPU, one per row of x ({N}), got {flags.dtype} {tuple(flags.shape)}")
+    flags = flags.contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib.na_voxel_mask_rows(_ptr(x), _ptr(flags), N, Cn, float(fill0), _ptr(out), _stream()))
+    return out
+
+
+def voxel_sparse_render(head: str, rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, live: torch.Tensor,
+                        grid_radius: float, order: int = -1, sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True,
+                        lanes: int = VOXEL_SPARSE_LANES):
+    """The one-launch renderers of a voxel model (head "rgb" | "plv" | "sh") over a shared row ts [M] or per-ray rows ts [..., M],
+    gathering and walking only the samples the table `live` (uint8 [S,S,S], ops.voxel_live_table) marks: a dead sample has alpha =
+    weight = 0 exactly and its colour is not read.  With a table of ones: voxel_*_render_rayts bit for bit.  Outputs of voxel_render_rayts."""
+    lib = _lib.load()
+    if head == "rgb":
+        densities, rgb, S, _ = _voxel_grid(densities, rgb)
+        if rgb.shape[-1] != 3:
+            raise ValueError(f"voxel_sparse_render: the rgb head has 3 colour parameters per voxel, got {rgb.shape[-1]}")
+        order = -1
+    elif head == "plv":
+        densities, rgb, S, order = _voxel_plv_grid(densities, rgb)
+    elif head == "sh":
+        densities, rgb, S, _ = _voxel_sh_grid(densities, rgb, order)
+    else:
+        raise ValueError(f"voxel_sparse_render: head {head!r} (rgb, plv, sh)")
+    live = _voxel_live(live, S, densities.device)
+    rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
+    shared = ts.dim() == 1  # (one row for every ray)
+    if rays.shape[-1] != 6 or (not shared and tuple(ts.shape[:-1]) != tuple(rays.shape[:-1])):
+        raise ValueError(f"rays must be [..., 6] and ts [M] or [..., M], got {tuple(rays.shape)} and {tuple(ts.shape)}")
+    M, R = ts.shape[-1], rays.numel() // 6
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], M, rays.device, bg, want_weights)
+    check(lib.na_voxel_sparse_render(VOX_HEAD[head], int(order), int(lanes), 1 if shared else 0, _ptr(rays), R, _ptr(ts), M, _ptr(densities),
+                                     _ptr(rgb), S, float(grid_radius), _ptr(live), SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights),
+                                     _ptr(out), _stream()))
+    return out, alpha, weights
 
 
 # ------------------------------------------------------------------------------------------------- DynamicNeRFVoxel (csrc/dyn_voxel.hip)

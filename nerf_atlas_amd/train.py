@@ -51,6 +51,7 @@ DEFAULTS = dict(
     voxel_refl_order=None,  # this build's flag: order K (0..4) of the per-voxel pos-linear-view head, the reference's hard-coded 4
     voxel_sh_order=None,  # this build's flag: order K (0..4) of the per-voxel spherical-harmonic colour head
     voxel_steps_fine=0,  # this build's flag: N resampled steps per ray, --model voxel renders coarse -> fine over steps + N
+    voxel_sparsify=[],  # this build's flag: ITER:THRESH pairs, NeRFVoxel.sparsify(THRESH) at the start of iteration ITER
     depth_images=False, flow_map=False, rigidity_map=False, with_alpha=False,  # runner.py:360-392: maps next to the test frames
     render_over_time=-1, render_over_time_steps=100, render_over_time_end_sec=1.0,  # runner.py:252-261: a time sweep of one test camera
     msssim_loss=False,  # runner.py:359, :985-990: report ms-ssim next to the PSNR summary
@@ -86,6 +87,7 @@ def make_args(**overrides) -> SimpleNamespace:
     if a.test_crop_size <= 0:
         a.test_crop_size = a.crop_size
     a.voxel_upsample = parse_voxel_upsample(a.voxel_upsample)
+    a.voxel_sparsify = parse_voxel_sparsify(a.voxel_sparsify)
     return a
 
 
@@ -104,6 +106,43 @@ def parse_voxel_upsample(specs):
         if it < 0 or (plan and it <= plan[-1][0]):
             raise ValueError(f"--voxel-upsample: iterations must be increasing, got {it} after {[p[0] for p in plan]}")
         plan.append((it, reso))
+    return plan
+
+
+def parse_voxel_sparsify(specs):
+    """--voxel-sparsify ITER:THRESH [ITER:THRESH ...] -> [(iteration, threshold)]: iterations strictly increasing, thresholds finite
+    and >= 0 (0 keeps every voxel)."""
+    plan = []
+    for spec in specs:
+        if isinstance(spec, str):
+            m = re.fullmatch(r"(\d+):([^:\s]+)", spec)
+            try:
+                spec = (int(m.group(1)), float(m.group(2)))
+            except (AttributeError, ValueError):
+                raise ValueError(f"--voxel-sparsify {spec!r}: expected ITER:THRESH, a non-negative integer and a float >= 0") from None
+        it, thresh = spec
+        if isinstance(it, bool) or int(it) != it:
+            raise ValueError(f"--voxel-sparsify {it!r}:{thresh!r}: the iteration is a non-negative integer")
+        it, thresh = int(it), float(thresh)
+        if not math.isfinite(thresh) or thresh < 0:
+            raise ValueError(f"--voxel-sparsify {it}:{thresh}: the density threshold is a finite float >= 0")
+        if it < 0 or (plan and it <= plan[-1][0]):
+            raise ValueError(f"--voxel-sparsify: iterations must be increasing, got {it} after {[p[0] for p in plan]}")
+        plan.append((it, thresh))
+    return plan
+
+
+def check_voxel_sparsify(args, is_dyn=False):
+    """--voxel-sparsify ITER:THRESH: NeRFVoxel.sparsify during training of the static --model voxel; anything it cannot
+    apply to raises by name.  Returns the plan."""
+    plan = parse_voxel_sparsify(getattr(args, "voxel_sparsify", []) or [])
+    if not plan:
+        return plan
+    if args.model != "voxel":
+        raise ValueError(f"--voxel-sparsify over --model {args.model}: the flag marks the empty voxels of --model voxel")
+    if getattr(args, "dyn_model", None) is not None or is_dyn:
+        raise ValueError(f"--voxel-sparsify with --dyn-model {getattr(args, 'dyn_model', None)}: the deformation's renderers and warp do not "
+                         "know the liveness table; the flag applies to the static --model voxel")
     return plan
 
 
@@ -199,6 +238,7 @@ def load_model(args, is_dyn=False, device="cuda"):
     if args.model == "sdf":
         raise NotImplementedError("--model sdf (surface rendering) is outside the volume-rendering hot path")
     voxel_steps_fine = check_voxel_steps_fine(args, is_dyn)
+    check_voxel_sparsify(args, is_dyn)
     steps_fine = int(getattr(args, "steps_fine", 0) or 0)
     if steps_fine < 0:
         raise ValueError(f"--steps-fine {steps_fine}: the number of resampled steps per ray cannot be negative")
@@ -541,9 +581,22 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
     world > 1: data-parallel replicas (one process per GPU, identical seeds): every rank draws the same views and
     crop, renders views idxs[rank::world], and the gradients are averaged with one flat RCCL all-reduce before the
     optimiser step (dist.allreduce_gradients); the reference's own --data-parallel is broken (SURVEY header table)."""
-    if args.epochs == 0:
-        return []
     dyn_voxel = isinstance(model, nerf.DynamicNeRFVoxel)
+    sparsify_at = dict(parse_voxel_sparsify(getattr(args, "voxel_sparsify", []) or []))
+    if sparsify_at and dyn_voxel:
+        raise ValueError("--voxel-sparsify with --dyn-model voxel: the deformation's renderers and warp do not know the liveness table")
+    if sparsify_at and not isinstance(model.nerf, nerf.NeRFVoxel):
+        raise ValueError("--voxel-sparsify needs --model voxel (the flag calls NeRFVoxel.sparsify)")
+    # ([iteration, threshold, live fraction of the table] per --voxel-sparsify event)
+    sparsified = train.last_sparsify = []
+
+    def sparsify(i):
+        if i in sparsify_at:
+            sparsified.append([i, sparsify_at[i], model.nerf.sparsify(sparsify_at[i])])
+
+    if args.epochs == 0:
+        sparsify(0)  # (ITER == epochs: before the test render)
+        return []
     if dyn_voxel and not model.ctrl_pts_grid.is_cuda:
         # both terms contract d(rigid_dp)/d(pts) / d(dp)/d(pts) of the grid lookup (runner.py:694-699), which only csrc/dyn_voxel_div.hip
         # forms (NeRFVoxel.upsample's rule: no CPU implementation); raised before cam / labels are touched
@@ -619,6 +672,7 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
     for i in range(args.epochs):
         if i in upsample_at:
             upsample_voxels(model, opt, upsample_at[i])
+        sparsify(i)  # (after an upsampling of the same iteration, which clears the table; the optimiser is left alone)
         idxs = next_idxs(i)
         if world > 1:
             idxs = na_dist.shard_batch(idxs, rank, world)
@@ -735,6 +789,7 @@ def train(model, cam, labels, opt, args, sched=None, on_iter=None, rank: int = 0
             sched.step()
         if on_iter is not None:
             on_iter(i, losses[-1])
+    sparsify(args.epochs)  # (ITER == epochs: after the last step, before the test render)
     return losses
 
 
@@ -830,7 +885,7 @@ def fit(args, device="cuda", replay_reference_rng=False, init=None, on_iter=None
     if getattr(args, "msssim_loss", False):
         with torch.no_grad():
             extra["test_ssim"], extra["test_msssim"] = test_similarity(gots, test_labels)
-    return dict(extra, model=model, losses=losses, reg_terms=list(getattr(train, "last_reg_terms", [])),
+    return dict(extra, model=model, losses=losses, sparsify=[list(e) for e in getattr(train, "last_sparsify", [])], reg_terms=list(getattr(train, "last_reg_terms", [])),
                 tv_terms=[[float(v) for v in row] for row in getattr(train, "last_tv_terms", [])],
                 ffjord_terms=[float(v) for v in getattr(train, "last_ffjord_terms", [])],
                 len_terms=[[float(v) for v in row] for row in getattr(train, "last_len_terms", [])], test_psnr=psnrs, test_psnr_mean=float(np.mean(psnrs)), frames=gots,
