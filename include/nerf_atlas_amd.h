@@ -819,7 +819,7 @@ int na_voxel_sample_backward_pts(const float* pts, int64_t N, const float* densi
                                  double grid_radius, float* g_pts, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * NeRFVoxel with the per-voxel pos-linear-view head (PosLinearView.to_voxel, src/refl.py:265-280; csrc/voxel_plv.hip): rgb is
+ * NeRFVoxel with the per-voxel pos-linear-view head (PosLinearView.to_voxel, src/refl.py:265-280; csrc/voxel.hip): rgb is
  * [S,S,S,C] with C = 3 + (order+1)^2, a row [raw rgb (3) | (order+1)^2 coefficients of one real spherical-harmonic channel], order 0..4
  * (else NA_EINVAL; 4 is the reference's).  Per sample s = sum_k Y_k(d / max(|d|, 1e-12)) c_k with c_k the interpolated coefficient
  * and d = rays[n % R, 3:6] (un-normalised; rays is required in both position forms), and the colour is
@@ -857,7 +857,7 @@ int na_voxel_plv_render(const float* rays, const float* pts, int64_t R, const fl
                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * NeRFVoxel with the per-voxel spherical-harmonic colour head (SphericalHarmonic.to_voxel, src/refl.py:715-722; csrc/voxel_sh.hip): rgb is
+ * NeRFVoxel with the per-voxel spherical-harmonic colour head (SphericalHarmonic.to_voxel, src/refl.py:715-722; csrc/voxel.hip): rgb is
  * [S,S,S,C] with C = 3 (order+1)^2, channel-major -- coefficient k of colour channel c at c (order+1)^2 + k -- order 0..4.  C does not
  * identify the head (3 is the RGB head's count, 12 the pos-linear-view head's at order 2), so every entry point takes both and returns
  * NA_EINVAL unless C == 3 (order+1)^2.  Per sample s_c = sum_u w_u sum_k Y_k(d / max(|d|, 1e-12)) rgb[row_u, c (order+1)^2 + k] with

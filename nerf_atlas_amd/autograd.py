@@ -534,30 +534,48 @@ class GridTVFn(Function):
         return ops.grid_tv_backward(grid, idxs, g.contiguous(), True), None, None  # (the forward checked the indices)
 
 
+def _voxel_lookup_save(ctx, pts_arg, densities, rgb, grid_radius, rays, pts, ts, order=None):
+    """What the lookup node of every voxel head keeps (pts_arg: index of `pts` among forward's arguments): only the positions -- the
+    rays (None where the RGB head reads explicit pts) and explicit pts or ts; the cells are recomputed -- and the grids only when explicit
+    pts require a gradient (DynamicNeRFVoxel's warped points), for the gather that returns it."""
+    ctx.grid_radius, ctx.S, ctx.order = grid_radius, densities.shape[0], order
+    ctx.explicit = pts is not None
+    ctx.pts_grad = ctx.explicit and ctx.needs_input_grad[pts_arg]
+    ctx.save_for_backward(rays, pts if ctx.explicit else ts, *((densities, rgb) if ctx.pts_grad else ()))
+
+
+def _voxel_lookup_backward(ctx, g, scatter, gather, fill=None):
+    """(g_densities, g_rgb, g_pts) of a lookup node.  g: the gradients of its outputs, (g_raw,) or (g_raw, g_sh); fill: per output the
+    trailing shape of the zeros that stand in for a gradient autograd did not materialise (a node that asks for that); scatter(*g, rays=, pts= | ts=) is the head's scatter-add into the two grids, run if either wants a gradient; gather(*g, pts,
+    rays, densities, rgb) is its position gradient, run for explicit pts that require one (the rays x ts form has none)."""
+    rays, pos, *grids = ctx.saved_tensors
+    if fill is not None:
+        batch = tuple(pos.shape[:-1]) if ctx.explicit else (pos.shape[0],) + tuple(rays.shape[:-1])
+        g = [x if x is not None else pos.new_zeros(batch + tail) for x, tail in zip(g, fill)]
+    g = [x.contiguous() for x in g]
+    kw = {"rays": rays, "pts": pos} if ctx.explicit else {"rays": rays, "ts": pos}
+    g_den = g_rgb = g_pts = None
+    if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+        g_den, g_rgb = scatter(*g, **kw)
+    if ctx.pts_grad:
+        g_pts = gather(*g, pos, rays, *grids)
+    return g_den, g_rgb, g_pts
+
+
 class VoxelSampleFn(Function):
-    """raw [..., 1 + C] of NeRFVoxel's grid lookup (ops.voxel_sample); backward scatters into the two grids (ops.voxel_sample_backward).
-    Only the positions are saved -- explicit pts, or rays and ts -- and the cells are recomputed.  Explicit pts that require a gradient
-    (DynamicNeRFVoxel's warped points) get one (ops.voxel_sample_backward_pts: a gather; the grids are saved for it); the
-    rays x ts form has no position gradient."""
+    """raw [..., 1 + C] of NeRFVoxel's grid lookup (ops.voxel_sample); backward scatters into the two grids (ops.voxel_sample_backward)
+    and gives explicit pts their gradient (ops.voxel_sample_backward_pts): `_voxel_lookup_save` / `_voxel_lookup_backward`."""
 
     @staticmethod
     def forward(ctx, densities, rgb, grid_radius, pts, rays, ts):
-        ctx.grid_radius, ctx.S = grid_radius, densities.shape[0]
-        ctx.explicit = pts is not None
-        ctx.pts_grad = ctx.explicit and ctx.needs_input_grad[3]
-        ctx.save_for_backward(*((pts,) if ctx.explicit else (rays, ts)), *((densities, rgb) if ctx.pts_grad else ()))
+        _voxel_lookup_save(ctx, 3, densities, rgb, grid_radius, rays, pts, ts)
         return ops.voxel_sample(densities, rgb, grid_radius, pts=pts, rays=rays, ts=ts)
 
     @staticmethod
     def backward(ctx, g):
-        pos = ctx.saved_tensors
-        kw = {"pts": pos[0]} if ctx.explicit else {"rays": pos[0], "ts": pos[1]}
-        g = g.contiguous()
-        g_den = g_rgb = g_pts = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            g_den, g_rgb = ops.voxel_sample_backward(g, ctx.S, ctx.grid_radius, **kw)
-        if ctx.pts_grad and ctx.needs_input_grad[3]:
-            g_pts = ops.voxel_sample_backward_pts(g, pos[0], pos[1], pos[2], ctx.grid_radius)
+        g_den, g_rgb, g_pts = _voxel_lookup_backward(
+            ctx, (g,), lambda g, **kw: ops.voxel_sample_backward(g, ctx.S, ctx.grid_radius, **kw),
+            lambda g, pts, rays, den, rgb: ops.voxel_sample_backward_pts(g, pts, den, rgb, ctx.grid_radius))
         return g_den, g_rgb, None, g_pts, None, None
 
 
@@ -580,61 +598,37 @@ class VoxelMaskRowsFn(Function):
 
 
 class VoxelPlvSampleFn(Function):
-    """(raw [..., 4], sh [...]) of NeRFVoxel's lookup with the pos-linear-view head (ops.voxel_plv_sample); backward scatters into the
-    two grids (ops.voxel_plv_sample_backward).  Like VoxelSampleFn only the positions are saved -- the rays (their directions are the
-    head's view) and explicit pts or ts -- and the cells are recomputed; explicit pts that require a gradient get one
-    (ops.voxel_plv_sample_backward_pts, the grids are saved for it), the rays x ts form has no position gradient."""
+    """(raw [..., 4], sh [...]) of NeRFVoxel's lookup with the pos-linear-view head (ops.voxel_plv_sample); the rays' directions are the
+    head's view.  Backward: ops.voxel_plv_sample_backward / ops.voxel_plv_sample_backward_pts, as VoxelSampleFn."""
 
     @staticmethod
     def forward(ctx, densities, rgb, grid_radius, rays, pts, ts):
-        ctx.grid_radius, ctx.S, ctx.order = grid_radius, densities.shape[0], ops.PLV_CHANNELS.get(rgb.shape[-1])
-        ctx.explicit = pts is not None
-        ctx.pts_grad = ctx.explicit and ctx.needs_input_grad[4]
-        ctx.save_for_backward(rays, pts if ctx.explicit else ts, *((densities, rgb) if ctx.pts_grad else ()))
+        _voxel_lookup_save(ctx, 4, densities, rgb, grid_radius, rays, pts, ts, ops.PLV_CHANNELS.get(rgb.shape[-1]))
         ctx.set_materialize_grads(False)
         return ops.voxel_plv_sample(densities, rgb, grid_radius, rays, pts=pts, ts=ts)
 
     @staticmethod
     def backward(ctx, g_raw, g_sh):
-        saved = ctx.saved_tensors
-        rays, pos = saved[0], saved[1]
-        kw = {"pts": pos} if ctx.explicit else {"ts": pos}
-        batch = tuple(pos.shape[:-1]) if ctx.explicit else (pos.shape[0],) + tuple(rays.shape[:-1])
-        g_raw = g_raw.contiguous() if g_raw is not None else rays.new_zeros(batch + (4,))
-        g_sh = g_sh.contiguous() if g_sh is not None else rays.new_zeros(batch)
-        g_den = g_rgb = g_pts = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            g_den, g_rgb = ops.voxel_plv_sample_backward(g_raw, g_sh, ctx.S, ctx.order, ctx.grid_radius, rays, **kw)
-        if ctx.pts_grad:
-            g_pts = ops.voxel_plv_sample_backward_pts(g_raw, g_sh, pos, rays, saved[2], saved[3], ctx.grid_radius)
+        g_den, g_rgb, g_pts = _voxel_lookup_backward(
+            ctx, (g_raw, g_sh), lambda g, s, **kw: ops.voxel_plv_sample_backward(g, s, ctx.S, ctx.order, ctx.grid_radius, **kw),
+            lambda g, s, pts, rays, den, rgb: ops.voxel_plv_sample_backward_pts(g, s, pts, rays, den, rgb, ctx.grid_radius), fill=((4,), ()))
         return g_den, g_rgb, None, None, g_pts, None
 
 
 class VoxelShSampleFn(Function):
-    """raw [..., 4] = [density | s_r s_g s_b] of NeRFVoxel's lookup with the spherical-harmonic colour head (ops.voxel_sh_sample);
-    backward scatters into the two grids (ops.voxel_sh_sample_backward).  Like VoxelPlvSampleFn only the positions are saved -- the rays
-    and explicit pts or ts -- and the cells are recomputed; explicit pts that require a gradient get one
-    (ops.voxel_sh_sample_backward_pts, the grids are saved for it), the rays x ts form has no position gradient."""
+    """raw [..., 4] = [density | s_r s_g s_b] of NeRFVoxel's lookup with the spherical-harmonic colour head (ops.voxel_sh_sample).
+    Backward: ops.voxel_sh_sample_backward / ops.voxel_sh_sample_backward_pts, as VoxelSampleFn."""
 
     @staticmethod
     def forward(ctx, densities, rgb, order, grid_radius, rays, pts, ts):
-        ctx.grid_radius, ctx.S, ctx.order = grid_radius, densities.shape[0], order
-        ctx.explicit = pts is not None
-        ctx.pts_grad = ctx.explicit and ctx.needs_input_grad[5]
-        ctx.save_for_backward(rays, pts if ctx.explicit else ts, *((densities, rgb) if ctx.pts_grad else ()))
+        _voxel_lookup_save(ctx, 5, densities, rgb, grid_radius, rays, pts, ts, order)
         return ops.voxel_sh_sample(densities, rgb, order, grid_radius, rays, pts=pts, ts=ts)
 
     @staticmethod
     def backward(ctx, g_raw):
-        saved = ctx.saved_tensors
-        rays, pos = saved[0], saved[1]
-        kw = {"pts": pos} if ctx.explicit else {"ts": pos}
-        g_raw = g_raw.contiguous()
-        g_den = g_rgb = g_pts = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            g_den, g_rgb = ops.voxel_sh_sample_backward(g_raw, ctx.S, ctx.order, ctx.grid_radius, rays, **kw)
-        if ctx.pts_grad:
-            g_pts = ops.voxel_sh_sample_backward_pts(g_raw, pos, rays, saved[2], saved[3], ctx.order, ctx.grid_radius)
+        g_den, g_rgb, g_pts = _voxel_lookup_backward(
+            ctx, (g_raw,), lambda g, **kw: ops.voxel_sh_sample_backward(g, ctx.S, ctx.order, ctx.grid_radius, **kw),
+            lambda g, pts, rays, den, rgb: ops.voxel_sh_sample_backward_pts(g, pts, rays, den, rgb, ctx.order, ctx.grid_radius))
         return g_den, g_rgb, None, None, None, g_pts, None
 
 

@@ -38,8 +38,6 @@ UNITS = [
     ("fourier_grad.hip", [], ""),
     ("composite_rayts.hip", [], ""),
     ("voxel.hip", [], ""),
-    ("voxel_plv.hip", [], ""),
-    ("voxel_sh.hip", [], ""),
     ("voxel_fine.hip", [], ""),
     ("voxel_sparse.hip", [], ""),
     ("dyn_voxel.hip", [], ""),

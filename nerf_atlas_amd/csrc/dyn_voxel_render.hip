@@ -85,12 +85,8 @@ __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const fl
         vox_gather<K, SH>(px + rdp[0], py + rdp[1], pz + rdp[2], g, den, rgb, Y, raw);
         const float a = vox_alpha(raw[0], ts, t, T, nrm);
         if (live && m.alpha != nullptr) m.alpha[(int64_t)t * R + r] = a;
-        float c0 = apply_sigmoid_kind(raw[1], act_kind), c1 = apply_sigmoid_kind(raw[2], act_kind), c2 = apply_sigmoid_kind(raw[3], act_kind);
-        if constexpr (K >= 0 && !SH) {
-          const float lin = plv_scale(raw[4]);
-          c0 = lin * c0; c1 = lin * c1; c2 = lin * c2;
-        }
-        park[slot][j][0] = make_float4(a, c0, c1, c2);
+        const float3 col = vox_colour<K, SH>(raw, act_kind);
+        park[slot][j][0] = make_float4(a, col.x, col.y, col.z);
         park[slot][j][1] = make_float4(rdp[0], rdp[1], rdp[2], rg);
       }
       __syncthreads();
@@ -126,53 +122,31 @@ __global__ __launch_bounds__(NA_DVR_BLOCK) void dyn_voxel_render_kernel(const fl
 
 using namespace na;
 
-// `order` -1: the per-voxel RGB head (C = 3); 0 .. 4: the pos-linear-view head, or with `sh` the spherical-harmonic colour head
-static int dyn_voxel_render_any(const char* who, int order, bool sh, const float* rays, const float* t_ray, int64_t R, const float* ts, int T,
+// every entry point ends here, its shape and n_ctrl checked: the head's grid check (C as VoxHead::check reads it), the checks common to all, the launch
+static int dyn_voxel_render_any(const char* who, VoxHead h, int C, const float* rays, const float* t_ray, int64_t R, const float* ts, int T,
                                 const float* densities, const float* rgb, const float* ctrl_pts_grid, const float* rigidity_grid, int S,
                                 int n_ctrl, double grid_radius, int act_kind, int bg_kind, float* out, float* depth, float* acc,
                                 float* flow, float* rigidity_map, float* alpha, float* weights, void* stream) {
-  NA_REQUIRE(act_kind >= NA_SIG_NORMAL && act_kind <= NA_SIG_IDENTITY, NA_EUNSUPPORTED, "%s: activation kind %d", who, act_kind);
-  NA_REQUIRE(bg_kind == NA_BG_BLACK || bg_kind == NA_BG_WHITE, NA_EUNSUPPORTED, "%s: bg kind %d", who, bg_kind);
+  NA_REQUIRE(T >= 1 && R >= 0, NA_EINVAL, "%s: bad shape T=%d R=%lld", who, T, (long long)R);
+  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED, "%s: n_ctrl %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", who, n_ctrl);
+  if (int rc = h.check(who, S, C, grid_radius)) return rc;
+  if (int rc = vox_check_kinds(who, act_kind, bg_kind)) return rc;
   if (R == 0) return NA_OK;
 #define NA_DVR_PTR(p) NA_REQUIRE(p != nullptr, NA_ENULL, "%s: null pointer " #p, who)
   NA_DVR_PTR(rays); NA_DVR_PTR(t_ray); NA_DVR_PTR(ts); NA_DVR_PTR(densities); NA_DVR_PTR(rgb); NA_DVR_PTR(ctrl_pts_grid);
   NA_DVR_PTR(rigidity_grid); NA_DVR_PTR(out);
 #undef NA_DVR_PTR
-  const int row = order < 0 ? 3 : sh ? 3 * (order + 1) * (order + 1) : 3 + (order + 1) * (order + 1);  // floats of a grid row
-  NA_REQUIRE(order < 0 || row % 4 != 0 || ((uintptr_t)rgb & 15) == 0, NA_EINVAL,
-             "%s: rgb must be 16-byte aligned at order %d", who, order);
+  NA_REQUIRE(h.rgb_aligned(rgb), NA_EINVAL, "%s: rgb must be 16-byte aligned at order %d", who, h.order);
   const VoxGrid g = vox_grid(S, grid_radius);
   const DvrMaps m{depth, acc, flow, rigidity_map, alpha, weights};
-#define NA_DVR_LAUNCH_KS(NC, K, SH)                                                                                                        \
-  hipLaunchKernelGGL((dyn_voxel_render_kernel<NC, K, SH>), dim3(grid_for(R, NA_DVR_BLOCK / NA_DVR_LANES)), dim3(NA_DVR_BLOCK), 0,                  \
-                     (hipStream_t)stream, rays, t_ray, ts, T, R, g, densities, rgb, ctrl_pts_grid, rigidity_grid, act_kind, bg_kind, out, m)
-#define NA_DVR_LAUNCH_K(NC, K) NA_DVR_LAUNCH_KS(NC, K, false)
-#define NA_DVR_LAUNCH_S0(NC) NA_DVR_LAUNCH_KS(NC, 0, true)
-#define NA_DVR_LAUNCH_S1(NC) NA_DVR_LAUNCH_KS(NC, 1, true)
-#define NA_DVR_LAUNCH_S2(NC) NA_DVR_LAUNCH_KS(NC, 2, true)
-#define NA_DVR_LAUNCH_S3(NC) NA_DVR_LAUNCH_KS(NC, 3, true)
-#define NA_DVR_LAUNCH_S4(NC) NA_DVR_LAUNCH_KS(NC, 4, true)
-#define NA_DVR_LAUNCH_M1(NC) NA_DVR_LAUNCH_K(NC, -1)
-#define NA_DVR_LAUNCH_0(NC) NA_DVR_LAUNCH_K(NC, 0)
-#define NA_DVR_LAUNCH_1(NC) NA_DVR_LAUNCH_K(NC, 1)
-#define NA_DVR_LAUNCH_2(NC) NA_DVR_LAUNCH_K(NC, 2)
-#define NA_DVR_LAUNCH_3(NC) NA_DVR_LAUNCH_K(NC, 3)
-#define NA_DVR_LAUNCH_4(NC) NA_DVR_LAUNCH_K(NC, 4)
-  if (sh) switch (order) {
-    case 0: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_S0) break;
-    case 1: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_S1) break;
-    case 2: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_S2) break;
-    case 3: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_S3) break;
-    default: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_S4) break;
-  }
-  else switch (order) {
-    case 0: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_0) break;
-    case 1: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_1) break;
-    case 2: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_2) break;
-    case 3: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_3) break;
-    case 4: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_4) break;
-    default: NA_DV_DISPATCH(n_ctrl, NA_DVR_LAUNCH_M1) break;
-  }
+  vox_for_head(h, [&](auto k, auto tag) {
+#define NA_DVR_NC(NC)                                                                                                                     \
+  hipLaunchKernelGGL((dyn_voxel_render_kernel<NC, decltype(k)::value, decltype(tag)::value>), dim3(grid_for(R, NA_DVR_BLOCK / NA_DVR_LANES)), \
+                     dim3(NA_DVR_BLOCK), 0, (hipStream_t)stream, rays, t_ray, ts, T, R, g, densities, rgb, ctrl_pts_grid, rigidity_grid,  \
+                     act_kind, bg_kind, out, m)
+    NA_DV_DISPATCH(n_ctrl, NA_DVR_NC)
+#undef NA_DVR_NC
+  });
   return check_launch(who);
 }
 
@@ -182,23 +156,16 @@ int na_dyn_voxel_render(const float* rays, const float* t_ray, int64_t R, const 
                         const float* ctrl_pts_grid, const float* rigidity_grid, int S, int C, int n_ctrl, double grid_radius, int act_kind,
                         int bg_kind, float* out, float* depth, float* acc, float* flow, float* rigidity_map, float* alpha, float* weights,
                         void* stream) {
-  NA_REQUIRE(T >= 1 && R >= 0, NA_EINVAL, "na_dyn_voxel_render: bad shape T=%d R=%lld", T, (long long)R);
-  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED,
-             "na_dyn_voxel_render: n_ctrl %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", n_ctrl);
-  if (int rc = vox_check_grid("na_dyn_voxel_render", S, C, grid_radius)) return rc;
-  return dyn_voxel_render_any("na_dyn_voxel_render", -1, false, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid, S, n_ctrl,
-                              grid_radius, act_kind, bg_kind, out, depth, acc, flow, rigidity_map, alpha, weights, stream);
+  return dyn_voxel_render_any("na_dyn_voxel_render", {NA_VOX_HEAD_RGB, -1}, C, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid,
+                              S, n_ctrl, grid_radius, act_kind, bg_kind, out, depth, acc, flow, rigidity_map, alpha, weights, stream);
 }
 
 int na_dyn_voxel_plv_render(const float* rays, const float* t_ray, int64_t R, const float* ts, int T, const float* densities,
                             const float* rgb, const float* ctrl_pts_grid, const float* rigidity_grid, int S, int order, int n_ctrl,
                             double grid_radius, int act_kind, int bg_kind, float* out, float* depth, float* acc, float* flow,
                             float* rigidity_map, float* alpha, float* weights, void* stream) {
-  NA_REQUIRE(T >= 1 && R >= 0, NA_EINVAL, "na_dyn_voxel_plv_render: bad shape T=%d R=%lld", T, (long long)R);
-  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED,
-             "na_dyn_voxel_plv_render: n_ctrl %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", n_ctrl);
-  if (int rc = vox_plv_check_grid("na_dyn_voxel_plv_render", S, order, grid_radius)) return rc;
-  return dyn_voxel_render_any("na_dyn_voxel_plv_render", order, false, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid, S,
+  const VoxHead h{NA_VOX_HEAD_PLV, order};
+  return dyn_voxel_render_any("na_dyn_voxel_plv_render", h, h.row_floats(), rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid, S,
                               n_ctrl, grid_radius, act_kind, bg_kind, out, depth, acc, flow, rigidity_map, alpha, weights, stream);
 }
 
@@ -206,13 +173,8 @@ int na_dyn_voxel_sh_render(const float* rays, const float* t_ray, int64_t R, con
                            const float* rgb, const float* ctrl_pts_grid, const float* rigidity_grid, int S, int C, int order, int n_ctrl,
                            double grid_radius, int act_kind, int bg_kind, float* out, float* depth, float* acc, float* flow,
                            float* rigidity_map, float* alpha, float* weights, void* stream) {
-  NA_REQUIRE(T >= 1 && R >= 0, NA_EINVAL, "na_dyn_voxel_sh_render: bad shape T=%d R=%lld", T, (long long)R);
-  NA_REQUIRE(n_ctrl >= 2 && n_ctrl <= 11, NA_EUNSUPPORTED,
-             "na_dyn_voxel_sh_render: n_ctrl %d (2 .. 11 control points: 3 (n - 1) <= 32 channels per voxel)", n_ctrl);
-  if (int rc = vox_plv_check_grid("na_dyn_voxel_sh_render", S, order, grid_radius)) return rc;
-  NA_REQUIRE(C == 3 * (order + 1) * (order + 1), NA_EINVAL, "na_dyn_voxel_sh_render: C = %d, order %d holds 3 (order + 1)^2", C, order);
-  return dyn_voxel_render_any("na_dyn_voxel_sh_render", order, true, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid, rigidity_grid, S,
-                              n_ctrl, grid_radius, act_kind, bg_kind, out, depth, acc, flow, rigidity_map, alpha, weights, stream);
+  return dyn_voxel_render_any("na_dyn_voxel_sh_render", {NA_VOX_HEAD_SH, order}, C, rays, t_ray, R, ts, T, densities, rgb, ctrl_pts_grid,
+                              rigidity_grid, S, n_ctrl, grid_radius, act_kind, bg_kind, out, depth, acc, flow, rigidity_map, alpha, weights, stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// The real spherical-harmonic basis of degrees 0..4 as device code shared by sh_head.hip (the sph-har head) and voxel_plv.hip /
-// dyn_voxel_render.hip (the per-voxel pos-linear-view head): one definition, so that every user evaluates the same arithmetic.
+// The real spherical-harmonic basis of degrees 0..4 as device code shared by sh_head.hip (the sph-har head) and voxel_plv.h's
+// kernels (the two per-voxel view-dependent heads: voxel.hip, voxel_fine.hip, voxel_sparse.hip, dyn_voxel_render.hip): one definition, so that every user evaluates the same arithmetic.
 #pragma once
 #include "common.h"
 

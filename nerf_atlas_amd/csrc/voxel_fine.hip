@@ -54,24 +54,19 @@ __global__ __launch_bounds__(VFR_BLOCK) void voxel_fine_kernel(const float* __re
     for (int t0 = 0; t0 < M; t0 += L) {
       const int t = t0 + j;
       if (t < M) {
-        // o + t d as vox_position forms it: an fp32 multiply, then an fp32 add
-        const float tt = row[t];
-        const float px = ry[0] + tt * ry[3], py = ry[1] + tt * ry[4], pz = ry[2] + tt * ry[5];
-        float a, c0 = 0.f, c1 = 0.f, c2 = 0.f;
+        const float3 p = vox_ray_point(ry, row[t]);
+        float a;
+        float3 c = make_float3(0.f, 0.f, 0.f);
         if constexpr (PROP) {
-          a = vox_alpha(vox_gather_density(px, py, pz, g, den), row, t, M, nrm);
+          a = vox_alpha(vox_gather_density(p.x, p.y, p.z, g, den), row, t, M, nrm);
         } else {
           float raw[5];
-          vox_gather<K, SH>(px, py, pz, g, den, rgb, Y, raw);
+          vox_gather<K, SH>(p.x, p.y, p.z, g, den, rgb, Y, raw);
           a = vox_alpha(raw[0], row, t, M, nrm);
-          c0 = apply_sigmoid_kind(raw[1], act_kind); c1 = apply_sigmoid_kind(raw[2], act_kind); c2 = apply_sigmoid_kind(raw[3], act_kind);
-          if constexpr (K >= 0 && !SH) {
-            const float lin = plv_scale(raw[4]);
-            c0 = lin * c0; c1 = lin * c1; c2 = lin * c2;
-          }
+          c = vox_colour<K, SH>(raw, act_kind);
         }
         if (live && alpha_out != nullptr) alpha_out[(int64_t)t * R + r] = a;
-        park[slot][j] = make_float4(a, c0, c1, c2);
+        park[slot][j] = make_float4(a, c.x, c.y, c.z);
       }
       __syncthreads();
       if (j == 0 && live) {
@@ -96,68 +91,46 @@ __global__ __launch_bounds__(VFR_BLOCK) void voxel_fine_kernel(const float* __re
 
 using namespace na;
 
-enum { VFR_RGB = 0, VFR_PLV = 1, VFR_SH = 2, VFR_DENSITY = 3 };  // include/nerf_atlas_amd.h NA_VOX_HEAD_*
-
 // lanes per ray of the shipped entry points, every head and the proposal (the other values' times)
 constexpr int VFR_LANES = 16;
 
-template <int K, bool SH, bool PROP>
-static void vfr_launch(int lanes, hipStream_t s, const float* rays, const float* ts_ray, int64_t stride, int M, int64_t R, VoxGrid g,
-                       const float* den, const float* rgb, int act_kind, int bg_kind, float* alpha, float* weights, float* out) {
-#define NA_VFR_L(LN)                                                                                                                   \
-  hipLaunchKernelGGL((voxel_fine_kernel<K, SH, PROP, LN>), dim3(grid_for(R, VFR_BLOCK / LN)), dim3(VFR_BLOCK), 0, s, rays, ts_ray, stride, M, R, \
-                     g, den, rgb, act_kind, bg_kind, alpha, weights, out)
-  switch (lanes) {
-    case 4: NA_VFR_L(4); break;
-    case 8: NA_VFR_L(8); break;
-    case 16: NA_VFR_L(16); break;
-    case 32: NA_VFR_L(32); break;
-    default: NA_VFR_L(64); break;
-  }
-#undef NA_VFR_L
-}
-
-// every entry point ends here, its own checks done: the checks common to all, and the launch
-static int vfr_any(const char* who, int head, int order, int lanes, const float* rays, int64_t R, const float* ts_ray, int64_t stride, int M,
+// every entry point ends here, its shape checked: the checks common to all (C as VoxHead::check reads it), and the launch.
+// NA_VOX_HEAD_DENSITY is the proposal: no colour grid, no activation, no out.
+static int vfr_any(const char* who, VoxHead h, int C, int lanes, const float* rays, int64_t R, const float* ts_ray, int64_t stride, int M,
                    const float* densities, const float* rgb, int S, double grid_radius, int act_kind, int bg_kind, float* alpha,
                    float* weights, float* out, void* stream) {
-  NA_REQUIRE(lanes == 4 || lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64, NA_EINVAL, "%s: %d lanes per ray (4, 8, 16, 32, 64)", who, lanes);
-  if (head != VFR_DENSITY) {
-    NA_REQUIRE(act_kind >= NA_SIG_NORMAL && act_kind <= NA_SIG_IDENTITY, NA_EUNSUPPORTED, "%s: activation kind %d", who, act_kind);
-    NA_REQUIRE(bg_kind == NA_BG_BLACK || bg_kind == NA_BG_WHITE, NA_EUNSUPPORTED, "%s: bg kind %d", who, bg_kind);
+  const bool prop = h.kind == NA_VOX_HEAD_DENSITY;
+  if (int rc = h.check(who, S, C, grid_radius)) return rc;
+  NA_REQUIRE(vox_lanes_ok(lanes), NA_EINVAL, "%s: %d lanes per ray (4, 8, 16, 32, 64)", who, lanes);
+  if (!prop) {
+    if (int rc = vox_check_kinds(who, act_kind, bg_kind)) return rc;
   }
   if (R == 0) return NA_OK;
-  NA_REQUIRE(rays, NA_ENULL, "%s: rays is null", who);
-  NA_REQUIRE(ts_ray, NA_ENULL, "%s: %s is null", who, head == VFR_DENSITY ? "ts" : "ts_ray");
-  NA_REQUIRE(densities, NA_ENULL, "%s: densities is null", who);
-  if (head == VFR_DENSITY) {
+  if (prop) {
+    NA_REQUIRE(rays, NA_ENULL, "%s: rays is null", who);
+    NA_REQUIRE(ts_ray, NA_ENULL, "%s: ts is null", who);
+    NA_REQUIRE(densities, NA_ENULL, "%s: densities is null", who);
     NA_REQUIRE(weights, NA_ENULL, "%s: weights is null", who);
-  } else {
-    NA_REQUIRE(rgb, NA_ENULL, "%s: rgb is null", who);
-    NA_REQUIRE(out, NA_ENULL, "%s: out is null", who);
-    const int row = head == VFR_RGB ? 3 : head == VFR_SH ? 3 * (order + 1) * (order + 1) : 3 + (order + 1) * (order + 1);  // floats of a grid row
-    NA_REQUIRE(row % 4 != 0 || ((uintptr_t)rgb & 15) == 0, NA_EINVAL, "%s: rgb must be 16-byte aligned at order %d", who, order);
+  } else if (int rc = vox_check_render_ptrs(who, h, rays, ts_ray, "ts_ray", densities, rgb, out)) {
+    return rc;
   }
   const VoxGrid g = vox_grid(S, grid_radius);
-  hipStream_t s = (hipStream_t)stream;
-#define NA_VFR_HEAD(K, SH) vfr_launch<K, SH, false>(lanes, s, rays, ts_ray, stride, M, R, g, densities, rgb, act_kind, bg_kind, alpha, weights, out)
-  if (head == VFR_DENSITY) vfr_launch<-1, false, true>(lanes, s, rays, ts_ray, stride, M, R, g, densities, nullptr, 0, 0, alpha, weights, nullptr);
-  else if (head == VFR_RGB) NA_VFR_HEAD(-1, false);
-  else if (head == VFR_PLV) switch (order) {
-    case 0: NA_VFR_HEAD(0, false); break;
-    case 1: NA_VFR_HEAD(1, false); break;
-    case 2: NA_VFR_HEAD(2, false); break;
-    case 3: NA_VFR_HEAD(3, false); break;
-    default: NA_VFR_HEAD(4, false); break;
-  }
-  else switch (order) {
-    case 0: NA_VFR_HEAD(0, true); break;
-    case 1: NA_VFR_HEAD(1, true); break;
-    case 2: NA_VFR_HEAD(2, true); break;
-    case 3: NA_VFR_HEAD(3, true); break;
-    default: NA_VFR_HEAD(4, true); break;
-  }
-#undef NA_VFR_HEAD
+  vox_for_head(h, [&](auto k, auto tag) {
+    vox_for_lanes(lanes, [&](auto l) {
+      constexpr int K = decltype(k)::value, L = decltype(l)::value;
+      constexpr bool SH = decltype(tag)::value;
+      const dim3 grid(grid_for(R, VFR_BLOCK / L)), block(VFR_BLOCK);
+      if constexpr (K < 0) {
+        if (prop) {
+          hipLaunchKernelGGL((voxel_fine_kernel<-1, false, true, L>), grid, block, 0, (hipStream_t)stream, rays, ts_ray, stride, M, R, g, densities,
+                             nullptr, 0, 0, alpha, weights, nullptr);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((voxel_fine_kernel<K, SH, false, L>), grid, block, 0, (hipStream_t)stream, rays, ts_ray, stride, M, R, g, densities, rgb,
+                         act_kind, bg_kind, alpha, weights, out);
+    });
+  });
   return check_launch(who);
 }
 
@@ -167,8 +140,7 @@ int na_voxel_proposal(const float* rays, int64_t R, const float* ts, int T, cons
                       float* weights, void* stream) {
   const char* who = "na_voxel_proposal";
   NA_REQUIRE(T >= 1 && R >= 0, NA_EINVAL, "%s: bad shape T=%d R=%lld", who, T, (long long)R);
-  if (int rc = vox_check_grid(who, S, 3, grid_radius)) return rc;
-  return vfr_any(who, VFR_DENSITY, -1, VFR_LANES, rays, R, ts, 0, T, densities, nullptr, S, grid_radius, 0, 0, alpha, weights,
+  return vfr_any(who, {NA_VOX_HEAD_DENSITY, -1}, 3, VFR_LANES, rays, R, ts, 0, T, densities, nullptr, S, grid_radius, 0, 0, alpha, weights,
                  nullptr, stream);
 }
 
@@ -176,8 +148,7 @@ int na_voxel_render_rayts(const float* rays, int64_t R, const float* ts_ray, int
                           double grid_radius, int act_kind, int bg_kind, float* alpha, float* weights, float* out, void* stream) {
   const char* who = "na_voxel_render_rayts";
   NA_REQUIRE(M >= 1 && R >= 0, NA_EINVAL, "%s: bad shape M=%d R=%lld", who, M, (long long)R);
-  if (int rc = vox_check_grid(who, S, C, grid_radius)) return rc;
-  return vfr_any(who, VFR_RGB, -1, VFR_LANES, rays, R, ts_ray, M, M, densities, rgb, S, grid_radius, act_kind, bg_kind, alpha, weights,
+  return vfr_any(who, {NA_VOX_HEAD_RGB, -1}, C, VFR_LANES, rays, R, ts_ray, M, M, densities, rgb, S, grid_radius, act_kind, bg_kind, alpha, weights,
                  out, stream);
 }
 
@@ -186,9 +157,9 @@ int na_voxel_plv_render_rayts(const float* rays, int64_t R, const float* ts_ray,
                               void* stream) {
   const char* who = "na_voxel_plv_render_rayts";
   NA_REQUIRE(M >= 1 && R >= 0, NA_EINVAL, "%s: bad shape M=%d R=%lld", who, M, (long long)R);
-  if (int rc = vox_plv_check_grid(who, S, order, grid_radius)) return rc;
-  return vfr_any(who, VFR_PLV, order, VFR_LANES, rays, R, ts_ray, M, M, densities, rgb, S, grid_radius, act_kind, bg_kind, alpha,
-                 weights, out, stream);
+  const VoxHead h{NA_VOX_HEAD_PLV, order};
+  return vfr_any(who, h, h.row_floats(), VFR_LANES, rays, R, ts_ray, M, M, densities, rgb, S, grid_radius, act_kind, bg_kind, alpha, weights, out,
+                 stream);
 }
 
 int na_voxel_sh_render_rayts(const float* rays, int64_t R, const float* ts_ray, int M, const float* densities, const float* rgb, int S, int C,
@@ -196,10 +167,7 @@ int na_voxel_sh_render_rayts(const float* rays, int64_t R, const float* ts_ray, 
                              void* stream) {
   const char* who = "na_voxel_sh_render_rayts";
   NA_REQUIRE(M >= 1 && R >= 0, NA_EINVAL, "%s: bad shape M=%d R=%lld", who, M, (long long)R);
-  if (int rc = vox_plv_check_grid(who, S, order, grid_radius)) return rc;
-  NA_REQUIRE(C == 3 * (order + 1) * (order + 1), NA_EINVAL, "%s: C = %d, the spherical-harmonic head of order %d holds 3 (order + 1)^2 = %d", who, C,
-             order, 3 * (order + 1) * (order + 1));
-  return vfr_any(who, VFR_SH, order, VFR_LANES, rays, R, ts_ray, M, M, densities, rgb, S, grid_radius, act_kind, bg_kind, alpha,
+  return vfr_any(who, {NA_VOX_HEAD_SH, order}, C, VFR_LANES, rays, R, ts_ray, M, M, densities, rgb, S, grid_radius, act_kind, bg_kind, alpha,
                  weights, out, stream);
 }
 
@@ -207,15 +175,11 @@ int na_voxel_fine_lanes(int head, int order, int lanes, int shared_row, const fl
                         const float* densities, const float* rgb, int S, double grid_radius, int act_kind, int bg_kind, float* alpha,
                         float* weights, float* out, void* stream) {
   const char* who = "na_voxel_fine_lanes";
-  NA_REQUIRE(head >= VFR_RGB && head <= VFR_DENSITY, NA_EINVAL, "%s: head %d (NA_VOX_HEAD_*)", who, head);
+  NA_REQUIRE(head >= NA_VOX_HEAD_RGB && head <= NA_VOX_HEAD_DENSITY, NA_EINVAL, "%s: head %d (NA_VOX_HEAD_*)", who, head);
   NA_REQUIRE(M >= 1 && R >= 0, NA_EINVAL, "%s: bad shape M=%d R=%lld", who, M, (long long)R);
-  if (head == VFR_PLV || head == VFR_SH) {
-    if (int rc = vox_plv_check_grid(who, S, order, grid_radius)) return rc;
-  } else if (int rc = vox_check_grid(who, S, 3, grid_radius)) {
-    return rc;
-  }
-  return vfr_any(who, head, order, lanes, rays, R, ts_ray, shared_row ? 0 : M, M, densities, rgb, S, grid_radius, act_kind, bg_kind, alpha, weights,
-                 out, stream);
+  const VoxHead h{head, order};
+  return vfr_any(who, h, h.row_floats(), lanes, rays, R, ts_ray, shared_row ? 0 : M, M, densities, rgb, S, grid_radius, act_kind, bg_kind, alpha,
+                 weights, out, stream);
 }
 
 }  // extern "C"

@@ -1,14 +1,15 @@
 // The kernels of a voxel model (NeRFVoxel, src/nerf.py:401-524) for both of its heads, as templates over K:
-//   K = -1      the per-voxel RGB head: grid rows of C = 3 colour parameters (voxel.hip has the entry points)
-//   K = 0 .. 4  the view-dependent head (PosLinearView.to_voxel, src/refl.py:265-280; entry points in voxel_plv.hip): the grid row is
+//   K = -1      the per-voxel RGB head: grid rows of C = 3 colour parameters (voxel.hip has the entry points of all three heads)
+//   K = 0 .. 4  the view-dependent head (PosLinearView.to_voxel, src/refl.py:265-280): the grid row is
 //               [raw rgb (3) | (K+1)^2 coefficients of ONE spherical-harmonic channel], C = 3 + (K+1)^2 floats, and
 //     rgb = act(raw_rgb) * (sigmoid(s) / 2 + 0.5),   s = sum_k Y_k(normalize(view)) c_k,   c_k = the interpolated coefficient k.
 // Interpolation and expansion are both linear in the grid, and Y depends on the ray only, so the lookup contracts every corner's
 // coefficients with the ray's basis as the row arrives: the (K+1)^2 interpolated coefficients never exist.  At K = -1 there is no
 // basis, no sh output and no linear scale: `if constexpr (K >= 0)` leaves the RGB head's own code.  The ray of sample n is n % R.
-// Also here, for dyn_voxel_render.hip as well: the lookup (vox_gather) and one compositing step (vox_alpha, VoxWalk).
+// Also here, for every renderer (this file's, voxel_fine.hip, voxel_sparse.hip, dyn_voxel_render.hip): the lookup (vox_gather), one
+// shading step (vox_colour), the position of a ray's own step (vox_ray_point) and one compositing step (vox_alpha, VoxWalk).  The host side of a head -- VoxHead, vox_for_head -- is voxel_head.h's.
 //
-// A third head rides on the same kernels under the tag SH (entry points in voxel_sh.hip): the per-voxel spherical-harmonic
+// A third head rides on the same kernels under the tag SH: the per-voxel spherical-harmonic
 // colour (SphericalHarmonic.to_voxel, src/refl.py:715-722, the Plenoxels model).  The grid row is 3 channel blocks of NK = (K+1)^2
 // coefficients, C = 3 NK floats, coefficient k of colour channel c at c NK + k, and
 //     rgb_c = act(s_c),   s_c = sum_u w_u sum_k Y_k(normalize(view)) row_u[c NK + k].
@@ -26,8 +27,8 @@
 // sample -- NaN.
 #pragma once
 #include "sh_basis.h"
+#include "voxel_head.h"
 #include "voxel_scatter.h"
-#include <type_traits>
 
 namespace na {
 
@@ -150,11 +151,21 @@ __device__ __forceinline__ void vox_gather(float px, float py, float pz, const V
 // (sigmoid(s) / 2 + 0.5) * act(p): pos_linear_combine_kernel's arithmetic behind apply_sigmoid_kind
 __device__ __forceinline__ float plv_scale(float s) { return sigmoidf_(s) / 2.0f + 0.5f; }
 
-static int vox_plv_check_grid(const char* who, int S, int order, double grid_radius) {
-  NA_REQUIRE(order >= 0 && order <= 4, NA_EINVAL, "%s: order %d outside 0..4", who, order);
-  NA_REQUIRE(S >= 2 && S <= 1024 && S % 2 == 0, NA_EINVAL, "%s: resolution %d (even, 2 .. 1024)", who, S);
-  NA_REQUIRE(grid_radius > 0 && grid_radius < 1e30, NA_EINVAL, "%s: grid_radius %g", who, grid_radius);
-  return NA_OK;
+// the shading step of every renderer: a gathered row's three colour logits through the activation, times the linear scale with the
+// pos-linear-view head (lin * act(p)); SH and the RGB head: the activation alone
+template <int K, bool SH>
+__device__ __forceinline__ float3 vox_colour(const float raw[5], int act_kind) {
+  float c0 = apply_sigmoid_kind(raw[1], act_kind), c1 = apply_sigmoid_kind(raw[2], act_kind), c2 = apply_sigmoid_kind(raw[3], act_kind);
+  if constexpr (K >= 0 && !SH) {
+    const float lin = plv_scale(raw[4]);
+    c0 = lin * c0; c1 = lin * c1; c2 = lin * c2;
+  }
+  return make_float3(c0, c1, c2);
+}
+
+// o + tt d of the ray at ry = rays + r * 6 as vox_position forms it: an fp32 multiply, then an fp32 add
+__device__ __forceinline__ float3 vox_ray_point(const float* ry, float tt) {
+  return make_float3(ry[0] + tt * ry[3], ry[1] + tt * ry[4], ry[2] + tt * ry[5]);
 }
 
 // ------------------------------------------------------------------------------------ one compositing step
@@ -268,7 +279,7 @@ __global__ __launch_bounds__(256) void plv_backward_pts_kernel(const float* __re
 //                     entries (512 rows at K = 4), the deterministic mode 8-byte fixed-point entries (256 rows)
 //   variant 2 (LEAD)  1024 rows x 4 sums x 8 B for [density | rgb]; the SH block goes straight to the global accumulators.  This
 //                     is the RGB head's table (it has no SH block).
-// NA_PLV_SCATTER (voxel_plv.hip) picks the variant na_voxel_plv_sample_backward runs (DESIGN.md 3p has the times of both).
+// NA_PLV_SCATTER (voxel.hip) picks the variant na_voxel_plv_sample_backward runs (DESIGN.md 3p has the times of both).
 constexpr int PLV_LDS_BUDGET = 60 * 1024;  // table bytes of a workgroup: two workgroups share a CU's 160 KiB
 
 // rows of a table of `sums` entries of `entry` bytes (and a 4-byte tag) inside the budget: a power of two, 1024 at most
@@ -361,7 +372,7 @@ static void plv_launch_backward(unsigned wg, hipStream_t s, const float* pts, co
 //                         of the sums per row buys up to four times the rows (512 / 256 at K = 4), for cells, weights and basis
 //                         computed three times; the density sum rides in pass 0
 // Every sum has one home whatever the geometry, and the deterministic mode adds integers only: the variants agree bit for bit there.
-// NA_SH_SCATTER / NA_SH_SCATTER_DET (voxel_sh.hip) pick the variant of each mode (DESIGN.md 3s has the times of both).
+// NA_SH_SCATTER / NA_SH_SCATTER_DET (voxel.hip) pick the variant of each mode (DESIGN.md 3s has the times of both).
 template <int K, int VARIANT, bool DET> struct ShTable {
   static constexpr int NK = Plv<K, true>::NK, CPP = VARIANT == 1 ? 3 : 1, PASSES = 3 / CPP;  // channel blocks per pass
   static constexpr int SUMS = 1 + CPP * NK, ENTRY = DET ? 8 : 4;
@@ -480,10 +491,8 @@ __global__ __launch_bounds__(64) void plv_render_kernel(const float* __restrict_
           const float w = walk.weight(a);
           if (alpha_out != nullptr) alpha_out[(int64_t)t * R + r] = a;
           if (weights_out != nullptr) weights_out[(int64_t)t * R + r] = w;
-          float lin = 1.0f;
-          if constexpr (K >= 0 && !SH) lin = plv_scale(raw[u][4]);
-          const auto colour = [&](float p) { return K >= 0 && !SH ? lin * apply_sigmoid_kind(p, act_kind) : apply_sigmoid_kind(p, act_kind); };
-          walk.add(w, colour(raw[u][1]), colour(raw[u][2]), colour(raw[u][3]), t == T - 1);
+          const float3 c = vox_colour<K, SH>(raw[u], act_kind);
+          walk.add(w, c.x, c.y, c.z, t == T - 1);
         }
       }
     }

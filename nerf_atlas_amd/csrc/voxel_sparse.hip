@@ -14,7 +14,7 @@
 //      stored right there.  One ballot of the (single) wave gives every ray's live bits; the live step indices go, in ascending order,
 //      to the ray's FIFO in LDS (a ring of 2 L entries: at most L - 1 wait from the chunk before, at most L arrive).
 //   B  once L indices wait (at the last chunk: whatever waits, in two rounds), L lanes take them, run the per-step code of the dense
-//      kernel on the ORIGINAL row (vox_gather, vox_alpha, activation, plv_scale) and park [alpha | 3 colours]; then one lane walks them.
+//      kernel on the ORIGINAL row (vox_ray_point, vox_gather, vox_alpha, vox_colour) and park [alpha | 3 colours]; then one lane walks them.
 // The trip counts of both loops depend on M alone, so every thread meets every barrier; LDS does not depend on M.
 #include "voxel_plv.h"
 
@@ -65,9 +65,8 @@ __global__ __launch_bounds__(256) void live_samples_kernel(const float* __restri
     if (pts != nullptr || stride == 0) {
       vox_position(pts, rays, ts, R, n, px, py, pz);
     } else {
-      const float* ry = rays + (n % R) * 6;
-      const float tt = ts[(n % R) * stride + n / R];
-      px = ry[0] + tt * ry[3]; py = ry[1] + tt * ry[4]; pz = ry[2] + tt * ry[5];
+      const float3 p = vox_ray_point(rays + (n % R) * 6, ts[(n % R) * stride + n / R]);
+      px = p.x; py = p.y; pz = p.z;
     }
     flags[n] = vsp_live(px, py, pz, g, live) ? 1 : 0;
   }
@@ -112,8 +111,8 @@ __global__ __launch_bounds__(VSP_BLOCK) void voxel_sparse_kernel(const float* __
       const int t = t0 + j;
       bool on = false;
       if (t < M) {
-        const float tt = row[t];
-        on = vsp_live(ry[0] + tt * ry[3], ry[1] + tt * ry[4], ry[2] + tt * ry[5], g, table);
+        const float3 p = vox_ray_point(ry, row[t]);
+        on = vsp_live(p.x, p.y, p.z, g, table);
         if (!on && ray) {
           if (alpha_out != nullptr) alpha_out[(int64_t)t * R + r] = 0.f;
           if (weights_out != nullptr) weights_out[(int64_t)t * R + r] = 0.f;
@@ -130,19 +129,13 @@ __global__ __launch_bounds__(VSP_BLOCK) void voxel_sparse_kernel(const float* __
         const int n = last ? (waiting < L ? waiting : L) : (waiting >= L ? L : 0);
         if (j < n) {
           const int tq = fifo[slot][(head + j) % Q];
-          // o + t d as vox_position forms it: an fp32 multiply, then an fp32 add
-          const float tt = row[tq];
-          const float px = ry[0] + tt * ry[3], py = ry[1] + tt * ry[4], pz = ry[2] + tt * ry[5];
+          const float3 p = vox_ray_point(ry, row[tq]);
           float raw[5];
-          vox_gather<K, SH>(px, py, pz, g, den, rgb, Y, raw);
+          vox_gather<K, SH>(p.x, p.y, p.z, g, den, rgb, Y, raw);
           const float a = vox_alpha(raw[0], row, tq, M, nrm);
-          float c0 = apply_sigmoid_kind(raw[1], act_kind), c1 = apply_sigmoid_kind(raw[2], act_kind), c2 = apply_sigmoid_kind(raw[3], act_kind);
-          if constexpr (K >= 0 && !SH) {
-            const float lin = plv_scale(raw[4]);
-            c0 = lin * c0; c1 = lin * c1; c2 = lin * c2;
-          }
+          const float3 c = vox_colour<K, SH>(raw, act_kind);
           if (ray && alpha_out != nullptr) alpha_out[(int64_t)tq * R + r] = a;
-          park[slot][j] = make_float4(a, c0, c1, c2);
+          park[slot][j] = make_float4(a, c.x, c.y, c.z);
         }
         __syncthreads();
         if (j == 0 && ray) {
@@ -165,25 +158,6 @@ __global__ __launch_bounds__(VSP_BLOCK) void voxel_sparse_kernel(const float* __
 }  // namespace na
 
 using namespace na;
-
-enum { VSP_RGB = 0, VSP_PLV = 1, VSP_SH = 2 };  // include/nerf_atlas_amd.h NA_VOX_HEAD_*
-
-template <int K, bool SH>
-static void vsp_launch(int lanes, hipStream_t s, const float* rays, const float* ts_ray, int64_t stride, int M, int64_t R, VoxGrid g,
-                       const float* den, const float* rgb, const uint8_t* live, int act_kind, int bg_kind, float* alpha, float* weights,
-                       float* out) {
-#define NA_VSP_L(LN)                                                                                                                    \
-  hipLaunchKernelGGL((voxel_sparse_kernel<K, SH, LN>), dim3(grid_for(R, VSP_BLOCK / LN)), dim3(VSP_BLOCK), 0, s, rays, ts_ray, stride, M, R, \
-                     g, den, rgb, live, act_kind, bg_kind, alpha, weights, out)
-  switch (lanes) {
-    case 4: NA_VSP_L(4); break;
-    case 8: NA_VSP_L(8); break;
-    case 16: NA_VSP_L(16); break;
-    case 32: NA_VSP_L(32); break;
-    default: NA_VSP_L(64); break;
-  }
-#undef NA_VSP_L
-}
 
 extern "C" {
 
@@ -233,45 +207,24 @@ int na_voxel_sparse_render(int head, int order, int lanes, int shared_row, const
                            const float* densities, const float* rgb, int S, double grid_radius, const uint8_t* live, int act_kind,
                            int bg_kind, float* alpha, float* weights, float* out, void* stream) {
   const char* who = "na_voxel_sparse_render";
-  NA_REQUIRE(head >= VSP_RGB && head <= VSP_SH, NA_EINVAL, "%s: head %d (NA_VOX_HEAD_RGB, _PLV, _SH)", who, head);
+  NA_REQUIRE(head >= NA_VOX_HEAD_RGB && head <= NA_VOX_HEAD_SH, NA_EINVAL, "%s: head %d (NA_VOX_HEAD_RGB, _PLV, _SH)", who, head);
   NA_REQUIRE(M >= 1 && R >= 0, NA_EINVAL, "%s: bad shape M=%d R=%lld", who, M, (long long)R);
-  if (head == VSP_RGB) {
-    if (int rc = vox_check_grid(who, S, 3, grid_radius)) return rc;
-  } else if (int rc = vox_plv_check_grid(who, S, order, grid_radius)) {
-    return rc;
-  }
-  NA_REQUIRE(lanes == 4 || lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64, NA_EINVAL, "%s: %d lanes per ray (4, 8, 16, 32, 64)", who, lanes);
-  NA_REQUIRE(act_kind >= NA_SIG_NORMAL && act_kind <= NA_SIG_IDENTITY, NA_EUNSUPPORTED, "%s: activation kind %d", who, act_kind);
-  NA_REQUIRE(bg_kind == NA_BG_BLACK || bg_kind == NA_BG_WHITE, NA_EUNSUPPORTED, "%s: bg kind %d", who, bg_kind);
+  const VoxHead h{head, order};
+  if (int rc = h.check(who, S, h.row_floats(), grid_radius)) return rc;
+  NA_REQUIRE(vox_lanes_ok(lanes), NA_EINVAL, "%s: %d lanes per ray (4, 8, 16, 32, 64)", who, lanes);
+  if (int rc = vox_check_kinds(who, act_kind, bg_kind)) return rc;
   NA_REQUIRE(live, NA_ENULL, "%s: live is null (a table of ones renders everything)", who);
   if (R == 0) return NA_OK;
-  NA_REQUIRE(rays, NA_ENULL, "%s: rays is null", who);
-  NA_REQUIRE(ts, NA_ENULL, "%s: ts is null", who);
-  NA_REQUIRE(densities, NA_ENULL, "%s: densities is null", who);
-  NA_REQUIRE(rgb, NA_ENULL, "%s: rgb is null", who);
-  NA_REQUIRE(out, NA_ENULL, "%s: out is null", who);
-  const int row = head == VSP_RGB ? 3 : head == VSP_SH ? 3 * (order + 1) * (order + 1) : 3 + (order + 1) * (order + 1);  // floats of a grid row
-  NA_REQUIRE(row % 4 != 0 || ((uintptr_t)rgb & 15) == 0, NA_EINVAL, "%s: rgb must be 16-byte aligned at order %d", who, order);
+  if (int rc = vox_check_render_ptrs(who, h, rays, ts, "ts", densities, rgb, out)) return rc;
   const VoxGrid g = vox_grid(S, grid_radius);
-  hipStream_t s = (hipStream_t)stream;
   const int64_t stride = shared_row ? 0 : M;
-#define NA_VSP_HEAD(K, SH) vsp_launch<K, SH>(lanes, s, rays, ts, stride, M, R, g, densities, rgb, live, act_kind, bg_kind, alpha, weights, out)
-  if (head == VSP_RGB) NA_VSP_HEAD(-1, false);
-  else if (head == VSP_PLV) switch (order) {
-    case 0: NA_VSP_HEAD(0, false); break;
-    case 1: NA_VSP_HEAD(1, false); break;
-    case 2: NA_VSP_HEAD(2, false); break;
-    case 3: NA_VSP_HEAD(3, false); break;
-    default: NA_VSP_HEAD(4, false); break;
-  }
-  else switch (order) {
-    case 0: NA_VSP_HEAD(0, true); break;
-    case 1: NA_VSP_HEAD(1, true); break;
-    case 2: NA_VSP_HEAD(2, true); break;
-    case 3: NA_VSP_HEAD(3, true); break;
-    default: NA_VSP_HEAD(4, true); break;
-  }
-#undef NA_VSP_HEAD
+  vox_for_head(h, [&](auto k, auto tag) {
+    vox_for_lanes(lanes, [&](auto l) {
+      constexpr int L = decltype(l)::value;
+      hipLaunchKernelGGL((voxel_sparse_kernel<decltype(k)::value, decltype(tag)::value, L>), dim3(grid_for(R, VSP_BLOCK / L)), dim3(VSP_BLOCK), 0,
+                         (hipStream_t)stream, rays, ts, stride, M, R, g, densities, rgb, live, act_kind, bg_kind, alpha, weights, out);
+    });
+  });
   return check_launch(who);
 }
 

@@ -636,10 +636,10 @@ class NeRFVoxel(CommonNeRF):
     """src/nerf.py:401-524: a dense grid of densities [S,S,S,1] and per-voxel colour parameters rgb [S,S,S,C], read by the reference's
     8-neighbour lookup (csrc/voxel.hip) -- no MLP anywhere.  The static model with the per-voxel RGB head
     (`--refl-kind pos`, refl.Positional.to_voxel) or the view-dependent one (`--refl-kind pos-linear-view --voxel-refl-order K`,
-    refl.PosLinearView.to_voxel: rgb rows [raw rgb | (K+1)^2 spherical-harmonic coefficients], csrc/voxel_plv.hip, DESIGN.md 3p --
-    both routes below then run the ops.voxel_plv_* / autograd.VoxelPlvSampleFn operators), or the spherical-harmonic colour itself
-    (`--refl-kind sph-har --voxel-sh-order K`, refl.SphericalHarmonic.to_voxel: rgb rows of 3 (K+1)^2 coefficients, csrc/voxel_sh.hip,
-    DESIGN.md 3s -- ops.voxel_sh_* / autograd.VoxelShSampleFn, whose raw output is the RGB head's); `_head_kind` selects.  The
+    refl.PosLinearView.to_voxel: rgb rows [raw rgb | (K+1)^2 spherical-harmonic coefficients], DESIGN.md 3p -- both routes below then
+    run the ops.voxel_plv_* / autograd.VoxelPlvSampleFn operators), or the spherical-harmonic colour itself (`--refl-kind sph-har
+    --voxel-sh-order K`, refl.SphericalHarmonic.to_voxel: rgb rows of 3 (K+1)^2 coefficients, DESIGN.md 3s -- ops.voxel_sh_* /
+    autograd.VoxelShSampleFn, whose raw output is the RGB head's); `_head_spec` is the one place the head is read off.  The
     parameters keep the reference's names, so its state_dict loads.
 
     Routes of `forward` / `from_pts`:
@@ -770,37 +770,45 @@ class NeRFVoxel(CommonNeRF):
         kind = self.sigmoid_kind if self._head is None else getattr(self._head, "act_kind", None)
         return kind if kind in ops.SIGMOID else None
 
-    def _head_kind(self):
-        """which kernels read the rgb rows: "plv" [raw rgb | (order + 1)^2 coefficients] (refl.PosLinearView, csrc/voxel_plv.hip),
-        "sh" 3 channel blocks of (order + 1)^2 coefficients (refl.SphericalHarmonic, csrc/voxel_sh.hip), else "rgb" (csrc/voxel.hip)"""
-        return {refl.PosLinearView: "plv", refl.SphericalHarmonic: "sh"}.get(type(self._head), "rgb")
+    def _head_spec(self):
+        """(kind, order) of the installed head, as every ops.voxel_* function and kernel names it: "plv" rgb rows [raw rgb | (order + 1)^2
+        coefficients] (refl.PosLinearView; the order follows from the row's length, None for a row no order gives), "sh" 3 channel blocks
+        of (order + 1)^2 coefficients (refl.SphericalHarmonic; the head's own order), else "rgb" with order -1"""
+        kind = {refl.PosLinearView: "plv", refl.SphericalHarmonic: "sh"}.get(type(self._head), "rgb")
+        return kind, self._head.order if kind == "sh" else ops.PLV_CHANNELS.get(self.rgb.shape[-1]) if kind == "plv" else -1
 
-    def _plv(self):
-        """the pos-linear-view head is installed"""
-        return self._head_kind() == "plv"
+    def _head_kind(self): return self._head_spec()[0]
+
+    def _plv(self): return self._head_kind() == "plv"
 
     def _sh_order(self):
         """the order of the installed spherical-harmonic colour head, or None"""
-        return self._head.order if self._head_kind() == "sh" else None
+        kind, order = self._head_spec()
+        return order if kind == "sh" else None
 
     def _fusable(self, pts=None):
-        if not self.training and not ag.needs_grad(pts, self.densities, self.rgb) and self._act_kind() is not None and self._plv():
-            return self.rgb.shape[-1] == 3 + self._head.num_sh_coeffs
-        if self._head_kind() == "sh":
-            return (not self.training and not ag.needs_grad(pts, self.densities, self.rgb) and self._act_kind() is not None
-                    and self.rgb.shape[-1] == 3 * self._head.num_sh_coeffs)
-        return (not self.training and not ag.needs_grad(pts, self.densities, self.rgb) and self.rgb.shape[-1] == 3
-                and self._act_kind() is not None and (self._head is None or type(self._head) is refl.Positional))
+        if self.training or ag.needs_grad(pts, self.densities, self.rgb) or self._act_kind() is None:
+            return False
+        kind, C = self._head_kind(), self.rgb.shape[-1]
+        if kind == "rgb":
+            return C == 3 and (self._head is None or type(self._head) is refl.Positional)
+        return C == (3 + self._head.num_sh_coeffs if kind == "plv" else 3 * self._head.num_sh_coeffs)
 
-    def _render(self, rays, ts, pts=None):
-        kind = self._head_kind()
-        if kind == "sh":
-            out, self.alpha, self.weights = ops.voxel_sh_render(rays.contiguous(), ts, self.densities.data, self.rgb.data, self._head.order,
-                                                                self.grid_radius, self._act_kind(), self._kernel_bg(), True, pts=pts)
-            return self._finish_sky(out)
-        render = ops.voxel_plv_render if kind == "plv" else ops.voxel_render
-        out, self.alpha, self.weights = render(rays.contiguous(), ts, self.densities.data, self.rgb.data, self.grid_radius,
-                                               self._act_kind(), self._kernel_bg(), True, pts=pts)
+    def _render(self, rays, ts, pts=None, per_ray=False):
+        """the eval route as ONE launch (two with bg "random"): the shared row ts [T], at o + t d or explicit pts, or every ray's own row
+        ts [*batch, M] (per_ray: the fine pass); with a liveness table the sparse renderer takes either kind of row"""
+        kind, order = self._head_spec()
+        grids, head = (self.densities.data, self.rgb.data), ((order,) if kind == "sh" else ())
+        look = (self.grid_radius, self._act_kind(), self._kernel_bg(), True)
+        family = {"rgb": "voxel", "plv": "voxel_plv", "sh": "voxel_sh"}[kind]  # (the public names: what a caller sees and a test counts)
+        if self.live is not None:
+            assert pts is None, "the sparse renderer forms o + t d itself"
+            res = ops.voxel_sparse_render(kind, rays.contiguous(), ts, *grids, self.live, self.grid_radius, order, *look[1:])
+        elif per_ray:
+            res = getattr(ops, family + "_render_rayts")(rays, ts, *grids, *head, *look)
+        else:
+            res = getattr(ops, family + "_render")(rays.contiguous(), ts, *grids, *head, *look, pts=pts)
+        out, self.alpha, self.weights = res
         return self._finish_sky(out)
 
     def _live_flags(self, rays, ts, pts=None):
@@ -809,63 +817,36 @@ class NeRFVoxel(CommonNeRF):
             return ops.voxel_live_samples(self.live, self.grid_radius, pts=pts.detach().contiguous())
         return ops.voxel_live_samples(self.live, self.grid_radius, rays=rays.contiguous(), ts=ts)
 
-    def _render_sparse(self, rays, ts):
-        """the eval route with a liveness table: ONE launch over the shared row ts [T] or per-ray rows ts [*batch, M]"""
-        kind = self._head_kind()
-        order = self._head.order if kind == "sh" else ops.PLV_CHANNELS[self.rgb.shape[-1]] if kind == "plv" else -1
-        out, self.alpha, self.weights = ops.voxel_sparse_render(kind, rays.contiguous(), ts, self.densities.data, self.rgb.data, self.live,
-                                                                self.grid_radius, order, self._act_kind(), self._kernel_bg(), True)
-        return self._finish_sky(out)
-
     def _operators(self, rays, ts, r_d, pts=None):
-        if self._plv():
-            # lookup with the coefficients contracted in the kernel -> split -> activation -> linear scale -> compositing
-            raw, sh = ag.VoxelPlvSampleFn.apply(self.densities, self.rgb, self.grid_radius, rays.contiguous(),
-                                                None if pts is None else pts.contiguous(), None if pts is not None else ts)
-            if self.live is not None:
-                flags = self._live_flags(rays, ts, pts)
-                raw, sh = ag.VoxelMaskRowsFn.apply(raw, flags), ag.VoxelMaskRowsFn.apply(sh, flags, 0.0)
-            if ag.needs_grad(raw):
-                density, params = ag.SplitHeadFn.apply(raw)
-            else:
-                density, params = raw[..., 0].contiguous(), raw[..., 1:]
-            return self._composite(density, self.brdf(params=params.contiguous(), view=r_d, sh=sh), ts, rays)
-        if self._head_kind() == "sh":
-            # lookup with every channel block contracted in the kernel: raw is the RGB head's [density | 3 colour logits]
-            raw = ag.VoxelShSampleFn.apply(self.densities, self.rgb, self._head.order, self.grid_radius, rays.contiguous(),
-                                           None if pts is None else pts.contiguous(), None if pts is not None else ts)
-        elif pts is None:
-            raw = ag.VoxelSampleFn.apply(self.densities, self.rgb, self.grid_radius, None, rays.contiguous(), ts)
+        """the head's lookup node (the coefficients contracted with the ray's basis in the kernel) -> mask of a sparsified model -> split
+        -> the head's activation (and linear scale) -> compositing"""
+        kind, order = self._head_spec()
+        pos = (None, ts) if pts is None else (pts.contiguous(), None)
+        sh = {}
+        if kind == "plv":
+            raw, sh["sh"] = ag.VoxelPlvSampleFn.apply(self.densities, self.rgb, self.grid_radius, rays.contiguous(), *pos)
+        elif kind == "sh":  # raw is the RGB head's [density | 3 colour logits]
+            raw = ag.VoxelShSampleFn.apply(self.densities, self.rgb, order, self.grid_radius, rays.contiguous(), *pos)
         else:
-            raw = ag.VoxelSampleFn.apply(self.densities, self.rgb, self.grid_radius, pts.contiguous(), None, None)
+            raw = ag.VoxelSampleFn.apply(self.densities, self.rgb, self.grid_radius, pos[0], rays.contiguous() if pts is None else None, pos[1])
         if self.live is not None:
-            # dead samples: density -> a value whose softplus is exactly 0, colour parameters -> 0; their gradient rows -> 0
-            raw = ag.VoxelMaskRowsFn.apply(raw, self._live_flags(rays, ts, pts))
+            # dead samples: density -> a value whose softplus is exactly 0, colour parameters and sh -> 0; their gradient rows -> 0
+            flags = self._live_flags(rays, ts, pts)
+            raw = ag.VoxelMaskRowsFn.apply(raw, flags)
+            sh = {k: ag.VoxelMaskRowsFn.apply(v, flags, 0.0) for k, v in sh.items()}
         if ag.needs_grad(raw):
             density, params = ag.SplitHeadFn.apply(raw)
         else:
             density, params = raw[..., 0].contiguous(), raw[..., 1:]
-        return self._composite(density, self.brdf(params=params.contiguous(), view=r_d), ts, rays)
+        return self._composite(density, self.brdf(params=params.contiguous(), view=r_d, **sh), ts, rays)
 
     def forward(self, rays):
         if self.steps_fine > 0: return self.forward_coarse_fine(rays, self.steps_fine)
         r_o, r_d, self.ts, _ = compute_ts(rays, self.t_near, self.t_far, self.steps, perturb=self._perturb())
         self.ts_ray = None
         if self._fusable():
-            return self._render(rays, self.ts) if self.live is None else self._render_sparse(rays, self.ts)
+            return self._render(rays, self.ts)
         return self._operators(rays, self.ts, r_d)  # (positions o + t d are formed inside the lookup kernels, as na_compute_pts forms them)
-
-    def _render_rayts(self, rays, ts_ray):
-        """`_render` over per-ray steps: the fine pass of the eval route as one launch (two with bg "random")"""
-        kind = self._head_kind()
-        if kind == "sh":
-            out, self.alpha, self.weights = ops.voxel_sh_render_rayts(rays, ts_ray, self.densities.data, self.rgb.data, self._head.order,
-                                                                      self.grid_radius, self._act_kind(), self._kernel_bg(), True)
-            return self._finish_sky(out)
-        render = ops.voxel_plv_render_rayts if kind == "plv" else ops.voxel_render_rayts
-        out, self.alpha, self.weights = render(rays, ts_ray, self.densities.data, self.rgb.data, self.grid_radius, self._act_kind(),
-                                               self._kernel_bg(), True)
-        return self._finish_sky(out)
 
     def forward_coarse_fine(self, rays, steps_fine: int, u=None):
         """Coarse -> fine rendering (`--voxel-steps-fine`, this build's flag).  A proposal pass reads the DENSITY grid alone at
@@ -883,7 +864,7 @@ class NeRFVoxel(CommonNeRF):
             u = utils.rand((steps_fine,) + tuple(rays.shape[:-1]), rays.device)
         ts_ray = ops.resample_ts(ts, w, steps_fine, u)
         if self._fusable():
-            out = self._render_rayts(rays, ts_ray) if self.live is None else self._render_sparse(rays, ts_ray)
+            out = self._render(rays, ts_ray, per_ray=True)
         else:
             pts = ops.compute_pts_rayts(rays, ts_ray)
             out = self._operators(rays, ts_ray, r_d, pts=pts)
@@ -1244,8 +1225,10 @@ class DynamicNeRFVoxel(nn.Module):
         if c.bg == "random":
             want.append("weights")  # (the random sky is added behind the launch from the weights)
         tt = t[:, None, None].expand(rays.shape[:-1]).contiguous()
+        kind, order = c._head_spec()
         res = ops.dyn_voxel_render(rays.contiguous(), tt, ts, c.densities.data, c.rgb.data, self.ctrl_pts_grid.data, self.rigidity_grid.data,
-                                   self.spline, c.grid_radius, c._act_kind(), c._kernel_bg(), want=want, plv=c._plv(), sh_order=c._sh_order())
+                                   self.spline, c.grid_radius, c._act_kind(), c._kernel_bg(), want=want, plv=kind == "plv",
+                                   sh_order=order if kind == "sh" else None)
         weights = res.pop("weights", None)
         if weights is not None:
             kept, c.weights = c.weights, weights

@@ -1673,16 +1673,22 @@ def eikonal_loss_backward(normals: torch.Tensor, g: torch.Tensor) -> torch.Tenso
     return out
 
 
-# ------------------------------------------------------------------------------------------------- NeRFVoxel (csrc/voxel.hip)
-def _voxel_grid(densities: torch.Tensor, rgb: torch.Tensor):
-    """(S, C) of densities [S,S,S,1] and rgb [S,S,S,C]; an odd resolution makes the reference's ids `floor + x.5` truncated."""
-    densities, rgb = _f32(densities, "densities"), _f32(rgb, "rgb")
-    S = densities.shape[0]
-    if densities.dim() != 4 or tuple(densities.shape) != (S, S, S, 1) or rgb.dim() != 4 or tuple(rgb.shape[:3]) != (S, S, S):
-        raise ValueError(f"voxel grids must be densities [S,S,S,1] and rgb [S,S,S,C], got {tuple(densities.shape)} and {tuple(rgb.shape)}")
+# ------------------------------------------------------------------------------------------------- NeRFVoxel (csrc/voxel.hip, voxel_fine.hip)
+# One section for the three colour heads of a voxel model: "rgb" (rows of C colour parameters), "plv" (pos-linear-view, rows [raw rgb |
+# (order+1)^2 coefficients]) and "sh" (spherical-harmonic colour, rows of 3 (order+1)^2 coefficients).  `_voxel_head` is the one place a
+# head is recognised; one implementation per operator takes the head's name, and the public voxel_* / voxel_plv_* / voxel_sh_* functions
+# are its three spellings.
+PLV_CHANNELS = {3 + (k + 1) ** 2: k for k in range(5)}   # C = 3 + (order + 1)^2 -> order
+VOX_HEAD = {"rgb": 0, "plv": 1, "sh": 2, "density": 3}   # include/nerf_atlas_amd.h NA_VOX_HEAD_*
+VOXEL_FINE_LANES = (4, 8, 16, 32, 64)                    # lanes per ray na_voxel_fine_lanes is instantiated for
+VOXEL_SPARSE_LANES = 16      # lanes per ray of the shipped sparse renderer (DESIGN.md 3w)
+VOXEL_DEAD_DENSITY = -1e30   # what a dead sample's density column is masked to: finite, and fast_softplus(-1e30 - 1) is 0
+
+
+def _voxel_even(S: int):
+    """an odd resolution makes the reference's ids `floor + x.5` truncated"""
     if S % 2 != 0 or S < 2:
         raise ValueError(f"voxel resolution {S}: even resolutions only (the reference's ids are floor(.) + S / 2)")
-    return densities, rgb, S, rgb.shape[-1]
 
 
 def _aligned16(t: torch.Tensor) -> torch.Tensor:
@@ -1690,99 +1696,64 @@ def _aligned16(t: torch.Tensor) -> torch.Tensor:
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
-def _voxel_positions(pts, rays, ts):
-    """(pts, rays, ts, R, T, batch shape of one row of samples): explicit pts [..., 3] (T = 1), or rays [..., 6] x ts [T]"""
-    if pts is not None:
+def _voxel_head(kind: str, densities: torch.Tensor, rgb: torch.Tensor, order: Optional[int] = None):
+    """(densities, rgb, S, C, order) of densities [S,S,S,1] and rgb [S,S,S,C] under the head `kind`.  "rgb": any C (the library refuses a
+    count without a kernel), order -1.  "plv": C = 3 + (order+1)^2 names the order.  "sh": C does not identify the head (3 is the RGB
+    head's, 12 the pos-linear-view head's at order 2), so the order is explicit and checked against C.  The two view-dependent heads read
+    rows 16 bytes at a time where they are aligned: their grid is returned 16-byte aligned."""
+    if kind not in ("rgb", "plv", "sh"):
+        raise ValueError(f"voxel head {kind!r} (rgb, plv, sh)")
+    if kind == "sh":
+        _voxel_order(order)
+    densities, rgb = _f32(densities, "densities"), _f32(rgb, "rgb")
+    S = densities.shape[0]
+    if densities.dim() != 4 or tuple(densities.shape) != (S, S, S, 1) or rgb.dim() != 4 or tuple(rgb.shape[:3]) != (S, S, S):
+        raise ValueError(f"voxel grids must be densities [S,S,S,1] and rgb [S,S,S,C], got {tuple(densities.shape)} and {tuple(rgb.shape)}")
+    _voxel_even(S)
+    Cn = rgb.shape[-1]
+    if kind == "rgb":
+        return densities, rgb, S, Cn, -1
+    if kind == "plv":
+        if Cn not in PLV_CHANNELS:
+            raise ValueError(f"rgb has {Cn} channels: the pos-linear-view voxel head holds 3 + (order + 1)^2 = {sorted(PLV_CHANNELS)}")
+        order = PLV_CHANNELS[Cn]
+    elif Cn != 3 * (order + 1) ** 2:
+        raise ValueError(f"rgb has {Cn} channels: the spherical-harmonic voxel head of order {order} holds 3 (order + 1)^2 = {3 * (order + 1) ** 2}")
+    return densities, _aligned16(rgb), S, Cn, order
+
+
+def _voxel_abi(kind: str, Cn: int, order: int):
+    """(the head's entry points by operator, the arguments that name the head behind S in their parameter lists)"""
+    lib = _lib.load()
+    if kind == "rgb":
+        return dict(sample=lib.na_voxel_sample, backward=lib.na_voxel_sample_backward, backward_pts=lib.na_voxel_sample_backward_pts,
+                    render=lib.na_voxel_render, render_rayts=lib.na_voxel_render_rayts, dyn_render=lib.na_dyn_voxel_render), (Cn,)
+    if kind == "plv":
+        return dict(sample=lib.na_voxel_plv_sample, backward=lib.na_voxel_plv_sample_backward,
+                    backward_variant=lib.na_voxel_plv_sample_backward_variant, backward_pts=lib.na_voxel_plv_sample_backward_pts,
+                    render=lib.na_voxel_plv_render, render_rayts=lib.na_voxel_plv_render_rayts, dyn_render=lib.na_dyn_voxel_plv_render), (order,)
+    return dict(sample=lib.na_voxel_sh_sample, backward=lib.na_voxel_sh_sample_backward,
+                backward_variant=lib.na_voxel_sh_sample_backward_variant, backward_pts=lib.na_voxel_sh_sample_backward_pts,
+                render=lib.na_voxel_sh_render, render_rayts=lib.na_voxel_sh_render_rayts, dyn_render=lib.na_dyn_voxel_sh_render), (Cn, order)
+
+
+def _voxel_order(order) -> int:
+    if isinstance(order, bool) or not isinstance(order, int) or order not in range(5):
+        raise ValueError(f"order {order!r} outside 0..4")
+    return order
+
+
+def _voxel_positions(kind: str, pts, rays, ts):
+    """(pts or None, rays or None, ts or None, R, T, batch shape of the samples).  The RGB head reads no ray: explicit pts [..., 3] are one
+    row of samples (T = 1), else rays [..., 6] x ts [T].  The view-dependent heads always take rays [..., 6], with explicit pts
+    [T, *rays.shape[:-1], 3] (any T) or ts [T]; the ray of sample n is n % R."""
+    if kind == "rgb" and pts is not None:
         pts = _f32(pts, "pts")
         if pts.shape[-1] != 3:
             raise ValueError(f"pts must be [..., 3], got {tuple(pts.shape)}")
         return pts, None, None, pts.numel() // 3, 1, tuple(pts.shape[:-1])
-    if rays is None or ts is None:
+    if rays is None or (pts is None and ts is None):
         raise ValueError("voxel lookup needs explicit pts, or rays and ts")
-    rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
-    if rays.shape[-1] != 6 or ts.dim() != 1:
-        raise ValueError(f"rays must be [..., 6] and ts [T], got {tuple(rays.shape)} and {tuple(ts.shape)}")
-    return None, rays, ts, rays.numel() // 6, ts.shape[0], (ts.shape[0],) + tuple(rays.shape[:-1])
-
-
-def voxel_sample(densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float, pts: Optional[torch.Tensor] = None,
-                 rays: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """raw [..., 1 + C] = [density | C colour parameters] of the reference's 8-neighbour lookup (src/nerf.py:493-524) at explicit
-    pts [..., 3], or at o + t d of rays [..., 6] x ts [T] formed in the kernel ([T, ..., 1 + C])."""
-    lib = _lib.load()
-    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
-    pts, rays, ts, R, T, batch = _voxel_positions(pts, rays, ts)
-    raw = torch.empty(batch + (1 + Cn,), device=densities.device, dtype=torch.float32)
-    check(lib.na_voxel_sample(_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, Cn, float(grid_radius), _ptr(raw),
-                              _stream()))
-    return raw
-
-
-def voxel_sample_backward(g_raw: torch.Tensor, S: int, grid_radius: float, pts: Optional[torch.Tensor] = None,
-                          rays: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None):
-    """(g_densities [S,S,S,1], g_rgb [S,S,S,C]) of voxel_sample given g_raw [..., 1 + C] and the same positions."""
-    lib = _lib.load()
-    g_raw = _f32(g_raw, "g_raw")
-    if S % 2 != 0 or S < 2:
-        raise ValueError(f"voxel resolution {S}: even resolutions only")
-    pts, rays, ts, R, T, _ = _voxel_positions(pts, rays, ts)
-    Cn = g_raw.shape[-1] - 1
-    if Cn < 1 or g_raw.numel() != T * R * (1 + Cn):
-        raise ValueError(f"g_raw must be [..., 1 + C] with one row per sample ({T * R}), got {tuple(g_raw.shape)}")
-    g_raw = _aligned16(g_raw)
-    g_den = torch.zeros(S, S, S, 1, device=g_raw.device, dtype=torch.float32)
-    g_rgb = torch.zeros(S, S, S, Cn, device=g_raw.device, dtype=torch.float32)
-    check(lib.na_voxel_sample_backward(_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(g_raw), S, Cn, float(grid_radius), _ptr(g_den),
-                                       _ptr(g_rgb), _stream()))
-    return g_den, g_rgb
-
-
-def voxel_render(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float,
-                 sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True, pts: Optional[torch.Tensor] = None):
-    """NeRFVoxel's eval route as ONE launch: positions (o + t d, or explicit pts [T, ..., 3]) -> lookup -> activation -> compositing.
-    (out [..., C], alpha [T, ...], weights [T, ...]); bg black | white (random: composite against black, then sky_random)."""
-    lib = _lib.load()
-    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
-    rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
-    T = ts.shape[0]
-    R, pts = _ls_batch(rays, T, pts)
-    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
-    check(lib.na_voxel_render(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, Cn, float(grid_radius),
-                              SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
-    return out, alpha, weights
-
-
-def voxel_sample_backward_pts(g_raw: torch.Tensor, pts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor,
-                              grid_radius: float) -> torch.Tensor:
-    """g_pts [..., 3]: the gradient of voxel_sample w.r.t. explicit pts [..., 3] given g_raw [..., 1 + C] (a gather: one launch, no atomics)"""
-    lib = _lib.load()
-    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
-    pts, _, _, N, _, _ = _voxel_positions(pts, None, None)
-    g_raw = _f32(g_raw, "g_raw")
-    if g_raw.shape[-1] != 1 + Cn or g_raw.numel() != N * (1 + Cn):
-        raise ValueError(f"g_raw must be [..., {1 + Cn}] with one row per sample ({N}), got {tuple(g_raw.shape)}")
-    g_raw = _aligned16(g_raw)
-    g_pts = torch.empty(pts.shape, device=pts.device, dtype=torch.float32)
-    check(lib.na_voxel_sample_backward_pts(_ptr(pts), N, _ptr(densities), _ptr(rgb), _ptr(g_raw), S, Cn, float(grid_radius), _ptr(g_pts),
-                                           _stream()))
-    return g_pts
-
-
-# ------------------------------------------------------------------------------------------------- NeRFVoxel, pos-linear-view head (csrc/voxel_plv.hip)
-PLV_CHANNELS = {3 + (k + 1) ** 2: k for k in range(5)}  # C = 3 + (order + 1)^2 -> order
-
-
-def _voxel_plv_grid(densities: torch.Tensor, rgb: torch.Tensor):
-    """(densities, rgb, S, order) of the pos-linear-view voxel head: rgb [S,S,S, 3 + (order+1)^2], a 16-byte aligned grid"""
-    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
-    if Cn not in PLV_CHANNELS:
-        raise ValueError(f"rgb has {Cn} channels: the pos-linear-view voxel head holds 3 + (order + 1)^2 = {sorted(PLV_CHANNELS)}")
-    return densities, _aligned16(rgb), S, PLV_CHANNELS[Cn]
-
-
-def _voxel_plv_positions(rays, pts, ts):
-    """(pts or None, rays [R,6], ts or None, R, T, batch of one row of samples): explicit pts [T, *rays.shape[:-1], 3] (any T), or rays x ts;
-    the ray of sample n is n % R either way"""
     rays = _f32(rays, "rays")
     if rays.shape[-1] != 6:
         raise ValueError(f"rays must be [..., 6], got {tuple(rays.shape)}")
@@ -1792,102 +1763,148 @@ def _voxel_plv_positions(rays, pts, ts):
         if pts.shape[-1] != 3 or R == 0 or (pts.numel() // 3) % R != 0:
             raise ValueError(f"pts must be [T, ..., 3] over the {R} rays, got {tuple(pts.shape)}")
         return pts, rays, None, R, pts.numel() // 3 // R, tuple(pts.shape[:-1])
-    if ts is None:
-        raise ValueError("voxel lookup needs explicit pts, or ts")
     ts = _f32(ts, "ts")
     if ts.dim() != 1:
-        raise ValueError(f"ts must be [T], got {tuple(ts.shape)}")
+        raise ValueError(f"rays must be [..., 6] and ts [T], got {tuple(rays.shape)} and {tuple(ts.shape)}")
     return None, rays, ts, R, ts.shape[0], (ts.shape[0],) + tuple(rays.shape[:-1])
+
+
+def _voxel_g_raw(kind: str, g_raw, g_sh, n: int, Cn: int):
+    """the lookup's output gradients, one row per sample: g_raw [..., 1 + C] (RGB head) or [..., 4], 16-byte aligned; g_sh [...] (plv)"""
+    g_raw = _f32(g_raw, "g_raw")
+    if kind == "rgb":
+        if Cn < 1 or g_raw.shape[-1] != 1 + Cn or g_raw.numel() != n * (1 + Cn):
+            raise ValueError(f"g_raw must be [..., {1 + Cn}] with one row per sample ({n}), got {tuple(g_raw.shape)}")
+    elif kind == "sh":
+        if g_raw.numel() != n * 4:
+            raise ValueError(f"g_raw must be [..., 4] with one row per sample ({n}), got {tuple(g_raw.shape)}")
+    else:
+        g_sh = _f32(g_sh, "g_sh")
+        if g_raw.numel() != n * 4 or g_sh.numel() != n:
+            raise ValueError(f"g_raw must be [..., 4] and g_sh [...] with one row per sample ({n}), got {tuple(g_raw.shape)} and {tuple(g_sh.shape)}")
+    return _aligned16(g_raw), g_sh
+
+
+def _voxel_sample(kind, densities, rgb, grid_radius, pts, rays, ts, order=None):
+    densities, rgb, S, Cn, order = _voxel_head(kind, densities, rgb, order)
+    pts, rays, ts, R, T, batch = _voxel_positions(kind, pts, rays, ts)
+    fn, head = _voxel_abi(kind, Cn, order)
+    raw = torch.empty(batch + (1 + Cn if kind == "rgb" else 4,), device=densities.device, dtype=torch.float32)
+    sh = torch.empty(batch, device=densities.device, dtype=torch.float32) if kind == "plv" else None
+    check(fn["sample"](_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, *head, float(grid_radius),
+                                                  _ptr(raw), *((_ptr(sh),) if kind == "plv" else ()), _stream()))
+    return (raw, sh) if kind == "plv" else raw
+
+
+def _voxel_sample_backward(kind, g_raw, g_sh, S, order, grid_radius, pts, rays, ts, variant=None):
+    g_raw = _f32(g_raw, "g_raw")
+    _voxel_even(S)
+    Cn = g_raw.shape[-1] - 1 if kind == "rgb" else 3 + (_voxel_order(order) + 1) ** 2 if kind == "plv" else 3 * (_voxel_order(order) + 1) ** 2
+    pts, rays, ts, R, T, _ = _voxel_positions(kind, pts, rays, ts)
+    g_raw, g_sh = _voxel_g_raw(kind, g_raw, g_sh, T * R, Cn)
+    if kind != "rgb":  # (the RGB head's 4 sums per voxel stay inside the default workspace up to S = 80 and it never asked for more)
+        config.require_deterministic_workspace(8 * S ** 3 * (1 + Cn))  # (a no-op outside config.set_deterministic's mode)
+    g_den = torch.zeros(S, S, S, 1, device=g_raw.device, dtype=torch.float32)
+    g_rgb = torch.zeros(S, S, S, Cn, device=g_raw.device, dtype=torch.float32)
+    fn, head = _voxel_abi(kind, Cn, order)
+    args = (_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(g_raw), *((_ptr(g_sh),) if kind == "plv" else ()), S, *head, float(grid_radius),
+            _ptr(g_den), _ptr(g_rgb))
+    if variant is None:
+        check(fn["backward"](*args, _stream()))
+    else:
+        check(fn["backward_variant"](*args, int(variant), _stream()))
+    return g_den, g_rgb
+
+
+def _voxel_sample_backward_pts(kind, g_raw, g_sh, pts, rays, densities, rgb, grid_radius, order=None):
+    densities, rgb, S, Cn, order = _voxel_head(kind, densities, rgb, order)
+    pts, rays, _, R, T, _ = _voxel_positions(kind, pts, rays, None)
+    g_raw, g_sh = _voxel_g_raw(kind, g_raw, g_sh, T * R, Cn)
+    g_pts = torch.empty(pts.shape, device=pts.device, dtype=torch.float32)
+    fn, head = _voxel_abi(kind, Cn, order)
+    rays_of = () if kind == "rgb" else (_ptr(rays), R)  # (the RGB head's entry point takes no rays)
+    check(fn["backward_pts"](_ptr(pts), *rays_of, T * R, _ptr(densities), _ptr(rgb), _ptr(g_raw), *((_ptr(g_sh),) if kind == "plv" else ()), S,
+                             *head, float(grid_radius), _ptr(g_pts), _stream()))
+    return g_pts
+
+
+def _voxel_render(kind, rays, ts, densities, rgb, grid_radius, order, sigmoid_kind, bg, want_weights, pts=None):
+    """the one-launch renderer over the shared row ts [T], at o + t d or at explicit pts [T, ..., 3]"""
+    densities, rgb, S, Cn, order = _voxel_head(kind, densities, rgb, order)
+    rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
+    T = ts.shape[0]
+    R, pts = _ls_batch(rays, T, pts)
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
+    fn, head = _voxel_abi(kind, Cn, order)
+    check(fn["render"](_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, *head, float(grid_radius), SIGMOID[sigmoid_kind],
+                       BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
+    return out, alpha, weights
+
+
+def _voxel_render_rayts(kind, rays, ts_ray, densities, rgb, grid_radius, order, sigmoid_kind, bg, want_weights):
+    """the one-launch renderer over per-ray rows ts_ray [*batch, M] of rays [*batch, 6]"""
+    densities, rgb, S, Cn, order = _voxel_head(kind, densities, rgb, order)
+    rays, ts_ray = _f32(rays, "rays"), _f32(ts_ray, "ts_ray")
+    assert rays.shape[-1] == 6 and ts_ray.dim() >= 1 and tuple(ts_ray.shape[:-1]) == tuple(rays.shape[:-1]), (ts_ray.shape, rays.shape)
+    R, M = rays.numel() // 6, ts_ray.shape[-1]
+    out, alpha, weights = _ls_outputs(rays.shape[:-1], M, rays.device, bg, want_weights)
+    fn, head = _voxel_abi(kind, Cn, order)
+    check(fn["render_rayts"](_ptr(rays), R, _ptr(ts_ray), M, _ptr(densities), _ptr(rgb), S, *head, float(grid_radius), SIGMOID[sigmoid_kind],
+                             BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
+    return out, alpha, weights
+
+
+def voxel_sample(densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float, pts: Optional[torch.Tensor] = None,
+                 rays: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """raw [..., 1 + C] = [density | C colour parameters] of the reference's 8-neighbour lookup (src/nerf.py:493-524) at explicit
+    pts [..., 3], or at o + t d of rays [..., 6] x ts [T] formed in the kernel ([T, ..., 1 + C])."""
+    return _voxel_sample("rgb", densities, rgb, grid_radius, pts, rays, ts)
+
+
+def voxel_sample_backward(g_raw: torch.Tensor, S: int, grid_radius: float, pts: Optional[torch.Tensor] = None,
+                          rays: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None):
+    """(g_densities [S,S,S,1], g_rgb [S,S,S,C]) of voxel_sample given g_raw [..., 1 + C] and the same positions."""
+    return _voxel_sample_backward("rgb", g_raw, None, S, -1, grid_radius, pts, rays, ts)
+
+
+def voxel_sample_backward_pts(g_raw: torch.Tensor, pts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor,
+                              grid_radius: float) -> torch.Tensor:
+    """g_pts [..., 3]: the gradient of voxel_sample w.r.t. explicit pts [..., 3] given g_raw [..., 1 + C] (a gather: one launch, no atomics)"""
+    return _voxel_sample_backward_pts("rgb", g_raw, None, pts, None, densities, rgb, grid_radius)
+
+
+def voxel_render(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float,
+                 sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True, pts: Optional[torch.Tensor] = None):
+    """NeRFVoxel's eval route as ONE launch: positions (o + t d, or explicit pts [T, ..., 3]) -> lookup -> activation -> compositing.
+    (out [..., C], alpha [T, ...], weights [T, ...]); bg black | white (random: composite against black, then sky_random)."""
+    return _voxel_render("rgb", rays, ts, densities, rgb, grid_radius, None, sigmoid_kind, bg, want_weights, pts=pts)
 
 
 def voxel_plv_sample(densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float, rays: torch.Tensor,
                      pts: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None):
     """(raw [..., 4] = [density | 3 colour parameters], sh [...] = sum_k Y_k(normalize(rays[..., 3:])) c_k) of NeRFVoxel's lookup with
     the pos-linear-view head, at explicit pts [T, *rays.shape[:-1], 3] or at o + t d of rays x ts [T]."""
-    lib = _lib.load()
-    densities, rgb, S, order = _voxel_plv_grid(densities, rgb)
-    pts, rays, ts, R, T, batch = _voxel_plv_positions(rays, pts, ts)
-    raw = torch.empty(batch + (4,), device=densities.device, dtype=torch.float32)
-    sh = torch.empty(batch, device=densities.device, dtype=torch.float32)
-    check(lib.na_voxel_plv_sample(_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, order, float(grid_radius),
-                                  _ptr(raw), _ptr(sh), _stream()))
-    return raw, sh
+    return _voxel_sample("plv", densities, rgb, grid_radius, pts, rays, ts)
 
 
 def voxel_plv_sample_backward(g_raw: torch.Tensor, g_sh: torch.Tensor, S: int, order: int, grid_radius: float, rays: torch.Tensor,
                               pts: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None, variant: Optional[int] = None):
     """(g_densities [S,S,S,1], g_rgb [S,S,S, 3 + (order+1)^2]) of voxel_plv_sample given g_raw [..., 4], g_sh [...] and the same
     positions.  variant: scatter variant 1 or 2 (measurements); None runs the shipped one."""
-    lib = _lib.load()
-    g_raw, g_sh = _f32(g_raw, "g_raw"), _f32(g_sh, "g_sh")
-    if S % 2 != 0 or S < 2:
-        raise ValueError(f"voxel resolution {S}: even resolutions only")
-    if order not in range(5):
-        raise ValueError(f"order {order!r} outside 0..4")
-    pts, rays, ts, R, T, _ = _voxel_plv_positions(rays, pts, ts)
-    if g_raw.numel() != T * R * 4 or g_sh.numel() != T * R:
-        raise ValueError(f"g_raw must be [..., 4] and g_sh [...] with one row per sample ({T * R}), got {tuple(g_raw.shape)} and {tuple(g_sh.shape)}")
-    g_raw = _aligned16(g_raw)
-    Cn = 3 + (order + 1) ** 2
-    config.require_deterministic_workspace(8 * S ** 3 * (1 + Cn))  # (a no-op outside config.set_deterministic's mode)
-    g_den = torch.zeros(S, S, S, 1, device=g_raw.device, dtype=torch.float32)
-    g_rgb = torch.zeros(S, S, S, Cn, device=g_raw.device, dtype=torch.float32)
-    args = (_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(g_raw), _ptr(g_sh), S, order, float(grid_radius), _ptr(g_den), _ptr(g_rgb))
-    if variant is None:
-        check(lib.na_voxel_plv_sample_backward(*args, _stream()))
-    else:
-        check(lib.na_voxel_plv_sample_backward_variant(*args, int(variant), _stream()))
-    return g_den, g_rgb
+    return _voxel_sample_backward("plv", g_raw, g_sh, S, order, grid_radius, pts, rays, ts, variant)
 
 
 def voxel_plv_sample_backward_pts(g_raw: torch.Tensor, g_sh: torch.Tensor, pts: torch.Tensor, rays: torch.Tensor, densities: torch.Tensor,
                                   rgb: torch.Tensor, grid_radius: float) -> torch.Tensor:
     """g_pts [..., 3]: the gradient of voxel_plv_sample w.r.t. explicit pts given g_raw [..., 4] and g_sh [...] (a gather, no atomics)"""
-    lib = _lib.load()
-    densities, rgb, S, order = _voxel_plv_grid(densities, rgb)
-    pts, rays, _, R, T, _ = _voxel_plv_positions(rays, pts, None)
-    g_raw, g_sh = _f32(g_raw, "g_raw"), _f32(g_sh, "g_sh")
-    if g_raw.numel() != T * R * 4 or g_sh.numel() != T * R:
-        raise ValueError(f"g_raw must be [..., 4] and g_sh [...] with one row per sample ({T * R}), got {tuple(g_raw.shape)} and {tuple(g_sh.shape)}")
-    g_raw = _aligned16(g_raw)
-    g_pts = torch.empty(pts.shape, device=pts.device, dtype=torch.float32)
-    check(lib.na_voxel_plv_sample_backward_pts(_ptr(pts), _ptr(rays), R, T * R, _ptr(densities), _ptr(rgb), _ptr(g_raw), _ptr(g_sh), S, order,
-                                               float(grid_radius), _ptr(g_pts), _stream()))
-    return g_pts
+    return _voxel_sample_backward_pts("plv", g_raw, g_sh, pts, rays, densities, rgb, grid_radius)
 
 
 def voxel_plv_render(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float,
                      sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True, pts: Optional[torch.Tensor] = None):
     """NeRFVoxel's eval route with the pos-linear-view head as ONE launch: basis per ray, positions (o + t d, or explicit pts
     [T, ..., 3]) -> lookup -> activation x linear scale -> compositing.  Outputs and backgrounds of voxel_render."""
-    lib = _lib.load()
-    densities, rgb, S, order = _voxel_plv_grid(densities, rgb)
-    rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
-    T = ts.shape[0]
-    R, pts = _ls_batch(rays, T, pts)
-    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
-    check(lib.na_voxel_plv_render(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, order, float(grid_radius),
-                                  SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
-    return out, alpha, weights
-
-
-# ------------------------------------------------------------------------------------------------- NeRFVoxel, spherical-harmonic colour head (csrc/voxel_sh.hip)
-def _voxel_sh_grid(densities: torch.Tensor, rgb: torch.Tensor, order: int):
-    """(densities, rgb, S, C) of the spherical-harmonic voxel head: rgb [S,S,S, 3 (order+1)^2], a 16-byte aligned grid.  The channel count
-    does not identify the head (3 is the RGB head's, 12 the pos-linear-view head's at order 2): the order is explicit and checked."""
-    if isinstance(order, bool) or not isinstance(order, int) or order not in range(5):
-        raise ValueError(f"order {order!r} outside 0..4")
-    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
-    if Cn != 3 * (order + 1) ** 2:
-        raise ValueError(f"rgb has {Cn} channels: the spherical-harmonic voxel head of order {order} holds 3 (order + 1)^2 = {3 * (order + 1) ** 2}")
-    return densities, _aligned16(rgb), S, Cn
-
-
-def _voxel_sh_g_raw(g_raw: torch.Tensor, n: int) -> torch.Tensor:
-    g_raw = _f32(g_raw, "g_raw")
-    if g_raw.numel() != n * 4:
-        raise ValueError(f"g_raw must be [..., 4] with one row per sample ({n}), got {tuple(g_raw.shape)}")
-    return _aligned16(g_raw)
+    return _voxel_render("plv", rays, ts, densities, rgb, grid_radius, None, sigmoid_kind, bg, want_weights, pts=pts)
 
 
 def voxel_sh_sample(densities: torch.Tensor, rgb: torch.Tensor, order: int, grid_radius: float, rays: torch.Tensor,
@@ -1895,71 +1912,30 @@ def voxel_sh_sample(densities: torch.Tensor, rgb: torch.Tensor, order: int, grid
     """raw [..., 4] = [density | s_r s_g s_b], s_c = sum_k Y_k(normalize(rays[..., 3:])) c_ck with c_ck the interpolated coefficient k of
     colour channel c (rgb[..., c (order+1)^2 + k]), of NeRFVoxel's lookup with the spherical-harmonic head, at explicit pts
     [T, *rays.shape[:-1], 3] or at o + t d of rays x ts [T].  The RGB head's layout: no coefficient array exists."""
-    lib = _lib.load()
-    densities, rgb, S, Cn = _voxel_sh_grid(densities, rgb, order)
-    pts, rays, ts, R, T, batch = _voxel_plv_positions(rays, pts, ts)
-    raw = torch.empty(batch + (4,), device=densities.device, dtype=torch.float32)
-    check(lib.na_voxel_sh_sample(_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, Cn, order, float(grid_radius),
-                                 _ptr(raw), _stream()))
-    return raw
+    return _voxel_sample("sh", densities, rgb, grid_radius, pts, rays, ts, order)
 
 
 def voxel_sh_sample_backward(g_raw: torch.Tensor, S: int, order: int, grid_radius: float, rays: torch.Tensor,
                              pts: Optional[torch.Tensor] = None, ts: Optional[torch.Tensor] = None, variant: Optional[int] = None):
     """(g_densities [S,S,S,1], g_rgb [S,S,S, 3 (order+1)^2]) of voxel_sh_sample given g_raw [..., 4] and the same positions.
     variant: scatter variant 1 or 2 (measurements); None runs the shipped one of the mode."""
-    lib = _lib.load()
-    if S % 2 != 0 or S < 2:
-        raise ValueError(f"voxel resolution {S}: even resolutions only")
-    if isinstance(order, bool) or not isinstance(order, int) or order not in range(5):
-        raise ValueError(f"order {order!r} outside 0..4")
-    pts, rays, ts, R, T, _ = _voxel_plv_positions(rays, pts, ts)
-    g_raw = _voxel_sh_g_raw(g_raw, T * R)
-    Cn = 3 * (order + 1) ** 2
-    config.require_deterministic_workspace(8 * S ** 3 * (1 + Cn))  # (a no-op outside config.set_deterministic's mode)
-    g_den = torch.zeros(S, S, S, 1, device=g_raw.device, dtype=torch.float32)
-    g_rgb = torch.zeros(S, S, S, Cn, device=g_raw.device, dtype=torch.float32)
-    args = (_ptr(pts), _ptr(rays), R, _ptr(ts), T, _ptr(g_raw), S, Cn, order, float(grid_radius), _ptr(g_den), _ptr(g_rgb))
-    if variant is None:
-        check(lib.na_voxel_sh_sample_backward(*args, _stream()))
-    else:
-        check(lib.na_voxel_sh_sample_backward_variant(*args, int(variant), _stream()))
-    return g_den, g_rgb
+    return _voxel_sample_backward("sh", g_raw, None, S, order, grid_radius, pts, rays, ts, variant)
 
 
 def voxel_sh_sample_backward_pts(g_raw: torch.Tensor, pts: torch.Tensor, rays: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor,
                                  order: int, grid_radius: float) -> torch.Tensor:
     """g_pts [..., 3]: the gradient of voxel_sh_sample w.r.t. explicit pts given g_raw [..., 4] (a gather, no atomics)"""
-    lib = _lib.load()
-    densities, rgb, S, Cn = _voxel_sh_grid(densities, rgb, order)
-    pts, rays, _, R, T, _ = _voxel_plv_positions(rays, pts, None)
-    g_raw = _voxel_sh_g_raw(g_raw, T * R)
-    g_pts = torch.empty(pts.shape, device=pts.device, dtype=torch.float32)
-    check(lib.na_voxel_sh_sample_backward_pts(_ptr(pts), _ptr(rays), R, T * R, _ptr(densities), _ptr(rgb), _ptr(g_raw), S, Cn, order,
-                                              float(grid_radius), _ptr(g_pts), _stream()))
-    return g_pts
+    return _voxel_sample_backward_pts("sh", g_raw, None, pts, rays, densities, rgb, grid_radius, order)
 
 
 def voxel_sh_render(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, order: int, grid_radius: float,
                     sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True, pts: Optional[torch.Tensor] = None):
     """NeRFVoxel's eval route with the spherical-harmonic head as ONE launch: basis per ray, positions (o + t d, or explicit pts
     [T, ..., 3]) -> lookup -> activation -> compositing.  Outputs and backgrounds of voxel_render."""
-    lib = _lib.load()
-    densities, rgb, S, Cn = _voxel_sh_grid(densities, rgb, order)
-    rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
-    T = ts.shape[0]
-    R, pts = _ls_batch(rays, T, pts)
-    out, alpha, weights = _ls_outputs(rays.shape[:-1], T, rays.device, bg, want_weights)
-    check(lib.na_voxel_sh_render(_ptr(rays), _ptr(pts), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), S, Cn, order, float(grid_radius),
-                                 SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
-    return out, alpha, weights
+    return _voxel_render("sh", rays, ts, densities, rgb, grid_radius, order, sigmoid_kind, bg, want_weights, pts=pts)
 
 
 # ------------------------------------------------------------------------------------------------- NeRFVoxel coarse -> fine (csrc/voxel_fine.hip)
-VOX_HEAD = {"rgb": 0, "plv": 1, "sh": 2, "density": 3}   # include/nerf_atlas_amd.h NA_VOX_HEAD_*
-VOXEL_FINE_LANES = (4, 8, 16, 32, 64)                    # lanes per ray na_voxel_fine_lanes is instantiated for
-
-
 def voxel_proposal(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, grid_radius: float):
     """The proposal pass of NeRFVoxel's coarse -> fine route as ONE launch: (alpha [T, ...], weights [T, ...]) of rays [..., 6] over the
     shared steps ts [T] from the density grid [S,S,S,1] alone -- bit for bit what voxel_render / voxel_plv_render / voxel_sh_render return
@@ -1969,8 +1945,7 @@ def voxel_proposal(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor
     S = densities.shape[0]
     if densities.dim() != 4 or tuple(densities.shape) != (S, S, S, 1):
         raise ValueError(f"the density grid must be [S,S,S,1], got {tuple(densities.shape)}")
-    if S % 2 != 0 or S < 2:
-        raise ValueError(f"voxel resolution {S}: even resolutions only (the reference's ids are floor(.) + S / 2)")
+    _voxel_even(S)
     if rays.shape[-1] != 6 or ts.dim() != 1:
         raise ValueError(f"rays must be [..., 6] and ts [T], got {tuple(rays.shape)} and {tuple(ts.shape)}")
     T, R = ts.shape[0], rays.numel() // 6
@@ -1980,48 +1955,23 @@ def voxel_proposal(rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor
     return alpha, weights
 
 
-def _voxel_rayts(rays: torch.Tensor, ts_ray: torch.Tensor):
-    """(rays, ts_ray, R, M) of per-ray steps ts_ray [*batch, M] over rays [*batch, 6]"""
-    rays, ts_ray = _f32(rays, "rays"), _f32(ts_ray, "ts_ray")
-    assert rays.shape[-1] == 6 and ts_ray.dim() >= 1 and tuple(ts_ray.shape[:-1]) == tuple(rays.shape[:-1]), (ts_ray.shape, rays.shape)
-    return rays, ts_ray, rays.numel() // 6, ts_ray.shape[-1]
-
-
 def voxel_render_rayts(rays: torch.Tensor, ts_ray: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float,
                        sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True):
     """`voxel_render` over per-ray steps ts_ray [..., M] (one increasing row per ray, e.g. `resample_ts`'s): positions o + t d -> lookup ->
     activation -> compositing as ONE launch.  (out [..., 3], alpha [M, ...], weights [M, ...]); bg black | white."""
-    lib = _lib.load()
-    densities, rgb, S, Cn = _voxel_grid(densities, rgb)
-    rays, ts_ray, R, M = _voxel_rayts(rays, ts_ray)
-    out, alpha, weights = _ls_outputs(rays.shape[:-1], M, rays.device, bg, want_weights)
-    check(lib.na_voxel_render_rayts(_ptr(rays), R, _ptr(ts_ray), M, _ptr(densities), _ptr(rgb), S, Cn, float(grid_radius),
-                                    SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
-    return out, alpha, weights
+    return _voxel_render_rayts("rgb", rays, ts_ray, densities, rgb, grid_radius, None, sigmoid_kind, bg, want_weights)
 
 
 def voxel_plv_render_rayts(rays: torch.Tensor, ts_ray: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, grid_radius: float,
                            sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True):
     """`voxel_plv_render` over per-ray steps ts_ray [..., M]; outputs and backgrounds of voxel_render_rayts."""
-    lib = _lib.load()
-    densities, rgb, S, order = _voxel_plv_grid(densities, rgb)
-    rays, ts_ray, R, M = _voxel_rayts(rays, ts_ray)
-    out, alpha, weights = _ls_outputs(rays.shape[:-1], M, rays.device, bg, want_weights)
-    check(lib.na_voxel_plv_render_rayts(_ptr(rays), R, _ptr(ts_ray), M, _ptr(densities), _ptr(rgb), S, order, float(grid_radius),
-                                        SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
-    return out, alpha, weights
+    return _voxel_render_rayts("plv", rays, ts_ray, densities, rgb, grid_radius, None, sigmoid_kind, bg, want_weights)
 
 
 def voxel_sh_render_rayts(rays: torch.Tensor, ts_ray: torch.Tensor, densities: torch.Tensor, rgb: torch.Tensor, order: int, grid_radius: float,
                           sigmoid_kind: str = "upshifted", bg: str = "black", want_weights: bool = True):
     """`voxel_sh_render` over per-ray steps ts_ray [..., M]; outputs and backgrounds of voxel_render_rayts."""
-    lib = _lib.load()
-    densities, rgb, S, Cn = _voxel_sh_grid(densities, rgb, order)
-    rays, ts_ray, R, M = _voxel_rayts(rays, ts_ray)
-    out, alpha, weights = _ls_outputs(rays.shape[:-1], M, rays.device, bg, want_weights)
-    check(lib.na_voxel_sh_render_rayts(_ptr(rays), R, _ptr(ts_ray), M, _ptr(densities), _ptr(rgb), S, Cn, order, float(grid_radius),
-                                       SIGMOID[sigmoid_kind], BG[bg], _ptr(alpha), _ptr(weights), _ptr(out), _stream()))
-    return out, alpha, weights
+    return _voxel_render_rayts("sh", rays, ts_ray, densities, rgb, grid_radius, order, sigmoid_kind, bg, want_weights)
 
 
 def voxel_fine_lanes(head: str, lanes: int, rays: torch.Tensor, ts: torch.Tensor, densities: torch.Tensor, rgb: Optional[torch.Tensor],
@@ -2045,10 +1995,6 @@ def voxel_fine_lanes(head: str, lanes: int, rays: torch.Tensor, ts: torch.Tensor
 
 
 # ------------------------------------------------------------------------------------------------- NeRFVoxel.sparsify (csrc/voxel_sparse.hip)
-VOXEL_SPARSE_LANES = 16      # lanes per ray of the shipped sparse renderer (DESIGN.md 3w)
-VOXEL_DEAD_DENSITY = -1e30   # what a dead sample's density column is masked to: finite, and fast_softplus(-1e30 - 1) is 0
-
-
 def voxel_d_thresh(thresh: float) -> float:
     """The raw density whose softplus(d - 1) equals `thresh`, 1 + log(expm1(thresh)) in Python doubles rounded once to fp32; -inf for
     thresh == 0 (every voxel is kept).  thresh < 0 or not finite raises ValueError."""
@@ -2081,8 +2027,7 @@ def voxel_live_table(densities: torch.Tensor, thresh: float, want_count: bool = 
     S = densities.shape[0]
     if tuple(densities.shape) not in ((S, S, S, 1), (S, S, S)):
         raise ValueError(f"the density grid must be [S,S,S,1], got {tuple(densities.shape)}")
-    if S % 2 != 0 or S < 2:
-        raise ValueError(f"voxel resolution {S}: even resolutions only (the reference's ids are floor(.) + S / 2)")
+    _voxel_even(S)
     d = voxel_d_thresh(thresh)
     live = torch.empty((S, S, S), device=densities.device, dtype=torch.uint8)
     count = torch.empty(1, device=densities.device, dtype=torch.int64) if want_count else None
@@ -2144,17 +2089,11 @@ def voxel_sparse_render(head: str, rays: torch.Tensor, ts: torch.Tensor, densiti
     gathering and walking only the samples the table `live` (uint8 [S,S,S], ops.voxel_live_table) marks: a dead sample has alpha =
     weight = 0 exactly and its colour is not read.  With a table of ones: voxel_*_render_rayts bit for bit.  Outputs of voxel_render_rayts."""
     lib = _lib.load()
-    if head == "rgb":
-        densities, rgb, S, _ = _voxel_grid(densities, rgb)
-        if rgb.shape[-1] != 3:
-            raise ValueError(f"voxel_sparse_render: the rgb head has 3 colour parameters per voxel, got {rgb.shape[-1]}")
-        order = -1
-    elif head == "plv":
-        densities, rgb, S, order = _voxel_plv_grid(densities, rgb)
-    elif head == "sh":
-        densities, rgb, S, _ = _voxel_sh_grid(densities, rgb, order)
-    else:
+    if head not in ("rgb", "plv", "sh"):
         raise ValueError(f"voxel_sparse_render: head {head!r} (rgb, plv, sh)")
+    densities, rgb, S, Cn, order = _voxel_head(head, densities, rgb, order)
+    if head == "rgb" and Cn != 3:
+        raise ValueError(f"voxel_sparse_render: the rgb head has 3 colour parameters per voxel, got {Cn}")
     live = _voxel_live(live, S, densities.device)
     rays, ts = _f32(rays, "rays"), _f32(ts, "ts")
     shared = ts.dim() == 1  # (one row for every ray)
@@ -2302,15 +2241,10 @@ def dyn_voxel_render(rays: torch.Tensor, t: torch.Tensor, ts: torch.Tensor, dens
     plv: the canonical model carries the pos-linear-view head (rgb [S,S,S, 3 + (order+1)^2]; na_dyn_voxel_plv_render, the composition
     then being over voxel_plv_render).  sh_order: it carries the spherical-harmonic colour head of that order (rgb [S,S,S, 3 (order+1)^2];
     na_dyn_voxel_sh_render, the composition over voxel_sh_render)."""
-    lib = _lib.load()
-    if sh_order is not None:
-        if plv:
-            raise ValueError("dyn_voxel_render: plv and sh_order name two different heads")
-        densities, rgb, S, Cn = _voxel_sh_grid(densities, rgb, sh_order)
-    elif plv:
-        densities, rgb, S, Cn = _voxel_plv_grid(densities, rgb)  # (Cn: the order)
-    else:
-        densities, rgb, S, Cn = _voxel_grid(densities, rgb)
+    if sh_order is not None and plv:
+        raise ValueError("dyn_voxel_render: plv and sh_order name two different heads")
+    kind = "sh" if sh_order is not None else "plv" if plv else "rgb"
+    densities, rgb, S, Cn, order = _voxel_head(kind, densities, rgb, sh_order)
     ctrl, rig, S2 = _dyn_voxel_grids(ctrl_pts_grid, rigidity_grid, spline)
     if S2 != S:
         raise ValueError(f"the canonical grids are {S}^3 and the deformation grids {S2}^3")
@@ -2330,9 +2264,8 @@ def dyn_voxel_render(rays: torch.Tensor, t: torch.Tensor, ts: torch.Tensor, dens
                         ("alpha", (T,) + batch), ("weights", (T,) + batch)):
         if name in want:
             res[name] = new(*shape)
-    entry = lib.na_dyn_voxel_sh_render if sh_order is not None else lib.na_dyn_voxel_plv_render if plv else lib.na_dyn_voxel_render
-    head = (Cn, sh_order) if sh_order is not None else (Cn,)
-    check(entry(_ptr(rays), _ptr(t), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), _ptr(ctrl), _ptr(rig), S, *head, spline, float(grid_radius),
+    fn, head = _voxel_abi(kind, Cn, order)
+    check(fn["dyn_render"](_ptr(rays), _ptr(t), R, _ptr(ts), T, _ptr(densities), _ptr(rgb), _ptr(ctrl), _ptr(rig), S, *head, spline, float(grid_radius),
                 SIGMOID[sigmoid_kind], BG[bg], _ptr(res["rgb"]), *(_ptr(res.get(name)) for name in DYN_VOXEL_MAPS), _stream()))
     return res
 

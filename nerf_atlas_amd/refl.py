@@ -114,7 +114,7 @@ class PosLinearView(Reflectance):
 
     def pos_linear_voxel_forward(self, params, view, sh=None):
         """src/refl.py:265-272: act(raw rgb) * (sigmoid(eval_sh(order, coefficients, normalize(view))) / 2 + 0.5).  NeRFVoxel's lookup
-        contracts the coefficients with the ray's basis itself (csrc/voxel_plv.hip), so `params` are the 3 interpolated colour
+        contracts the coefficients with the ray's basis itself (csrc/voxel.hip), so `params` are the 3 interpolated colour
         parameters and `sh` the expansion in front of the sigmoid; the combination is pos_linear_combine's kernel."""
         if sh is None:
             raise ValueError("the pos-linear-view voxel head is evaluated by NeRFVoxel's lookup (ops.voxel_plv_sample): pass its `sh`")
@@ -164,7 +164,7 @@ class SphericalHarmonic(Reflectance):
       plain    training, or one direction per sample: the MLP through SkipConnMLP's own paths, then the expansion as one kernel
                (autograd.ShShadeFn / ops.sh_shade).
     The per-voxel form (`to_voxel`, --voxel-sh-order K) has no MLP: the grid holds 3 (K+1)^2 coefficients per voxel and
-    NeRFVoxel's lookup contracts them with the ray's basis (csrc/voxel_sh.hip)."""
+    NeRFVoxel's lookup contracts them with the ray's basis (csrc/voxel.hip)."""
 
     def __init__(self, space=None, order: int = 2, view="elaz", voxel_order=None, **kwargs):
         super().__init__(**kwargs)

@@ -1,4 +1,4 @@
-"""--model voxel --refl-kind pos-linear-view --voxel-refl-order K on the GPU (csrc/voxel_plv.hip): the lookup with the head, its scatter
+"""--model voxel --refl-kind pos-linear-view --voxel-refl-order K on the GPU (csrc/voxel.hip): the lookup with the head, its scatter
 in both accumulation modes and both table variants, its position gradient and the one-launch eval route against tests/voxel_plv_ref.py
 (membership fixed in fp32, everything behind it in fp64), and the model on both routes against the recorded reference (g27).  Bounds:
 voxel_plv_ref's derived ones for the operators (worst |err| / bound printed), the project's 1e-4 for everything composited."""

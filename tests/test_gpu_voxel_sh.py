@@ -1,4 +1,4 @@
-"""--model voxel --refl-kind sph-har --voxel-sh-order K on the GPU (csrc/voxel_sh.hip): the lookup with the head, its scatter in both
+"""--model voxel --refl-kind sph-har --voxel-sh-order K on the GPU (csrc/voxel.hip): the lookup with the head, its scatter in both
 accumulation modes and both table geometries, its position gradient and the one-launch eval route.  Operators against
 tests/voxel_sh_ref.py (membership fixed in fp32, everything behind it in fp64) within its derived bounds (worst |err| / bound printed; an
 entry with bound 0 must be exact); the ties to the pinned kernels and the eval route against the operator composition bit for bit."""

@@ -1,4 +1,4 @@
-"""Plain reference of NeRFVoxel's lookup with the per-voxel pos-linear-view head (csrc/voxel_plv.hip; src/refl.py:265-280 over
+"""Plain reference of NeRFVoxel's lookup with the per-voxel pos-linear-view head (csrc/voxel.hip; src/refl.py:265-280 over
 src/nerf.py:493-524 of the reference), its scatter, its position gradient and the model, with the error bounds the tests hold the
 kernels to.  Imported by tests/test_voxel_plv_ref.py (CPU) and the GPU tests of the head.
 

@@ -1,4 +1,4 @@
-"""Plain reference of NeRFVoxel's lookup with the per-voxel spherical-harmonic colour head (csrc/voxel_sh.hip; the intended form of
+"""Plain reference of NeRFVoxel's lookup with the per-voxel spherical-harmonic colour head (csrc/voxel.hip; the intended form of
 src/refl.py:715-722 over src/nerf.py:493-524 of the reference), its scatter, its position gradient, the head and the model, with the
 error bounds the tests hold the kernels to.  Imported by tests/test_voxel_sh_ref.py (CPU) and the GPU tests of the head.
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times of the pos-linear-view voxel head on the GPU (csrc/voxel_plv.hip, na_dyn_voxel_plv_render), written to
+"""Times of the pos-linear-view voxel head on the GPU (csrc/voxel.hip, na_dyn_voxel_plv_render), written to
 profiles/voxel_plv/bench.json.
 
     python tools/voxel_plv_bench.py [--reps 9] [--inner 20] [--out profiles/voxel_plv]
@@ -11,7 +11,7 @@ the 64 x 64 x 80 test tile with all maps.
 
 "torch" rows are what a user would otherwise run: a plain-PyTorch restatement of the reference's head (advanced indexing of [N, 29]
 per corner, eval_sh restated from its closed forms, autograd), written for this tool and run on the same GPU in fp32 -- never a kernel
-of this project.  Both scatter variants (csrc/voxel_plv.hip: 1 whole rows in the LDS table, 2 leading sums in the table and the
+of this project.  Both scatter variants (csrc/voxel.hip: 1 whole rows in the LDS table, 2 leading sums in the table and the
 coefficient block straight to memory) are timed in both accumulation modes; the shipped one is NA_PLV_SCATTER's.
 """
 import argparse

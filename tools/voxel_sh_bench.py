@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times of the spherical-harmonic voxel head on the GPU (csrc/voxel_sh.hip, na_dyn_voxel_sh_render), written to
+"""Times of the spherical-harmonic voxel head on the GPU (csrc/voxel.hip, na_dyn_voxel_sh_render), written to
 profiles/voxel_sh/bench.json.
 
     python tools/voxel_sh_bench.py [--reps 9] [--inner 20] [--out profiles/voxel_sh]
